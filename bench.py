@@ -7,7 +7,11 @@ One step = encode+decode of one batch of synthetic 256×256×3 images per GPU, N
 with inputs already resident in HBM. Images shard by batch across ranks (no collective in the
 data path; "weak" scaling). Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+A plain run sets up, warms up, times the K steps and prints the line. --full adds what the
+headline does not need (the bf16 and x6 legs, the per-layer pass and its roofline, the CPU
+baseline); --dump-outputs DIR writes the last timed step's results as DIR/<name>.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -359,7 +363,10 @@ def run_train(args, net, x, world, dev):
     torch.cuda.synchronize()
     elapsed = idist.max_over_ranks(time.perf_counter() - t0, dev)
     ms = elapsed / args.steps * 1e3
-    comm = allreduce_overlap(args, net, params, opt, reducer, step, ms, dev) if world > 1 else None
+    if args.dump_outputs and idist.rank() == 0:   # before --full's overlap legs step any further
+        dump_outputs(args.dump_outputs, {"bpp": bpp.reshape(1)})
+    comm = (allreduce_overlap(args, net, params, opt, reducer, step, ms, dev)
+            if world > 1 and args.full else None)
     if loader is not None:
         loader.close()
         data_info["step_crops_per_s"] = round(B * args.steps / elapsed, 1)
@@ -591,6 +598,8 @@ def run_kodak(args, dev):
                 ref = torch.from_numpy(yd[f"yhat_{i:02d}"].astype(np.float32)).to(dev)
                 rows[i][len(keys)] = float((ev["y_hat"] != ref).sum().item())
     t = kodak_table(rows, len(keys) + 1, dev)
+    if args.dump_outputs and rank == 0:   # the last timed step's per-image bpp / PSNR / MS-SSIM
+        dump_outputs(args.dump_outputs, {"per_image_metrics": torch.from_numpy(t[:, :len(keys)].copy())})
     per = {i: {k: float(t[i, c]) for c, k in enumerate(keys)} for i in range(24)}
     rel = {k: max(abs(per[i][k] - meta["images"][i][k]) / abs(meta["images"][i][k]) for i in range(24))
            for k in keys}
@@ -659,9 +668,11 @@ def run_codec(args, dev):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            q, words, y, _ = step(timed=True)
+            q, words, y, clipped = step(timed=True)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"y_hat": y, "clipped": clipped})
         if not torch.equal(y, q["y_hat"]):
             raise SystemExit("codec bench: decoded latents differ from the encoded ones")
         bits, _ = kernels.reduce_partials(q["bits_partial"])
@@ -721,6 +732,8 @@ def run_encdec(args, dev):
             y_hat, recon = step(timed=True)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"y_hat": y_hat, "recon": recon})
         _, fwd_yhat, _ = net(x)
         same = bool(torch.equal(y_hat, fwd_yhat))
     enc_ms = float(np.mean([a.elapsed_time(b) for a, b in t_enc]))
@@ -811,6 +824,30 @@ def cpu_baseline_train(N: int, S: int, budget_s: float) -> dict:
                       f"N={N}, fp32 torch CPU, {cores} threads ({dt:.1f} s)"}
 
 
+DUMP_BUDGET = 64 * 10 ** 6 - 4096   # array bytes of one --dump-outputs (64 MB less the .npy headers)
+
+
+def dump_outputs(d: str, outputs: dict) -> None:
+    """--dump-outputs: every tensor of `outputs` as d/<name>.npy, float32 (float64 stays). When
+    they exceed DUMP_BUDGET together, each array larger than an equal share of it is written as
+    a 1-D sample of its flattened elements, at sorted indices drawn with a fixed seed (the same
+    indices for the same shape, so two builds' dumps compare element for element)."""
+    os.makedirs(d, exist_ok=True)
+
+    def size(t):
+        return t.numel() * (8 if t.dtype == torch.float64 else 4)
+    total = sum(size(t) for t in outputs.values())
+    share = DUMP_BUDGET // max(len(outputs), 1)
+    for name, t in outputs.items():
+        t = t.detach()
+        if total > DUMP_BUDGET and size(t) > share:
+            n = share // (8 if t.dtype == torch.float64 else 4)
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), n))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        t = t if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(d, name + ".npy"), t.cpu().numpy())
+
+
 def lib_sha() -> str:
     import hashlib
     from iclr_17_compression_amd import _lib
@@ -851,14 +888,26 @@ def pmc_traffic(layer: str, N: int, S: int, B: int, prec: str):
     return None, why, None
 
 
-def time_eval(net, x, args, world, dev) -> dict:
-    """W warm-up steps, then K timed steps between barrier + synchronize brackets, then a second
-    pass of K steps with HIP-event brackets per layer on the launching stream (outside the
-    wall-clock region, so the brackets cannot perturb it). Elapsed is the max over ranks."""
+CLOCK_RAMP_S = 0.3   # the GPU clock ramps over the first ~50 ms of load (tools/warm_probe.py)
+
+
+def time_eval(net, x, args, world, dev, per_layer: bool = True, ramp: bool = False) -> dict:
+    """W warm-up steps, then K timed steps between barrier + synchronize brackets; "outputs" is
+    what the last timed step returned. per_layer (--full) adds a second pass of K steps with
+    HIP-event brackets per layer on the launching stream (outside the wall-clock region, so the
+    brackets cannot perturb it). ramp: CLOCK_RAMP_S of the same step before the warm-up, so that
+    the timed region starts at steady clocks when no other leg has run before it (--full: the
+    bf16 leg has). Elapsed is the max over ranks."""
     step = Step(net, x)
     streams = args.bf16_streams if kernels.precision() == "bf16" else args.streams
     with torch.no_grad():
-        run = SplitStep(net, x, streams) if streams > 1 else step
+        split = SplitStep(net, x, streams) if streams > 1 else None
+        run = split or step
+        if ramp:
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < CLOCK_RAMP_S:
+                run()
+                torch.cuda.synchronize()
         for _ in range(args.warmup):
             run()
         torch.cuda.synchronize()
@@ -883,22 +932,33 @@ def time_eval(net, x, args, world, dev) -> dict:
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
-        if run is not step:   # the one-stream step of the per-layer pass, warm
-            for _ in range(3):
-                step()
-        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(8)] for _ in range(args.steps)]
-        for i in range(args.steps):
-            clipped, y_hat, bpp = step(evs[i])
-        torch.cuda.synchronize()
-        B, _, H, W = x.shape
-        bits, _ = kernels.reduce_partials(step.last_partial)
-    per_layer_ms = {name: float(np.mean([evs[i][j].elapsed_time(evs[i][j + 1]) for i in range(args.steps)]))
-                    for j, name in enumerate(LAYERS)}
+        # the last timed step's results (a graph replays into the tensors of its capture); split
+        # over streams: the parts' images and latents joined, one bpp per part
+        outs = [p.out for p in split.parts] if split else [step.out]
+        clipped, y_hat = (torch.cat([o[i] for o in outs]) for i in (0, 1))
+        bpps = torch.stack([o[2].reshape(()) for o in outs])
+        res = {"bpp": bpps.mean(), "clipped": clipped, "y_hat": y_hat,
+               "outputs": {"clipped": clipped, "y_hat": y_hat, "bpp": bpps}}
+        if per_layer:
+            if run is not step:   # the one-stream step of the per-layer pass, warm
+                for _ in range(3):
+                    step()
+            evs = [[torch.cuda.Event(enable_timing=True) for _ in range(8)] for _ in range(args.steps)]
+            for i in range(args.steps):
+                clipped, y_hat, bpp = step(evs[i])
+            torch.cuda.synchronize()
+            B, _, H, W = x.shape
+            bits, _ = kernels.reduce_partials(step.last_partial)
+            res.update({"bpp": bpp, "clipped": clipped, "y_hat": y_hat,
+                        "bpp_img": (bits / (H * W)).double(),
+                        "per_layer_ms": {name: float(np.mean([evs[i][j].elapsed_time(evs[i][j + 1])
+                                                              for i in range(args.steps)]))
+                                         for j, name in enumerate(LAYERS)}})
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    return {"elapsed": t.item(), "per_layer_ms": per_layer_ms, "bpp": bpp, "clipped": clipped,
-            "y_hat": y_hat, "bpp_img": (bits / (H * W)).double()}
+    res["elapsed"] = t.item()
+    return res
 
 
 def roofline(per_layer_ms: dict, prec: str, N: int, S: int, B: int):
@@ -1031,8 +1091,15 @@ def main() -> None:
                          "the multi-rank plumbing on a host without a GPU")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--N", type=int, default=192)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: eval — the bf16 and x6 legs, "
+                         "the per-layer pass with its roofline, the CPU baseline; train — the CPU "
+                         "baseline and (N > 1) the all-reduce overlap")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy "
+                         "(float32; at most 64 MB in all, a fixed seeded sample of a larger array)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU leg")
     ap.add_argument("--kodak-set", choices=tuple(KODAK_SETS), default="g9",
                     help="kodak mode: the operating point (g9 trained, g5 trained-like)")
     ap.add_argument("--train-dir", default="",
@@ -1052,7 +1119,7 @@ def main() -> None:
                     help="the same for the bf16 leg / --precision bf16")
     ap.add_argument("--graph", action="store_true",
                     help="eval: replay the timed steps from one HIP graph instead of launching them "
-                         "kernel by kernel (slower than eager: bf16 12 % in round 4, profiles/r04_ab_streams.log; x6 4 % in round 3)")
+                         "kernel by kernel (slower than eager: bf16 12 %% in round 4, profiles/r04_ab_streams.log; x6 4 %% in round 3)")
     ap.add_argument("--mode", choices=("eval", "train", "kodak", "codec", "encdec"), default="eval")
     ap.add_argument("--precision", choices=kernels.PRECISIONS, default=None,
                     help="inference contraction mode (default: ICLR17_PRECISION or x6)")
@@ -1137,7 +1204,7 @@ def main() -> None:
         result.update(layout)
         if args.global_batch:
             result["scaling"] = "strong"
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU leg: N=1 only
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU leg: N=1 only
             result["cpu_baseline"] = cpu_baseline_train(N, min(S, 256), args.cpu_budget)
         if rank == 0:
             print(json.dumps(result), flush=True)
@@ -1146,7 +1213,7 @@ def main() -> None:
         return
     prec = kernels.precision()
     rb = None
-    if prec in ("x6", "h3") and not args.no_bf16_leg:
+    if args.full and prec in ("x6", "h3") and not args.no_bf16_leg:
         # the bf16 throughput-mode leg runs first (reported as bf16_mode below). Its step is 4x
         # shorter and the GPU clock ramps over the first ~50 ms of load (tools/warm_probe.py:
         # bf16 0.567 → 0.465 ms, x6 2.49 → 2.06 ms per step), so it warms for at least 100 steps
@@ -1159,10 +1226,13 @@ def main() -> None:
                            world, dev)
         finally:
             kernels.set_precision(prec)
-    r = time_eval(net, x, args, world, dev)
+    # a plain run has no leg before the headline: it ramps the clock on the headline's own step
+    r = time_eval(net, x, args, world, dev, per_layer=args.full, ramp=not args.full)
     kernels.check_finite("bench bpp", r["bpp"])   # h3: NaN when an activation did not fit the form
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r["outputs"])
     rx = None
-    if prec == "h3" and not args.no_x6_leg:
+    if args.full and prec == "h3" and not args.no_x6_leg:
         # the x6 mode (full fp32 operands: an exact three-part bf16 split, six products per MAC)
         # on the same batch after the headline, so that a full-fp32-operand rate stays timed on
         # the driver's box next to the h3 one (reported as x6_mode below)
@@ -1172,13 +1242,11 @@ def main() -> None:
         finally:
             kernels.set_precision(prec)
     nstreams = args.bf16_streams if prec == "bf16" else args.streams
-    elapsed, per_layer_ms, bpp = r["elapsed"], r["per_layer_ms"], r["bpp"]
+    elapsed, bpp = r["elapsed"], r["bpp"]
     pixels = world * B * S * S * args.steps
     value = pixels / elapsed / 1e6
     ms_per_step = elapsed / args.steps * 1e3
     flops = layer_flops(N, S, S)
-    bytes_ = layer_bytes(N, S, S, 2 if prec == "bf16" else 4)
-    dominant, layers, roof = roofline(per_layer_ms, prec, N, S, B)
     total_flops = sum(flops.values()) * B
     result = {
         "metric": METRIC,
@@ -1205,12 +1273,16 @@ def main() -> None:
                    "launch": ("hipGraph replay of the whole step" if args.graph else
                               "eager (kernel by kernel)" + (f", batch split over {nstreams} HIP streams"
                                                             if nstreams > 1 else ""))},
-        "roofline": {**roof, "algorithmic_bytes_per_launch": bytes_[dominant] * B,
-                     "flop_per_launch": flops[dominant] * B,
-                     "whole_step_tflops": round(total_flops / (ms_per_step * 1e-3) / 1e12, 2)},
-        "layers": layers,
+        "whole_step_tflops": round(total_flops / (ms_per_step * 1e-3) / 1e12, 2),
         "bpp_last": round(bpp.item(), 6),
     }
+    if args.full:   # the per-layer pass: the dominant kernel's roofline and the layer table
+        bytes_ = layer_bytes(N, S, S, 2 if prec == "bf16" else 4)
+        dominant, layers, roof = roofline(r["per_layer_ms"], prec, N, S, B)
+        result["roofline"] = {**roof, "algorithmic_bytes_per_launch": bytes_[dominant] * B,
+                              "flop_per_launch": flops[dominant] * B,
+                              "whole_step_tflops": result.pop("whole_step_tflops")}
+        result["layers"] = layers
     if rb is not None:
         # the bf16 throughput mode on the same batch: rate, roofline, and its deviation from the
         # parity mode's (fp32-accurate) results — latent flips, Δbpp, ΔPSNR
@@ -1251,7 +1323,7 @@ def main() -> None:
                             "max_abs_rel_dbpp_per_image": float(((rx["bpp_img"] - r["bpp_img"]).abs()
                                                                  / r["bpp_img"].abs()).max())},
         }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU leg: N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU leg: N=1 only
         # per-pixel cost is size-independent: the sample is 256² images at any --size
         result["cpu_baseline"] = cpu_baseline(N, min(S, 256), min(S, 256), args.cpu_budget)
     if rank == 0:

@@ -84,6 +84,30 @@ def test_chain_roofline(tmp_path, monkeypatch):
             assert bounds["conv2_gdn2"] == "mfma" and bounds["deconv2_igdn2"] == "mfma"
 
 
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per output (float64 stays), whole while everything fits
+    the budget; over it, an array larger than its equal share becomes a 1-D sample of its
+    elements at the same (seeded) indices every time, and the files stay within the budget."""
+    import numpy as np
+    import torch
+    outs = {"a": torch.arange(1000, dtype=torch.float32).reshape(10, 100) * 0.5,
+            "b": torch.tensor([1.5], dtype=torch.float64),
+            "c": torch.arange(6, dtype=torch.bfloat16)}
+    bench.dump_outputs(str(tmp_path / "whole"), outs)
+    got = {k: np.load(tmp_path / "whole" / f"{k}.npy") for k in outs}
+    assert got["a"].dtype == np.float32 and np.array_equal(got["a"], outs["a"].numpy())
+    assert got["b"].dtype == np.float64 and got["b"].tolist() == [1.5]
+    assert got["c"].dtype == np.float32 and got["c"].tolist() == [0, 1, 2, 3, 4, 5]
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1200)   # a: 4000 bytes against a share of 400
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    s1, s2 = (np.load(tmp_path / d / "a.npy") for d in ("s1", "s2"))
+    assert s1.shape == (100,) and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) >= 0) and np.isin(s1, outs["a"].numpy()).all() and len(set(s1)) > 50
+    assert np.array_equal(np.load(tmp_path / "s1" / "c.npy"), got["c"])
+    assert sum(np.load(tmp_path / "s1" / f"{k}.npy").nbytes for k in outs) <= 1200
+
+
 def _run_bench(args, env_extra, timeout=240):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}

@@ -22,7 +22,7 @@ step() {  # step <name> <timeout-s> <cmd...>
 if [ "${TESTS:-1}" != "0" ]; then
   step gpu_tests 700 python -u -m pytest tests -m gpu -q -s -p no:cacheprovider --timeout 300 --timeout-method thread -rf
 fi
-step bench 300 python bench.py
+step bench 300 python bench.py --full
 grep '^{' "$O/bench.log" | tail -1 > "$O/${P}_bench.json"
 if [ "${BENCHES:-1}" != "0" ]; then
   for i in 1 2 3; do

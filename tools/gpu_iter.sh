@@ -21,7 +21,7 @@ if [ "${TESTS:-1}" != "0" ]; then
   step tests 600 python -u -m pytest ${TESTSEL:-tests} -m gpu -x -q -p no:cacheprovider --timeout 120 --timeout-method thread || exit 1
 fi
 [ "${X6CHECK:-1}" = "1" ] && { step x6_check 300 python tools/x6_check.py || exit 1; }
-step bench 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} || exit 1
+step bench 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} || exit 1
 if [ -n "${VARIANTS:-}" ]; then
   for v in $VARIANTS; do
     n=${v%%:*}; f=${v#*:}; f=${f//,/ }; d=/tmp/ab_$n; mkdir -p $d
@@ -34,7 +34,7 @@ if [ -n "${VARIANTS:-}" ]; then
   for r in $(seq ${ROUNDS:-2}); do
     for v in $VARIANTS; do
       n=${v%%:*}
-      ICLR17_LIB=/tmp/ab_$n/libiclr17.so step ab_${n}_$r 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} || exit 1
+      ICLR17_LIB=/tmp/ab_$n/libiclr17.so step ab_${n}_$r 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} || exit 1
       python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['value'], {k: v['ms'] for k, v in d.get('layers', {}).items()})" "$O/ab_${n}_$r.log" $n | tee -a "$O/ab.txt"
     done
   done

@@ -29,5 +29,5 @@ for e in ${ENVS:-base:}; do
   done
 done
 if [ "${BENCH:-1}" != "0" ]; then
-  step bench 300 python bench.py ${BENCH_ARGS:-}
+  step bench 300 python bench.py --full ${BENCH_ARGS:-}
 fi
