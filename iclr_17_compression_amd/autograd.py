@@ -375,6 +375,67 @@ class CodecTrainFn(torch.autograd.Function):
         return (dx, None, None, *grads)
 
 
+class MsSsimFn(torch.autograd.Function):
+    """Per-image MS-SSIM [B] (kernels.ms_ssim, bitwise) with its backward: the forward keeps the
+    derivative maps in a workspace (with the dY maps only when Y needs a gradient), the backward
+    computes the gradients ``needs_input_grad`` asks for and drops the workspace."""
+
+    @staticmethod
+    def forward(ctx, X, Y, data_range):
+        ctx.set_materialize_grads(False)
+        x, y = X.contiguous(), Y.contiguous()
+        ctx.saved_dy = bool(ctx.needs_input_grad[1])
+        out, ctx.ws = kernels.ms_ssim_fwd_saved(x, y, data_range, want_dy=ctx.saved_dy)
+        ctx.save_for_backward(x, y)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            ctx.ws = None
+            return None, None, None
+        if ctx.ws is None:
+            raise RuntimeError("iclr17: ms_ssim_diff was already differentiated (its workspace is "
+                               "dropped after the backward)")
+        x, y = ctx.saved_tensors
+        dx, dy = kernels.ms_ssim_bwd(x, y, ctx.ws, g, ctx.saved_dy,
+                                     want_dx=ctx.needs_input_grad[0],
+                                     want_dy=ctx.needs_input_grad[1])
+        ctx.ws = None
+        return dx, dy, None
+
+
+class SsimFn(torch.autograd.Function):
+    """Per-image single-scale (ssim [B], cs [B]) (kernels.ssim, bitwise) with its backward."""
+
+    @staticmethod
+    def forward(ctx, X, Y, data_range):
+        ctx.set_materialize_grads(False)
+        x, y = X.contiguous(), Y.contiguous()
+        ctx.saved_dy = bool(ctx.needs_input_grad[1])
+        s, cs, ctx.ws = kernels.ssim_fwd_saved(x, y, data_range, want_dy=ctx.saved_dy)
+        ctx.save_for_backward(x, y)
+        return s, cs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_ssim, g_cs):
+        if (g_ssim is None and g_cs is None) or \
+                not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            ctx.ws = None
+            return None, None, None
+        if ctx.ws is None:
+            raise RuntimeError("iclr17: ssim_diff was already differentiated (its workspace is "
+                               "dropped after the backward)")
+        x, y = ctx.saved_tensors
+        dx, dy = kernels.ssim_bwd(x, y, ctx.ws, g_ssim, g_cs, ctx.saved_dy,
+                                  want_dx=ctx.needs_input_grad[0],
+                                  want_dy=ctx.needs_input_grad[1])
+        ctx.ws = None
+        return dx, dy, None
+
+
 class AnalysisFn(torch.autograd.Function):
     """Analysis_net_17.forward with autograd: y, contiguous NCHW, from the codec's own analysis
     kernels (``Analysis_net_17.y_nhwc``), so round(y) is the codec's ŷ with grad on or off."""

@@ -16,6 +16,10 @@
 //   ms_ssim = Π_{l<4} (cs_l^w_l · ssim_4^w_4)
 // exactly as ms_ssim_torch.py:189-190 does (the last level's ssim enters every factor; its cs is
 // unused).
+//
+// The gradient path (the loss λ·(1 − MS-SSIM) + bpp; "Backward" below): saving variants of the
+// level kernel also write the per-pixel derivative maps, and one backward kernel per level, from
+// the coarsest up, turns them into dX / dY.
 #include <string.h>
 
 #include "common.h"
@@ -59,10 +63,17 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// SAVE (the gradient path, see "Backward" below): bit 0 also writes the per-pixel derivatives of
+// the cs map, bit 1 those of the ssim map, to dcs / dss as planes [map][plane][Ho][Wo] with
+// map 0 = ∂/∂mx, 1 = ∂/∂exx (= ∂/∂eyy), 2 = ∂/∂exy and, with want_dy, 3 = ∂/∂my. SAVE = 0 is the
+// evaluation kernel; the partial sums and their arithmetic are the same in every variant.
+template <int SAVE>
 __global__ void __launch_bounds__(256, 2) ssim_level_kernel(const float* __restrict__ X,
                                                             const float* __restrict__ Y, int H,
                                                             int W, float c1, float c2,
-                                                            double* __restrict__ partial) {
+                                                            double* __restrict__ partial,
+                                                            float* __restrict__ dcs,
+                                                            float* __restrict__ dss, int want_dy) {
   __shared__ __attribute__((aligned(16))) float sx[IH * IWP], sy[IH * IWP];
   __shared__ __attribute__((aligned(16))) float h[5][IH][TOW];
   __shared__ double red[2][4];
@@ -151,6 +162,27 @@ __global__ void __launch_bounds__(256, 2) ssim_level_kernel(const float* __restr
       const float ssim = ((2.0f * mxy + c1) / (mxx + myy + c1)) * cs;
       s_ssim += (double)ssim;
       s_cs += (double)cs;
+      if constexpr (SAVE != 0) {
+        const float D = vx + vy + c2, E = mxx + myy + c1;
+        const float L = (2.0f * mxy + c1) / E;
+        const float c_exy = 2.0f / D, c_exx = -cs / D;
+        const float c_mx = (2.0f * cs * mx - 2.0f * my) / D;
+        const float c_my = (2.0f * cs * my - 2.0f * mx) / D;
+        const long ms = (long)gridDim.z * Ho * Wo;   // one map of every plane
+        const long at = ((long)plane * Ho + (r0 + rs + j)) * Wo + (c0 + lane);
+        if constexpr ((SAVE & 1) != 0) {
+          dcs[at] = c_mx;
+          dcs[ms + at] = c_exx;
+          dcs[2 * ms + at] = c_exy;
+          if (want_dy) dcs[3 * ms + at] = c_my;
+        }
+        if constexpr ((SAVE & 2) != 0) {
+          dss[at] = cs * (2.0f * my - 2.0f * L * mx) / E + L * c_mx;
+          dss[ms + at] = L * c_exx;
+          dss[2 * ms + at] = L * c_exy;
+          if (want_dy) dss[3 * ms + at] = cs * (2.0f * mx - 2.0f * L * my) / E + L * c_my;
+        }
+      }
     }
   }
   s_ssim = wave_sum_d(s_ssim);
@@ -262,6 +294,152 @@ __global__ void __launch_bounds__(256) ssim_finish_kernel(const double* __restri
   }
 }
 
+// ------------------------------------------------------------------------------- Backward
+// The saving forward (ssim_level_kernel<SAVE>) leaves, per level, the per-pixel derivatives of the
+// map whose mean enters the result (cs for levels 0-3, ssim for level 4; both for single-scale
+// SSIM). The upstream gradient on a map is one scalar per image (coef), so
+//   dX(q) = (Gᵀ d_mx)(q) + 2·X(q)·(Gᵀ d_exx)(q) + Y(q)·(Gᵀ d_exy)(q)         (dY: x ↔ y, d_eyy = d_exx)
+// with Gᵀ the 'full' separable correlation of the Ho×Wo map (zero outside) into H×W; the window is
+// symmetric, so it is the forward's 'valid' filter over the zero-padded map. Nothing is scattered:
+// every sum has a fixed order and the gradients are bitwise reproducible.
+
+// coef[l][b] = g[b] · ∂M/∂mean_l / (3·Ho_l·Wo_l) for M = Π_{l<4} (C_l^{w_l} · S_4^{w_4}), chained
+// as torch differentiates prod (M / t_l), mul and pow (w·v^{w−1}), in double from the fp32 means
+// the forward used. Nothing is clamped: a non-positive mean gives NaN, as in the reference.
+__global__ void msssim_coef_kernel(const double* __restrict__ means /* [L][B][2] */,
+                                   const float* __restrict__ g, const FinishPlan pl, int B,
+                                   float* __restrict__ coef /* [L][B] */) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const double w4 = (double)c_msssim_w[LEVELS - 1];
+  const double s = (double)(float)means[((long)(LEVELS - 1) * B + b) * 2];
+  const double sp = pow(s, w4);
+  double a[LEVELS - 1], t[LEVELS - 1], M = 1.0;
+  for (int l = 0; l < LEVELS - 1; ++l) {
+    a[l] = pow((double)(float)means[((long)l * B + b) * 2 + 1], (double)c_msssim_w[l]);
+    t[l] = a[l] * sp;
+    M *= t[l];
+  }
+  const double gb = (double)g[b];
+  double dsp = 0.0;
+  for (int l = 0; l < LEVELS - 1; ++l) {
+    const double gt = gb * (M / t[l]);
+    const double cs = (double)(float)means[((long)l * B + b) * 2 + 1], w = (double)c_msssim_w[l];
+    coef[(long)l * B + b] = (float)(gt * sp * (w * pow(cs, w - 1.0)) / pl.count[l]);
+    dsp += gt * a[l];
+  }
+  coef[(long)(LEVELS - 1) * B + b] = (float)(dsp * (w4 * pow(s, w4 - 1.0)) / pl.count[LEVELS - 1]);
+}
+
+// Single-scale: coef[0][b] = g_ssim[b] / count, coef[1][b] = g_cs[b] / count (a null g: unused).
+__global__ void ssim_coef_kernel(const float* __restrict__ g_ssim, const float* __restrict__ g_cs,
+                                 double count, int B, float* __restrict__ coef /* [2][B] */) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  if (g_ssim) coef[b] = (float)((double)g_ssim[b] / count);
+  if (g_cs) coef[B + b] = (float)((double)g_cs[b] / count);
+}
+
+// One level of the backward: a workgroup owns a 16×64 tile of dX (and dY) of one plane. Per map it
+// stages the 26×74 window of the derivative map (tile + 10 rows above / columns left, zero outside
+// the map), scaled by the image's coefficient (two sets, DA·ca + DB·cb, when single-scale SSIM
+// has gradients on both ssim and cs), runs the forward's two register-sliding filter passes, and
+// keeps the 4 filtered values per thread; then the pointwise combination with X and Y and the
+// average pooling's backward from the level below,
+//   0.25 · d_{l+1}[(iy + H%2)/2][(ix + W%2)/2]   (every pixel lies in exactly one pooling window).
+// grid (⌈W/64⌉, ⌈H/16⌉, planes). dX / dY null: not wanted.
+__global__ void __launch_bounds__(256, 2) ssim_level_bwd_kernel(
+    const float* __restrict__ X, const float* __restrict__ Y, int H, int W,
+    const float* __restrict__ DA, const float* __restrict__ coefA, const float* __restrict__ DB,
+    const float* __restrict__ coefB, const float* __restrict__ poolX,
+    const float* __restrict__ poolY, int Hn, int Wn, float* __restrict__ dX,
+    float* __restrict__ dY) {
+  __shared__ __attribute__((aligned(16))) float sd[IH * IWP];
+  __shared__ __attribute__((aligned(16))) float h[IH][TOW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Ho = H - (WIN - 1), Wo = W - (WIN - 1);
+  const int plane = blockIdx.z, img = plane / 3;
+  const int r0 = blockIdx.y * TOH, c0 = blockIdx.x * TOW;
+  const long ms = (long)gridDim.z * Ho * Wo;
+  const float ca = coefA[img], cb = DB ? coefB[img] : 0.f;
+  float g[WIN];
+#pragma unroll
+  for (int k = 0; k < WIN; ++k) g[k] = c_gauss[k];
+  const int rs = wave * RS;
+  float m[4][RS];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+#pragma unroll
+    for (int j = 0; j < RS; ++j) m[q][j] = 0.f;
+    if ((q == 0 && !dX) || (q == 3 && !dY)) continue;   // uniform over the grid
+    const float* da = DA + q * ms + (long)plane * Ho * Wo;
+    const float* db = DB ? DB + q * ms + (long)plane * Ho * Wo : nullptr;
+    // (sd is free: the barrier before the previous map's H pass followed its W pass)
+    for (int i = tid; i < IH * IW; i += 256) {
+      const int r = i / IW, c = i - r * IW;
+      const int gr = r0 - (WIN - 1) + r, gc = c0 - (WIN - 1) + c;
+      float v = 0.f;
+      if (gr >= 0 && gr < Ho && gc >= 0 && gc < Wo) {
+        v = ca * da[(long)gr * Wo + gc];
+        if (db) v += cb * db[(long)gr * Wo + gc];
+      }
+      sd[r * IWP + c] = v;
+    }
+    __syncthreads();   // also: the previous map's H pass has read h
+    for (int task = tid; task < IH * (TOW / 4); task += 256) {
+      const int r = task >> 4, cq = (task & 15) * 4;
+      float v[16];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const f4 a = *(const f4*)(sd + r * IWP + cq + 4 * u);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[4 * u + e] = a[e];
+      }
+      f4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < WIN; ++k) acc = fmac(g[k], v[j + k], acc);
+        o[j] = acc;
+      }
+      *(f4*)(&h[r][cq]) = o;
+    }
+    __syncthreads();
+    float v[RS + WIN - 1];
+#pragma unroll
+    for (int i = 0; i < RS + WIN - 1; ++i) v[i] = h[rs + i][lane];
+#pragma unroll
+    for (int j = 0; j < RS; ++j) {
+      float acc = 0.f;
+#pragma unroll
+      for (int k = 0; k < WIN; ++k) acc = fmac(g[k], v[j + k], acc);
+      m[q][j] = acc;
+    }
+  }
+  const int col = c0 + lane;
+  if (col >= W) return;
+  const int ph = H % 2, pw = W % 2;
+#pragma unroll
+  for (int j = 0; j < RS; ++j) {
+    const int row = r0 + rs + j;
+    if (row >= H) break;
+    const long at = ((long)plane * H + row) * W + col;
+    const long pat = ((long)plane * Hn + (row + ph) / 2) * Wn + (col + pw) / 2;
+    const float x = X[at], y = Y[at];
+    if (dX) {
+      float d = (m[0][j] + 2.0f * x * m[1][j]) + y * m[2][j];
+      if (poolX) d += 0.25f * poolX[pat];
+      dX[at] = d;
+    }
+    if (dY) {
+      float d = (m[3][j] + 2.0f * y * m[1][j]) + x * m[2][j];
+      if (poolY) d += 0.25f * poolY[pat];
+      dY[at] = d;
+    }
+  }
+}
+
 int level_plan(int H, int W, Level* lv, int B, long* pyr_floats, long* partial_doubles,
                int levels = LEVELS) {
   long off = 0, part = 0;
@@ -279,6 +457,42 @@ int level_plan(int H, int W, Level* lv, int B, long* pyr_floats, long* partial_d
   *pyr_floats = off;
   *partial_doubles = part;
   return 0;
+}
+
+// Workspace of the gradient path, from its 256-byte aligned base:
+//   partial doubles | means [levels][B][2] doubles | pyramid of X, Y (levels ≥ 1) | pyramid of
+//   dX, dY (levels ≥ 1, the backward's) | derivative maps | coef floats
+// The maps of level l: MS-SSIM one set of nmaps (3, with dY 4) planes-of-every-image; single-scale
+// two sets (ssim, then cs).
+struct GradPlan {
+  Level lv[LEVELS];
+  int levels, nmaps;
+  long pyr, part;
+  long maps[LEVELS];   // first float of the level's maps
+  size_t off_means, off_pyr, off_gpyr, off_maps, off_coef, bytes;
+};
+
+int grad_plan(int B, int H, int W, int want_dy, int multiscale, GradPlan* gp) {
+  gp->levels = multiscale ? LEVELS : 1;
+  gp->nmaps = want_dy ? 4 : 3;
+  if (B <= 0 || level_plan(H, W, gp->lv, B, &gp->pyr, &gp->part, gp->levels) != 0) return -1;
+  long maps = 0;
+  for (int l = 0; l < gp->levels; ++l) {
+    gp->maps[l] = maps;
+    maps += (multiscale ? 1L : 2L) * gp->nmaps * B * 3 * (gp->lv[l].H - WIN + 1) *
+            (gp->lv[l].W - WIN + 1);
+  }
+  gp->off_means = (size_t)gp->part * 8;
+  gp->off_pyr = gp->off_means + (size_t)gp->levels * B * 2 * 8;
+  gp->off_gpyr = gp->off_pyr + (size_t)gp->pyr * 4;
+  gp->off_maps = gp->off_gpyr + (size_t)gp->pyr * 4;
+  gp->off_coef = gp->off_maps + (size_t)maps * 4;
+  gp->bytes = gp->off_coef + (size_t)(multiscale ? LEVELS : 2) * B * 4 + 256;
+  return 0;
+}
+
+char* aligned_base(void* workspace) {
+  return (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
 }
 
 }  // namespace
@@ -330,7 +544,8 @@ int iclr17_ms_ssim(const float* x, const float* y, int B, int H, int W, float da
     }
     const int Ho = Hl - WIN + 1, Wo = Wl - WIN + 1;
     dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
-    hipLaunchKernelGGL(ssim_level_kernel, grid, dim3(256), 0, st, X, Y, Hl, Wl, c1, c2, pl);
+    hipLaunchKernelGGL(ssim_level_kernel<0>, grid, dim3(256), 0, st, X, Y, Hl, Wl, c1, c2, pl,
+                       (float*)nullptr, (float*)nullptr, 0);
     fp.poff[l] = pl - partial;
     fp.tiles[l] = lv[l].tiles;
     fp.count[l] = 3.0 * Ho * Wo;
@@ -364,10 +579,176 @@ int iclr17_ssim(const float* x, const float* y, int B, int H, int W, float data_
   const float c2 = (0.03f * data_range) * (0.03f * data_range);
   const int Ho = H - WIN + 1, Wo = W - WIN + 1;
   dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
-  hipLaunchKernelGGL(ssim_level_kernel, grid, dim3(256), 0, st, x, y, H, W, c1, c2, partial);
+  hipLaunchKernelGGL(ssim_level_kernel<0>, grid, dim3(256), 0, st, x, y, H, W, c1, c2, partial,
+                     (float*)nullptr, (float*)nullptr, 0);
   hipLaunchKernelGGL(ssim_finish_kernel, dim3(B), dim3(256), 0, st, partial, 3L * lv[0].tiles,
                      3.0 * Ho * Wo, out_ssim, out_cs);
   return check_launch("ssim");
+}
+
+// ------------------------------------------------------------------------ gradient path
+size_t iclr17_ssim_grad_workspace_size(int B, int H, int W, int want_dy, int multiscale) {
+  GradPlan gp;
+  return grad_plan(B, H, W, want_dy, multiscale, &gp) == 0 ? gp.bytes : 0;
+}
+
+int iclr17_ms_ssim_fwd_saved(const float* x, const float* y, int B, int H, int W, float data_range,
+                             int want_dy, void* workspace, size_t workspace_bytes, float* out,
+                             void* stream) {
+  ICLR17_REQUIRE(x && y && workspace && out && B > 0, ICLR17_EINVAL,
+                 "ms_ssim_fwd_saved: null pointer");
+  ICLR17_REQUIRE(B <= 10000 && H <= 65535 * 2, ICLR17_EINVAL,
+                 "ms_ssim_fwd_saved: B=%d H=%d exceed the grid", B, H);
+  GradPlan gp;
+  ICLR17_REQUIRE(grad_plan(B, H, W, want_dy, 1, &gp) == 0, ICLR17_EINVAL,
+                 "ms_ssim_fwd_saved: %dx%d is too small for 5 levels of an 11-tap window", H, W);
+  ICLR17_REQUIRE(workspace_bytes >= gp.bytes, ICLR17_EINVAL,
+                 "ms_ssim_fwd_saved: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = aligned_base(workspace);
+  double* partial = (double*)ws;
+  double* means = (double*)(ws + gp.off_means);
+  float* pyrbuf = (float*)(ws + gp.off_pyr);
+  float* maps = (float*)(ws + gp.off_maps);
+  const float c1 = (0.01f * data_range) * (0.01f * data_range);
+  const float c2 = (0.03f * data_range) * (0.03f * data_range);
+  const float* X = x;
+  const float* Y = y;
+  double* pl = partial;
+  FinishPlan fp;
+  for (int l = 0; l < LEVELS; ++l) {
+    const int Hl = gp.lv[l].H, Wl = gp.lv[l].W;
+    if (l > 0) {
+      float* Xn = pyrbuf + gp.lv[l].off;
+      float* Yn = Xn + (long)B * 3 * Hl * Wl;
+      hipLaunchKernelGGL(avgpool2_kernel, dim3((Wl + 255) / 256, Hl, 2 * B * 3), dim3(256), 0, st,
+                         X, Y, B * 3, gp.lv[l - 1].H, gp.lv[l - 1].W, Xn, Yn);
+      X = Xn;
+      Y = Yn;
+    }
+    const int Ho = Hl - WIN + 1, Wo = Wl - WIN + 1;
+    dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
+    float* d = maps + gp.maps[l];
+    if (l < LEVELS - 1)
+      hipLaunchKernelGGL(ssim_level_kernel<1>, grid, dim3(256), 0, st, X, Y, Hl, Wl, c1, c2, pl, d,
+                         (float*)nullptr, want_dy);
+    else
+      hipLaunchKernelGGL(ssim_level_kernel<2>, grid, dim3(256), 0, st, X, Y, Hl, Wl, c1, c2, pl,
+                         (float*)nullptr, d, want_dy);
+    fp.poff[l] = pl - partial;
+    fp.tiles[l] = gp.lv[l].tiles;
+    fp.count[l] = 3.0 * Ho * Wo;
+    pl += 2L * B * 3 * gp.lv[l].tiles;
+  }
+  hipLaunchKernelGGL(msssim_finish_kernel, dim3(B), dim3(256), 0, st, partial, fp, B, means, out);
+  return check_launch("ms_ssim_fwd_saved");
+}
+
+int iclr17_ms_ssim_bwd(const float* x, const float* y, int B, int H, int W, int saved_dy,
+                       void* workspace, size_t workspace_bytes, const float* g, float* dx,
+                       float* dy, void* stream) {
+  ICLR17_REQUIRE(x && y && workspace && g && (dx || dy) && B > 0, ICLR17_EINVAL,
+                 "ms_ssim_bwd: null pointer");
+  ICLR17_REQUIRE(!dy || saved_dy, ICLR17_EINVAL,
+                 "ms_ssim_bwd: dy asked of a forward that saved no dY maps");
+  ICLR17_REQUIRE(B <= 10000 && H <= 65535 * 2, ICLR17_EINVAL,
+                 "ms_ssim_bwd: B=%d H=%d exceed the grid", B, H);
+  GradPlan gp;
+  ICLR17_REQUIRE(grad_plan(B, H, W, saved_dy, 1, &gp) == 0, ICLR17_EINVAL,
+                 "ms_ssim_bwd: %dx%d is too small for 5 levels of an 11-tap window", H, W);
+  ICLR17_REQUIRE(workspace_bytes >= gp.bytes, ICLR17_EINVAL, "ms_ssim_bwd: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = aligned_base(workspace);
+  const double* means = (const double*)(ws + gp.off_means);
+  const float* pyrbuf = (const float*)(ws + gp.off_pyr);
+  float* gpyr = (float*)(ws + gp.off_gpyr);
+  const float* maps = (const float*)(ws + gp.off_maps);
+  float* coef = (float*)(ws + gp.off_coef);
+  FinishPlan fp;
+  for (int l = 0; l < LEVELS; ++l)
+    fp.count[l] = 3.0 * (gp.lv[l].H - WIN + 1) * (gp.lv[l].W - WIN + 1);
+  hipLaunchKernelGGL(msssim_coef_kernel, dim3((B + 63) / 64), dim3(64), 0, st, means, g, fp, B,
+                     coef);
+  for (int l = LEVELS - 1; l >= 0; --l) {
+    const int Hl = gp.lv[l].H, Wl = gp.lv[l].W;
+    const long n = (long)B * 3 * Hl * Wl;
+    const float* X = l ? pyrbuf + gp.lv[l].off : x;
+    const float* Y = l ? pyrbuf + gp.lv[l].off + n : y;
+    float* oX = dx ? (l ? gpyr + gp.lv[l].off : dx) : nullptr;
+    float* oY = dy ? (l ? gpyr + gp.lv[l].off + n : dy) : nullptr;
+    const float *pX = nullptr, *pY = nullptr;
+    int Hn = 0, Wn = 0;
+    if (l < LEVELS - 1) {
+      Hn = gp.lv[l + 1].H;
+      Wn = gp.lv[l + 1].W;
+      pX = dx ? gpyr + gp.lv[l + 1].off : nullptr;
+      pY = dy ? gpyr + gp.lv[l + 1].off + (long)B * 3 * Hn * Wn : nullptr;
+    }
+    dim3 grid((Wl + TOW - 1) / TOW, (Hl + TOH - 1) / TOH, B * 3);
+    hipLaunchKernelGGL(ssim_level_bwd_kernel, grid, dim3(256), 0, st, X, Y, Hl, Wl,
+                       maps + gp.maps[l], coef + (long)l * B, (const float*)nullptr,
+                       (const float*)nullptr, pX, pY, Hn, Wn, oX, oY);
+  }
+  return check_launch("ms_ssim_bwd");
+}
+
+int iclr17_ssim_fwd_saved(const float* x, const float* y, int B, int H, int W, float data_range,
+                          int want_dy, void* workspace, size_t workspace_bytes, float* out_ssim,
+                          float* out_cs, void* stream) {
+  ICLR17_REQUIRE(x && y && workspace && out_ssim && out_cs && B > 0, ICLR17_EINVAL,
+                 "ssim_fwd_saved: null pointer");
+  ICLR17_REQUIRE(B <= 10000 && H <= 65535 * 2, ICLR17_EINVAL,
+                 "ssim_fwd_saved: B=%d H=%d exceed the grid", B, H);
+  GradPlan gp;
+  ICLR17_REQUIRE(grad_plan(B, H, W, want_dy, 0, &gp) == 0, ICLR17_EINVAL,
+                 "ssim_fwd_saved: %dx%d is smaller than the 11-tap window", H, W);
+  ICLR17_REQUIRE(workspace_bytes >= gp.bytes, ICLR17_EINVAL, "ssim_fwd_saved: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = aligned_base(workspace);
+  double* partial = (double*)ws;
+  float* maps = (float*)(ws + gp.off_maps);
+  const float c1 = (0.01f * data_range) * (0.01f * data_range);
+  const float c2 = (0.03f * data_range) * (0.03f * data_range);
+  const int Ho = H - WIN + 1, Wo = W - WIN + 1;
+  const long set = (long)gp.nmaps * B * 3 * Ho * Wo;
+  dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
+  hipLaunchKernelGGL(ssim_level_kernel<3>, grid, dim3(256), 0, st, x, y, H, W, c1, c2, partial,
+                     maps + set, maps, want_dy);
+  hipLaunchKernelGGL(ssim_finish_kernel, dim3(B), dim3(256), 0, st, partial, 3L * gp.lv[0].tiles,
+                     3.0 * Ho * Wo, out_ssim, out_cs);
+  return check_launch("ssim_fwd_saved");
+}
+
+int iclr17_ssim_bwd(const float* x, const float* y, int B, int H, int W, int saved_dy,
+                    void* workspace, size_t workspace_bytes, const float* g_ssim,
+                    const float* g_cs, float* dx, float* dy, void* stream) {
+  ICLR17_REQUIRE(x && y && workspace && (g_ssim || g_cs) && (dx || dy) && B > 0, ICLR17_EINVAL,
+                 "ssim_bwd: null pointer");
+  ICLR17_REQUIRE(!dy || saved_dy, ICLR17_EINVAL,
+                 "ssim_bwd: dy asked of a forward that saved no dY maps");
+  ICLR17_REQUIRE(B <= 10000 && H <= 65535 * 2, ICLR17_EINVAL,
+                 "ssim_bwd: B=%d H=%d exceed the grid", B, H);
+  GradPlan gp;
+  ICLR17_REQUIRE(grad_plan(B, H, W, saved_dy, 0, &gp) == 0, ICLR17_EINVAL,
+                 "ssim_bwd: %dx%d is smaller than the 11-tap window", H, W);
+  ICLR17_REQUIRE(workspace_bytes >= gp.bytes, ICLR17_EINVAL, "ssim_bwd: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = aligned_base(workspace);
+  const float* maps = (const float*)(ws + gp.off_maps);
+  float* coef = (float*)(ws + gp.off_coef);
+  const int Ho = H - WIN + 1, Wo = W - WIN + 1;
+  const long set = (long)gp.nmaps * B * 3 * Ho * Wo;
+  hipLaunchKernelGGL(ssim_coef_kernel, dim3((B + 63) / 64), dim3(64), 0, st, g_ssim, g_cs,
+                     3.0 * Ho * Wo, B, coef);
+  // set A: the ssim maps when g_ssim is given, else the cs maps; set B: the cs maps when both are
+  const float* DA = g_ssim ? maps : maps + set;
+  const float* cA = g_ssim ? coef : coef + B;
+  const float* DB = g_ssim && g_cs ? maps + set : nullptr;
+  dim3 grid((W + TOW - 1) / TOW, (H + TOH - 1) / TOH, B * 3);
+  hipLaunchKernelGGL(ssim_level_bwd_kernel, grid, dim3(256), 0, st, x, y, H, W, DA, cA, DB,
+                     (const float*)(coef + B), (const float*)nullptr, (const float*)nullptr, 0, 0,
+                     dx, dy);
+  return check_launch("ssim_bwd");
 }
 
 }  // extern "C"

@@ -779,6 +779,75 @@ def ssim(x: Tensor, y: Tensor, data_range: float = 1.0):
     return s, cs
 
 
+def _ssim_grad_args(x: Tensor, y: Tensor, want_dy: bool, multiscale: bool, what: str):
+    _check(x, "image", 4)
+    _check(y, "image", 4)
+    if x.shape != y.shape or x.shape[1] != 3 or x.device != y.device:
+        raise Iclr17Error(f"iclr17: {what} needs two [B,3,H,W] batches of one shape and device "
+                          f"(got {tuple(x.shape)} and {tuple(y.shape)})")
+    B, _, H, W = x.shape
+    nbytes = query("iclr17_ssim_grad_workspace_size", B, H, W, int(want_dy), int(multiscale))
+    if nbytes == 0:
+        raise Iclr17Error(f"iclr17: {what}: {H}x{W} is too small for "
+                          + ("5 levels of an 11-tap window" if multiscale else "the 11-tap window"))
+    return B, H, W, nbytes
+
+
+def ms_ssim_fwd_saved(x: Tensor, y: Tensor, data_range: float = 1.0, want_dy: bool = True):
+    """``ms_ssim`` (bitwise) plus the workspace ``ms_ssim_bwd`` reads → (per-image [B], ws).
+    x, y must be contiguous and stay unchanged until the backward."""
+    B, H, W, nbytes = _ssim_grad_args(x, y, want_dy, True, "ms_ssim_fwd_saved")
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    out = torch.empty(B, device=x.device, dtype=torch.float32)
+    call("iclr17_ms_ssim_fwd_saved", _p(x.contiguous()), _p(y.contiguous()), B, H, W,
+         float(data_range), int(want_dy), _p(ws), nbytes, _p(out), _stream(x))
+    return out, ws
+
+
+def ms_ssim_bwd(x: Tensor, y: Tensor, ws: Tensor, g: Tensor, saved_dy: bool,
+                want_dx: bool = True, want_dy: bool = True):
+    """g [B] = ∂loss/∂ms_ssim per image → (dx | None, dy | None), each [B,3,H,W]."""
+    B, H, W, nbytes = _ssim_grad_args(x, y, saved_dy, True, "ms_ssim_bwd")
+    _check(g, "ms_ssim gradient", 1)
+    if g.numel() != B or ws.dtype != torch.uint8 or ws.device != x.device or not (want_dx or want_dy):
+        raise Iclr17Error("iclr17: ms_ssim_bwd needs g [B], the forward's workspace and an output")
+    dx = torch.empty_like(x, memory_format=torch.contiguous_format) if want_dx else None
+    dy = torch.empty_like(x, memory_format=torch.contiguous_format) if want_dy else None
+    call("iclr17_ms_ssim_bwd", _p(x.contiguous()), _p(y.contiguous()), B, H, W, int(saved_dy),
+         _p(ws), ws.numel(), _p(g.contiguous()), _p(dx), _p(dy), _stream(x))
+    return dx, dy
+
+
+def ssim_fwd_saved(x: Tensor, y: Tensor, data_range: float = 1.0, want_dy: bool = True):
+    """``ssim`` (bitwise) plus the workspace ``ssim_bwd`` reads → (ssim [B], cs [B], ws)."""
+    B, H, W, nbytes = _ssim_grad_args(x, y, want_dy, False, "ssim_fwd_saved")
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    s = torch.empty(B, device=x.device, dtype=torch.float32)
+    cs = torch.empty(B, device=x.device, dtype=torch.float32)
+    call("iclr17_ssim_fwd_saved", _p(x.contiguous()), _p(y.contiguous()), B, H, W,
+         float(data_range), int(want_dy), _p(ws), nbytes, _p(s), _p(cs), _stream(x))
+    return s, cs, ws
+
+
+def ssim_bwd(x: Tensor, y: Tensor, ws: Tensor, g_ssim: Optional[Tensor], g_cs: Optional[Tensor],
+             saved_dy: bool, want_dx: bool = True, want_dy: bool = True):
+    """Per-image gradients on the ssim and cs means ([B] each, one may be None) → (dx, dy)."""
+    B, H, W, nbytes = _ssim_grad_args(x, y, saved_dy, False, "ssim_bwd")
+    for g in (g_ssim, g_cs):
+        if g is not None:
+            _check(g, "ssim gradient", 1)
+    if (g_ssim is None and g_cs is None) or any(g is not None and g.numel() != B for g in (g_ssim, g_cs)) \
+            or ws.dtype != torch.uint8 or ws.device != x.device or not (want_dx or want_dy):
+        raise Iclr17Error("iclr17: ssim_bwd needs g_ssim and/or g_cs [B], the forward's workspace "
+                          "and an output")
+    dx = torch.empty_like(x, memory_format=torch.contiguous_format) if want_dx else None
+    dy = torch.empty_like(x, memory_format=torch.contiguous_format) if want_dy else None
+    call("iclr17_ssim_bwd", _p(x.contiguous()), _p(y.contiguous()), B, H, W, int(saved_dy),
+         _p(ws), ws.numel(), _p(None if g_ssim is None else g_ssim.contiguous()),
+         _p(None if g_cs is None else g_cs.contiguous()), _p(dx), _p(dy), _stream(x))
+    return dx, dy
+
+
 def output_partials_per_image(H: int, W: int) -> int:
     return query("iclr17_output_partials_per_image", H, W)
 

@@ -191,10 +191,22 @@ class ImageCompressor(nn.Module):
         self._warm_packs(backward=True)   # one batched pack per parameter update
         return CodecTrainFn.apply(x.contiguous(), noise.contiguous(), self, *params)
 
-    def forward_train(self, input_image, noise: Optional[torch.Tensor] = None):
+    def forward_train(self, input_image, noise: Optional[torch.Tensor] = None,
+                      distortion: str = "mse"):
         """The tuple train.py:97 unpacks, as model.py:81 intends:
-        (clipped_recon, mse of the UNclipped recon (model.py:61), bpp), all differentiable."""
+        (clipped_recon, mse of the UNclipped recon (model.py:61), bpp), all differentiable.
+
+        ``distortion="ms-ssim"`` returns (clipped_recon, 1 − mean MS-SSIM(clipped_recon, x), bpp)
+        instead (losses.ms_ssim_diff on the clipped reconstruction, so the gradient reaches the
+        codec's backward through the clamp). In the h3 mode a step whose activations do not fit
+        the form has a NaN reconstruction, and so a NaN distortion, as its mse would be."""
+        if distortion not in ("mse", "ms-ssim"):
+            raise kernels.Iclr17Error(f"iclr17: distortion must be 'mse' or 'ms-ssim' "
+                                      f"(got {distortion!r})")
         clipped, _, bpp, mse = self._train_outputs(input_image, noise, list(self.parameters()))
+        if distortion == "ms-ssim":
+            from .losses import ms_ssim_diff
+            return clipped, 1 - ms_ssim_diff(clipped, input_image, data_range=1.0), bpp
         return clipped, mse, bpp
 
     # ------------------------------------------------------------- entropy coding (§8 f4)

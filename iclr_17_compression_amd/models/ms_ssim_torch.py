@@ -48,7 +48,8 @@ def _to_gpu(X, Y):
     return a value a loss such as 1 − ms_ssim(...) would silently not differentiate."""
     if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad):
         raise Iclr17Error("iclr17: ms_ssim/ssim have no backward on the GPU kernels; call them on "
-                          "detached tensors or under torch.no_grad()")
+                          "detached tensors or under torch.no_grad(), or use the differentiable "
+                          "iclr_17_compression_amd.losses.ms_ssim_diff / ssim_diff / MSSSIMLoss")
     if X.dtype != torch.float32:
         raise Iclr17Error(f"iclr17: ssim/ms_ssim take float32 images (got {X.dtype})")
     home = X.device

@@ -42,6 +42,7 @@ DEFAULTS = {  # train.py:15-29
     "lr": {"base": 1e-4, "decay": 0.1, "decay_interval": 2200000}, "warmup_step": 0,
     "out_channel_N": 128,
 }
+DISTORTIONS = ("mse", "ms-ssim")   # config key "distortion" (absent: "mse", the reference's loss)
 
 
 class AverageMeter:
@@ -71,6 +72,9 @@ def parse_config(path):
                 cfg["lr"].update(v)
             else:
                 cfg[k] = v
+    if cfg.get("distortion", "mse") not in DISTORTIONS:
+        raise ValueError(f"config: distortion must be one of {DISTORTIONS} "
+                         f"(got {cfg['distortion']!r})")
     return cfg
 
 
@@ -231,20 +235,31 @@ def main(argv=None):
 
 def train_epoch(net, loader, optimizer, reducer, cfg, lam, lr, epoch, global_step, tot, args,
                 device):
-    """train(), train.py:84-154: one pass over the loader's epoch."""
+    """train(), train.py:84-154: one pass over the loader's epoch. With the config's
+    "distortion": "ms-ssim" the loss is train_lambda · (1 − MS-SSIM(clipped, x)) + bpp."""
     logger.info("Epoch {} begin".format(epoch))
     net.train()
-    meters = {k: AverageMeter(cfg["print_freq"]) for k in ("elapsed", "loss", "psnr", "bpp", "mse")}
+    msssim = cfg.get("distortion", "mse") == "ms-ssim"
+    meters = {k: AverageMeter(cfg["print_freq"])
+              for k in ("elapsed", "loss", "psnr", "bpp", "mse", "msssim")}
     for x in loader.epoch(epoch):
         t0 = time.time()
         global_step += 1
-        clipped, mse, bpp = net.forward_train(x)
-        rd_loss = lam * mse + bpp
+        if msssim:
+            clipped, dist, bpp = net.forward_train(x, distortion="ms-ssim")
+            rd_loss = lam * dist + bpp
+        else:
+            clipped, mse, bpp = net.forward_train(x)
+            rd_loss = lam * mse + bpp
         optimizer.zero_grad(set_to_none=True)
         rd_loss.backward()
         reducer.finish()   # the all-reduces overlapped the backward (dist.GradAllReducer)
         optimizer.step()   # clamp after the all-reduce (DataParallel's GPU0 clamp), then Adam
         if global_step % cfg["cal_step"] == 0:
+            if msssim:   # PSNR of the clipped reconstruction, outside the graph
+                with torch.no_grad():
+                    mse = torch.mean((clipped.detach() - x) ** 2)
+                meters["msssim"].update(1.0 - dist.item())
             m, lv, bv = mse.item(), rd_loss.item(), bpp.item()
             # in the h3 mode an activation that did not fit the form made the step's loss NaN
             kernels.check_finite(f"training loss at step {global_step}", m, lv, bv)
@@ -263,7 +278,8 @@ def train_epoch(net, loader, optimizer, reducer, cfg, lam, lr, epoch, global_ste
                 f"Total Loss {M['loss'].val:.3f} ({M['loss'].avg:.3f})",
                 f"PSNR {M['psnr'].val:.3f} ({M['psnr'].avg:.3f})",
                 f"Bpp {M['bpp'].val:.5f} ({M['bpp'].avg:.5f})",
-                f"MSE {M['mse'].val:.5f} ({M['mse'].avg:.5f})"]))
+                f"MSE {M['mse'].val:.5f} ({M['mse'].avg:.5f})"]
+                + ([f"MS-SSIM {M['msssim'].val:.5f} ({M['msssim'].avg:.5f})"] if msssim else [])))
         if global_step % cfg["save_model_freq"] == 0 and args.test_dir:
             test_kodak(net, args.test_dir, device, global_step)      # train.py:150-152 (D8)
             net.train()

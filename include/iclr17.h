@@ -290,6 +290,33 @@ int iclr17_ssim(const float* x, const float* y, int B, int H, int W, float data_
                 void* workspace, size_t workspace_bytes, float* out_ssim, float* out_cs,
                 void* stream);
 
+/* MS-SSIM / SSIM with a backward (the training loss λ·(1 − MS-SSIM) + bpp). The *_fwd_saved
+ * entries compute bitwise what iclr17_ms_ssim / iclr17_ssim compute and also leave, in the
+ * workspace, what the backward reads: the image pyramid, the per-level means and the per-pixel
+ * derivative maps (with want_dy also those dY needs). The workspace therefore lives from the
+ * forward to the backward; its size comes from
+ *   iclr17_ssim_grad_workspace_size(B, H, W, want_dy, multiscale)   (0 = shape unsupported)
+ * with multiscale = 1 for the MS-SSIM pair and 0 for the single-scale pair.
+ * Backward: x, y and the workspace of the forward, saved_dy = the forward's want_dy, the upstream
+ * gradient per image (g [B]; single-scale: g_ssim [B] and g_cs [B], either may be null, not
+ * both), outputs dx / dy [B,3,H,W] (either may be null, not both; dy needs saved_dy). The
+ * workspace must be at least the size the query gives for saved_dy. Every sum has a fixed
+ * order: the gradients are bitwise reproducible. Nothing is clamped: a level whose mean is ≤ 0
+ * gives NaN gradients, as the reference's autograd does. */
+size_t iclr17_ssim_grad_workspace_size(int B, int H, int W, int want_dy, int multiscale);
+int iclr17_ms_ssim_fwd_saved(const float* x, const float* y, int B, int H, int W, float data_range,
+                             int want_dy, void* workspace, size_t workspace_bytes, float* out,
+                             void* stream);
+int iclr17_ms_ssim_bwd(const float* x, const float* y, int B, int H, int W, int saved_dy,
+                       void* workspace, size_t workspace_bytes, const float* g, float* dx,
+                       float* dy, void* stream);
+int iclr17_ssim_fwd_saved(const float* x, const float* y, int B, int H, int W, float data_range,
+                          int want_dy, void* workspace, size_t workspace_bytes, float* out_ssim,
+                          float* out_cs, void* stream);
+int iclr17_ssim_bwd(const float* x, const float* y, int B, int H, int W, int saved_dy,
+                    void* workspace, size_t workspace_bytes, const float* g_ssim,
+                    const float* g_cs, float* dx, float* dy, void* stream);
+
 /* datasets.py:27-33 training transform on the GPU: per image, PIL-exact bilinear resize of its
  * crop box to S×S (two passes, 8-bit fixed point), horizontal / vertical flips, /255 → out NCHW
  * fp32 [B,3,S,S]. src: uint8 HWC images back to back; desc: int64 [B][16] = {src byte offset, H,
