@@ -139,6 +139,7 @@ SIGNATURES = {
     "iclr17_pack_h3k": (_I, [_I, _P, _P, _I, _P]),
     "iclr17_h3_planes": (_I, [_P, ctypes.c_long, _P, _P, _P]),
     "iclr17_h3_planes_cm": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "iclr17_h3_range_words": (_I, [_I]),
     "iclr17_split_packed_h3_size": (_SZ, [_I, _I, _I]),
     "iclr17_split_packed_h3": (_I, [_P, _I, _I, _I, _P, _P]),
     "iclr17_pack_h3_batch": (_I, [_P, _I, _P]),

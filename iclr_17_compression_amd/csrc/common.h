@@ -197,7 +197,8 @@ __device__ __forceinline__ unsigned short h16_bits(_Float16 v) {
 // infinite value counts too: its results are not finite either way). The check is one compare on
 // the largest |a| of the four (NaN ignored by the max), not two per value: in the GDN epilogues
 // the per-value compares were a tenth of the VALU work
-__device__ __forceinline__ void h3_split4(const f4& x, uint2& hi, uint2& lo, bool& ovf) {
+// Returns that largest |a|.
+__device__ __forceinline__ float h3_split4(const f4& x, uint2& hi, uint2& lo, bool& ovf) {
   typedef float f2 __attribute__((ext_vector_type(2)));
   const f2 a0 = f2{x[0], x[1]} * kH3Sa, a1 = f2{x[2], x[3]} * kH3Sa;
   const h2v h0 = __builtin_convertvector(a0, h2v), h1 = __builtin_convertvector(a1, h2v);
@@ -207,6 +208,16 @@ __device__ __forceinline__ void h3_split4(const f4& x, uint2& hi, uint2& lo, boo
   lo = uint2{__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1)};
   const float m = fmaxf(fmaxf(fabsf(a0.x), fabsf(a0.y)), fmaxf(fabsf(a1.x), fabsf(a1.y)));
   ovf |= m >= 65520.0f;
+  return m;
+}
+
+// "Narrow" activations: |a| < kH3Narrow (|x| < 1024 at σ_a = 2⁻⁶), so that the RNE hi part stays
+// below 32 and hi·2¹¹ is exact in fp16 — the h3 engine's main loop may then put the 2¹¹ factor of
+// the hi·hi product on the activation fragment (one per step) instead of the weight fragments
+// (one per 32-channel tile). The same compare on the same maximum sets `wide` otherwise.
+constexpr float kH3Narrow = 16.0f;
+__device__ __forceinline__ void h3_split4(const f4& x, uint2& hi, uint2& lo, bool& ovf, bool& wide) {
+  wide |= h3_split4(x, hi, lo, ovf) >= kH3Narrow;
 }
 
 // 8 fp16 values × 2¹¹ (exact while they stay below 32: the weight scaling guarantees it)

@@ -15,7 +15,10 @@
 //     registers (4 packed fp16 multiplies per fragment) instead of being a third plane.
 // One k16 step = one tap × the chunk's 16 channels: per 32-channel tile three MFMAs, small terms
 // first: hi_w·lo_a, lo_w·hi_a, (hi_w·2¹¹)·hi_a, in place on the accumulator (the h3 chain's
-// rounding error is 0.7× the x6 chain's: common.h).
+// rounding error is 0.7× the x6 chain's: common.h). When every value of the input is narrow
+// (|a| < 16: the chain's wide word, HArgs::wide, read clear at the kernel's start) the 2¹¹ factor
+// goes on the step's one activation fragment instead — hi_w·(hi_a·2¹¹), the same exact product —
+// and a step needs 4 packed multiplies, not 4 per tile (h3k_body's main_loop, NARROW).
 //
 // INT_IN (deconv1 on ŷ: integers, exact in the hi plane while |ŷ| < 2048): the lo plane is zero,
 // only the hi plane is staged and the two products with hi_a run. INT_OK kernels check this per
@@ -82,6 +85,9 @@ struct HArgs {
   long out_x6_plane;
   int out_cm;           // the h3 output's chunk-major chunk: 0 (NHWC), 8, 16 or 32
   int* range;           // set to 1 when a value does not fit the h3 form (nullable)
+  int* wide;            // the range flag's second word (null when the caller's flag has one word):
+                        // set by every producer of an h3 activation with |a| ≥ kH3Narrow; a
+                        // consumer that reads it clear runs the narrow-activation main loop
   // HE_QUANT (conv3 + quantiser + rate): out = y (nullable), yhat = ŷ | ỹ fp32 NHWC, out_h3 = ŷ in
   // the h3 form (nullable), bits partial sums [B][T] (T = tiles · channel groups)
   int qmode;
@@ -232,7 +238,7 @@ __device__ __forceinline__ void quant_epilogue(const HArgs& a, f16v (&acc)[COT /
   // per tile, not one per element)
   float* const lq = (float*)lds0 + etid * 32;
   float bits = 0.f;
-  bool ovf = false;
+  bool ovf = false, wid = false;
   const bool poison = a.range != nullptr && (*(const volatile int*)a.range & 1) != 0;
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
@@ -278,10 +284,11 @@ __device__ __forceinline__ void quant_epilogue(const HArgs& a, f16v (&acc)[COT /
     }
     if (a.out_h3) {
       uint2 hb[4], lb[4];
-      bool ov = false;
+      bool ov = false, wd = false;
 #pragma unroll
-      for (int m = 0; m < 4; ++m) h3_split4(yq[m], hb[m], lb[m], ov);
+      for (int m = 0; m < 4; ++m) h3_split4(yq[m], hb[m], lb[m], ov, wd);
       ovf |= inside && ov;
+      wid |= inside && wd;
       u4 sv[2][2];
 #pragma unroll
       for (int pl = 0; pl < 2; ++pl)
@@ -303,6 +310,7 @@ __device__ __forceinline__ void quant_epilogue(const HArgs& a, f16v (&acc)[COT /
     }
   }
   if (ovf && a.range) atomicOr(a.range, 2);   // vector atomic, per offending lane (rare)
+  if (wid && a.wide) atomicOr(a.wide, 1);
   bits = wave_sum(poison ? __builtin_nanf("") : bits);
   float* sw = (float*)scratch;
   if (elane == 0) sw[ewave] = bits;
@@ -316,10 +324,13 @@ __device__ __forceinline__ void quant_epilogue(const HArgs& a, f16v (&acc)[COT /
 }
 
 // ICM: the input's chunk-major chunk (the layout of the h3 form below; 0: NHWC, conv1's image).
+// narrow (workgroup-uniform): every value of the input has |a| < kH3Narrow (the kernel read the
+// chain's wide word clear) — the main loop then runs in its narrow-activation form, whose results
+// are bit-identical to the general form's.
 template <int MODE, int TH, int CO, int CI, int EPI, bool INT_IN, int PH, int COT = CO,
           bool SEP = false, int ICM = 0>
 __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, int b, int ty, int tx,
-                                         int cg = 0) {
+                                         int cg, bool narrow) {
   static_assert(CO % COT == 0 && (COT == CO || EPI == HE_QUANT), "channel groups: conv3 only");
   // conv3's short steps (9 MFMAs per wave, one wave per SIMD) keep four DMA groups in flight, so
   // a weight slot has four steps to arrive instead of two (the other layers' 18-MFMA steps on two
@@ -567,6 +578,12 @@ __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, in
       f.wl[i] = *(lu4p)(wb + APL + i * 512);
     }
   };
+  // The main loop. NARROW (the narrow-activation form): the 2¹¹ factor of the third product sits
+  // on the step's one activation fragment, (hi_a·2¹¹) — exact for |hi_a| < 32 — instead of the NT
+  // weight fragments: 4 packed fp16 multiplies per step, not 4·NT. The same three products per
+  // tile in the same order, each the same exact fp16 × fp16 product: bit-identical sums.
+  auto main_loop = [&](auto narrow_form) {
+  constexpr bool NARROW = decltype(narrow_form)::value;
   Frag cur;
   int stage = 1;   // stage of step g+1
   for (int c = 0; c < NCH; ++c) {
@@ -587,12 +604,15 @@ __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, in
       read_frag(nxt, sP + ((s + 1 < S ? c : c + 1) & 1) * KK::PBUF + pbase,
                 tap_of(s + 1 < S ? s + 1 : 0), sB + stage * SB + abase, s + 1 < S ? s + 1 : 0);
       stage = stage + 1 == NST ? 0 : stage + 1;
+      u4 bh11 = cur.bh;
+      if constexpr (NARROW) bh11 = h3_x2048(cur.bh);
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
         f16v t = SEP ? cacc[i] : acc[i];
         if constexpr (!INT_IN) t = mfma32h(cur.wh[i], cur.bl, t);
         t = mfma32h(cur.wl[i], cur.bh, t);
-        t = mfma32h(h3_x2048(cur.wh[i]), cur.bh, t);
+        if constexpr (NARROW) t = mfma32h(cur.wh[i], bh11, t);
+        else t = mfma32h(h3_x2048(cur.wh[i]), cur.bh, t);
         if constexpr (SEP) cacc[i] = t;
         else acc[i] = t;
       }
@@ -608,6 +628,13 @@ __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, in
       for (int i = 0; i < NT; ++i) acc[i] += cacc[i];
     }
   }
+  };
+  // (readfirstlane: a scalar branch — the value comes from a vector load, which the compiler
+  // would otherwise branch on by exec mask)
+  // conv1 (16 steps, its window split in the kernel) keeps the general form: deciding per
+  // workgroup cost a workgroup reduction before the loop and measured slower.
+  if (!C1 && __builtin_amdgcn_readfirstlane((int)narrow)) main_loop(std::true_type{});
+  else main_loop(std::false_type{});
   vm_barrier();   // trailing sink loads landed; every wave is done with the stages
   if constexpr (EPI == HE_QUANT) {
     // (the kernel's LDS is sized by the full-input form: HK<…, false>)
@@ -642,7 +669,7 @@ __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, in
     }
   constexpr int NTH = KK::NTH, KB = KK::KB;
   static_assert(NT % 2 == 0, "GDN epilogue: pairs of 32-channel tiles");
-  bool ovf = false;
+  bool ovf = false, wid = false;
   // The channel contraction n_i = Σ_j γ_ij·x_j² in the h3 form. x² of a pixel (rounded to fp32,
   // as conv2d(x², γ) sees it) is scaled by a power of two s_p that puts the pixel's largest x²
   // in [2¹³, 2¹⁴) — the pixel is this elane's MFMA column, so the scale is undone per elane — and
@@ -787,10 +814,11 @@ __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, in
         // hands lane half 0 channels 0 .. 15 and half 1 channels 16 .. 31 (half the store
         // instructions of 8-byte stores; the epilogue's stores were issue-bound)
         uint2 hb[4], lb[4];
-        bool ov = false;
+        bool ov = false, wd = false;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) h3_split4(y[m], hb[m], lb[m], ov);
+        for (int m = 0; m < 4; ++m) h3_split4(y[m], hb[m], lb[m], ov, wd);
         ovf |= inside && ov;
+        wid |= inside && wd;
         u4 sv[2][2];
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
@@ -848,6 +876,7 @@ __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, in
     }
   }
   if (ovf && a.range) atomicOr(a.range, 1);   // vector atomic, per offending lane (rare)
+  if (wid && a.wide) atomicOr(a.wide, 1);
   }
 }
 
@@ -877,6 +906,10 @@ h3k_kernel(const HArgs a) {
   bid /= a.tiles_x;
   const int ty = bid % a.tiles_y;
   const int b = bid / a.tiles_y;
+  // the chain's wide word, read once: the kernel boundary on the stream orders the read after the
+  // producers of this launch's input (as deconv3's read of the range flag). This kernel's own
+  // epilogues may set it meanwhile for the next layer — either form gives the same bits.
+  const bool narrow = a.wide != nullptr && *(const volatile int*)a.wide == 0;
   bool small = false;
   if constexpr (INT_OK) {
     static_assert(MODE == BM_DECONV, "INT_OK: deconv1");
@@ -926,13 +959,13 @@ h3k_kernel(const HArgs a) {
   auto run = [&](auto int_in) {
     constexpr bool II = decltype(int_in)::value;
     if constexpr (MODE != BM_DECONV) {
-      h3k_body<MODE, TH, CO, CI, EPI, II, 0, COT, SEP, ICM>(a, smem, b, ty, tx, cg);
+      h3k_body<MODE, TH, CO, CI, EPI, II, 0, COT, SEP, ICM>(a, smem, b, ty, tx, cg, narrow);
     } else {
       switch (ph) {   // wave-uniform: the tap lists are compile-time per phase
-        case 0: h3k_body<MODE, TH, CO, CI, EPI, II, 0, CO, false, ICM>(a, smem, b, ty, tx); break;
-        case 1: h3k_body<MODE, TH, CO, CI, EPI, II, 1, CO, false, ICM>(a, smem, b, ty, tx); break;
-        case 2: h3k_body<MODE, TH, CO, CI, EPI, II, 2, CO, false, ICM>(a, smem, b, ty, tx); break;
-        default: h3k_body<MODE, TH, CO, CI, EPI, II, 3, CO, false, ICM>(a, smem, b, ty, tx); break;
+        case 0: h3k_body<MODE, TH, CO, CI, EPI, II, 0, CO, false, ICM>(a, smem, b, ty, tx, 0, narrow); break;
+        case 1: h3k_body<MODE, TH, CO, CI, EPI, II, 1, CO, false, ICM>(a, smem, b, ty, tx, 0, narrow); break;
+        case 2: h3k_body<MODE, TH, CO, CI, EPI, II, 2, CO, false, ICM>(a, smem, b, ty, tx, 0, narrow); break;
+        default: h3k_body<MODE, TH, CO, CI, EPI, II, 3, CO, false, ICM>(a, smem, b, ty, tx, 0, narrow); break;
       }
     }
   };
@@ -1187,23 +1220,25 @@ __global__ void __launch_bounds__(256) pack_h3_batch_kernel(const H3Batch b) {
 // fp32 → h3 planes (x·σ_a split): iclr17_h3_planes
 __global__ void __launch_bounds__(256) h3_planes_kernel(const float* __restrict__ x, long n4,
                                                         long plane, u16* __restrict__ out,
-                                                        int* range) {
-  bool ovf = false;
+                                                        int* range, int* wide) {
+  bool ovf = false, wid = false;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
     uint2 hb, lb;
-    h3_split4(*(const f4*)(x + 4 * i), hb, lb, ovf);
+    h3_split4(*(const f4*)(x + 4 * i), hb, lb, ovf, wid);
     *(uint2*)(out + 4 * i) = hb;
     *(uint2*)(out + plane + 4 * i) = lb;
   }
   if (ovf && range) atomicOr(range, 1);
+  if (wid && wide) atomicOr(wide, 1);
 }
 
 // fp32 NHWC [B][h][w][N] → the h3 form chunk-major [2][B][N/cm][h][w][cm] (iclr17_h3_planes_cm):
 // a thread per 4 consecutive channels of a pixel
 __global__ void __launch_bounds__(256) h3_planes_cm_kernel(const float* __restrict__ x, long n4,
                                                            int N, int cm, long hw, long plane,
-                                                           u16* __restrict__ out, int* range) {
-  bool ovf = false;
+                                                           u16* __restrict__ out, int* range,
+                                                           int* wide) {
+  bool ovf = false, wid = false;
   const int q4 = N / 4;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
     const long p = i / q4;
@@ -1211,11 +1246,12 @@ __global__ void __launch_bounds__(256) h3_planes_cm_kernel(const float* __restri
     const long b = p / hw, pix = p - b * hw;
     const long o = ((b * (N / cm) + ch / cm) * hw + pix) * cm + ch % cm;
     uint2 hb, lb;
-    h3_split4(*(const f4*)(x + 4 * i), hb, lb, ovf);
+    h3_split4(*(const f4*)(x + 4 * i), hb, lb, ovf, wid);
     *(uint2*)(out + o) = hb;
     *(uint2*)(out + plane + o) = lb;
   }
   if (ovf && range) atomicOr(range, 1);
+  if (wid && wide) atomicOr(wide, 1);
 }
 
 // The chain's h3 layouts (the consumer's patch chunk): conv1 → conv2 and conv2 →
@@ -1265,6 +1301,15 @@ static void launch_conv3(const HArgs& a, hipStream_t st) {
                      dim3(a.tiles_x * a.tiles_y * a.B * (N / kC3COT)), dim3(kC3TH / 2 * 64), 0, st, a);
 }
 
+// Words behind a caller's range_flag pointer (iclr17_h3_range_words): with two, word 1 is the
+// chain's wide word; with one (the default) no kernel reads or writes past word 0 and every main
+// loop runs in its general form.
+static std::atomic<int> g_range_words{1};
+static int* wide_word(int* range_flag) {
+  return range_flag != nullptr && g_range_words.load(std::memory_order_relaxed) >= 2 ? range_flag + 1
+                                                                                     : nullptr;
+}
+
 static bool valid_cm(int cm, int N) { return cm == 0 || ((cm == 8 || cm == 16 || cm == 32) && N % cm == 0); }
 
 }  // namespace h3k
@@ -1274,6 +1319,12 @@ using namespace iclr17;
 using namespace iclr17::h3k;
 
 extern "C" {
+
+int iclr17_h3_range_words(int words) {
+  ICLR17_REQUIRE(words == 1 || words == 2, ICLR17_EINVAL, "h3_range_words: %d (1 or 2)", words);
+  g_range_words.store(words, std::memory_order_relaxed);
+  return ICLR17_OK;
+}
 
 size_t iclr17_h3k_weight_size(int which, int N) {
   if (N != 128 && N != 192) return 0;
@@ -1375,7 +1426,7 @@ int iclr17_h3_planes(const float* x, long n, uint16_t* planes, int* range_flag, 
   const long n4 = n / 4;
   const int blocks = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
   hipLaunchKernelGGL(h3_planes_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, n4, n,
-                     planes, range_flag);
+                     planes, range_flag, wide_word(range_flag));
   return check_launch("h3_planes");
 }
 
@@ -1387,7 +1438,7 @@ int iclr17_h3_planes_cm(const float* x, int B, int h, int w, int N, int cm, uint
   const long n = (long)B * h * w * N, n4 = n / 4;
   const int blocks = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
   hipLaunchKernelGGL(h3_planes_cm_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, n4, N,
-                     cm, (long)h * w, n, planes, range_flag);
+                     cm, (long)h * w, n, planes, range_flag, wide_word(range_flag));
   return check_launch("h3_planes_cm");
 }
 
@@ -1413,6 +1464,7 @@ int iclr17_analysis_conv1_gdn_h3(const float* x, int B, int H, int W, int N,
   a.out_h3 = out_h3; a.out_h3_plane = (long)B * (H / 4) * (W / 4) * N; a.out_cm = out_cm;
   a.out_x6 = out_x6; a.out_x6_plane = a.out_h3_plane;
   a.range = range_flag;
+  a.wide = wide_word(range_flag);
   a.B = B; a.Hin = H; a.Win = W; a.Hout = H / 4; a.Wout = W / 4;
   a.gh = H / 4; a.gw = W / 4;
   constexpr int TH = 16;
@@ -1451,6 +1503,7 @@ int iclr17_analysis_conv2_gdn_h3(const uint16_t* in_h3, int B, int H, int W, int
   a.out_h3 = out_h3; a.out_h3_plane = (long)B * (h / 2) * (w / 2) * N; a.out_cm = out_cm;
   a.out_x6 = out_x6; a.out_x6_plane = a.out_h3_plane;
   a.range = range_flag;
+  a.wide = wide_word(range_flag);
   a.B = B; a.Hin = h; a.Win = w; a.Hout = h / 2; a.Wout = w / 2;
   a.gh = h / 2; a.gw = w / 2;
   const int TH = h3_tile_rows(a.gh, a.gw, B);
@@ -1494,6 +1547,7 @@ int iclr17_synthesis_deconv_igdn_h3(const uint16_t* in_h3, int B, int h, int w, 
   a.out_x6 = out_x6; a.out_x6_plane = (long)B * 4 * h * w * N;
   a.out_cm = out_cm;
   a.range = range_flag;
+  a.wide = wide_word(range_flag);
   a.B = B; a.Hin = h; a.Win = w; a.Hout = 2 * h; a.Wout = 2 * w;
   a.gh = h; a.gw = w;
   hipStream_t st = (hipStream_t)stream;
@@ -1529,6 +1583,7 @@ int iclr17_analysis_conv3_quant_rate_h3(const uint16_t* in_h3, int B, int H, int
   a.out = y_out;
   a.out_h3 = y_hat_h3; a.out_h3_plane = (long)B * (h / 2) * (w / 2) * N; a.out_cm = out_cm;
   a.range = range_flag;
+  a.wide = wide_word(range_flag);
   a.qmode = quant_mode; a.noise = noise; a.rate = rate_packed;
   a.rtab = rate_table; a.yhat = y_hat; a.partial = bits_partial;
   a.B = B; a.Hin = h; a.Win = w; a.Hout = h / 2; a.Wout = w / 2;

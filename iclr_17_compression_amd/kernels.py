@@ -446,26 +446,43 @@ H3_RANGE_MESSAGE = ("iclr17: an activation of magnitude >= 2^22 does not fit the
                     "chain's results are NaN); run this input with kernels.set_precision('x6')")
 
 
-def h3_range_flag(device) -> Tensor:
-    """The h3 range flag of the current stream on ``device`` (int32, 0 = every value of the
-    current chain fitted the h3 form). One flag per (device, stream), so chains running
-    concurrently on side streams (ImageCompressor.evaluate_many) do not clear each other's."""
+def _h3_flag_words(device):
+    """(both words, word 0, word 1) of the current stream's h3 flag on ``device``: word 0 is the
+    range flag, word 1 the chain's "wide" word (include/iclr17.h, iclr17_h3_range_words)."""
     dev = torch.device(device)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
     f = _range_flags.get(key)
     if f is None:
-        f = torch.zeros(1, device=dev, dtype=torch.int32)
+        if not _range_flags:
+            call("iclr17_h3_range_words", 2)   # every flag this module hands out has two words
+        words = torch.zeros(2, device=dev, dtype=torch.int32)
+        f = (words, words[:1], words[1:])
         _range_flags[key] = f
     return f
 
 
+def h3_range_flag(device) -> Tensor:
+    """The h3 range flag of the current stream on ``device`` (int32, 0 = every value of the
+    current chain fitted the h3 form). One flag per (device, stream), so chains running
+    concurrently on side streams (ImageCompressor.evaluate_many) do not clear each other's."""
+    return _h3_flag_words(device)[1]
+
+
+def h3_wide_flag(device) -> Tensor:
+    """The word after the range flag (int32): 0 = every h3 activation written since the chain
+    began had |x| < 1024, and the layers reading them ran the narrow-activation main loop; the
+    results do not depend on it."""
+    return _h3_flag_words(device)[2]
+
+
 def h3_chain_begin(device) -> None:
-    """Clear the current stream's h3 range flag at the start of a chain of h3 kernels (one fill
-    on the stream; no synchronisation). Every producer sets the flag when a value does not fit;
-    the chain's last kernel (deconv3_h3) reads it and writes NaN results when it is set."""
-    h3_range_flag(device).zero_()
+    """Clear the current stream's h3 range flag and wide word at the start of a chain of h3
+    kernels (one fill on the stream; no synchronisation). Every producer sets the flag when a
+    value does not fit; the chain's last kernel (deconv3_h3) reads it and writes NaN results when
+    it is set."""
+    _h3_flag_words(device)[0].zero_()
 
 
 def h3_range_overflowed(device) -> bool:

@@ -511,6 +511,15 @@ int iclr17_h3_planes(const float* x, long n, uint16_t* planes, int* range_flag, 
  * layout each h3 layer reads (conv2 / conv3: cm 8; deconv1 / deconv2: cm 16; deconv3: cm 32) */
 int iclr17_h3_planes_cm(const float* x, int B, int h, int w, int N, int cm, uint16_t* planes,
                         int* range_flag, void* stream);
+/* How many ints every range_flag pointer handed to the h3 entry points addresses: 1 (the default)
+ * or 2. With two, word 1 is the chain's "wide" word: every kernel that writes an h3 activation
+ * sets it to 1 when a value has |x| ≥ 1024, and a layer that reads it 0 at its start runs its
+ * main loop in the narrow-activation form (the 2^11 factor of the hi·hi product on the one
+ * activation fragment instead of the weight fragments: fewer VALU instructions, bit-identical
+ * results). The caller clears both words where a chain begins and must hand a layer the flag its
+ * input's producers saw since then. With one word, or a null range_flag, nothing past word 0 is
+ * read or written and every layer runs the general form. Process-wide; set it before launching. */
+int iclr17_h3_range_words(int words);
 /* A packed operand [taps][K/4][N][4] fp32 → two fp16 planes [2][taps][K/8][N][8] of w·σ_w + the
  * trailer (the h3 conv3 weights: the ICLR17_W_CONV5 packing with taps 25, K = N; deconv3's
  * ICLR17_W_DECONV9 packing with taps 9, 48 columns; a GDN γ_eff packing with taps 1, K = N).
