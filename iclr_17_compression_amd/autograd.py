@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import kernels
+from . import chain, kernels
 
 Tensor = torch.Tensor
 
@@ -54,6 +54,7 @@ class GDNFn(torch.autograd.Function):
     def forward(ctx, x, module, beta, gamma):
         beta_eff, gp = module.effective_params()
         ctx.module = module
+        ctx.x6 = kernels.precision() != "fp32"   # dγ's contraction (kernels.gdn_wgrad)
         ctx.save_for_backward(x)
         return kernels.gdn(x, beta_eff, gp, module.inverse)
 
@@ -65,7 +66,7 @@ class GDNFn(torch.autograd.Function):
         dx, dn, u = kernels.gdn_backward(x, g, be, gp, gpt, m.inverse)
         bb, gb, _ = m.bounds_f32()
         dbeta, dgamma = kernels.gdn_param_grads(dn, u, kernels.bias_grad_nhwc(dn), m.beta, m.gamma,
-                                                bb, gb)
+                                                bb, gb, x6=ctx.x6)
         return dx, None, dbeta.view_as(m.beta), dgamma.view_as(m.gamma)
 
 
@@ -121,14 +122,21 @@ def _split_of(saved: Dict[str, Tensor], key: str) -> Tensor:
 
 
 # ------------------------------------------------------------------------------ analysis
-def analysis_features_train(enc, x: Tensor):
+def _train_mode(mode: Optional[str]) -> chain.Mode:
+    """The mode object whose training kernels a step in ``mode`` (default: kernels.precision())
+    runs: h3, fp32, or x6 (also for bf16)."""
+    return chain.MODES[chain.MODES[mode or kernels.precision()].train_as]
+
+
+def analysis_features_train(enc, x: Tensor, mode: Optional[str] = None):
     """conv1+GDN1, conv2+GDN2 keeping the pre-activations the backward needs. In the x6 mode the
     kernels also hand conv2 (and conv3) their input in split form; "a2s" is then set. In the h3
     mode the forward runs the codec's own h3 kernels, which also write the split forms (the x6
     weight-gradient operands) and the pre-activations; "a2h" (conv3's h3 input) is then set."""
     N = enc.out_channel_N
-    if kernels.precision() == "h3":
-        kernels.h3_chain_begin(x.device)
+    m = _train_mode(mode)
+    if m.name == "h3":
+        m.begin(x.device)
         ge1, ge2 = enc.gdn1.effective_params_h3(), enc.gdn2.effective_params_h3()
         w2h, _ = enc.packed_h3()
         a1h, _, a1s, u1 = kernels.conv1_gdn_h3(x, enc.packed_conv1_h3(), enc.conv1.bias, *ge1, N,
@@ -137,7 +145,7 @@ def analysis_features_train(enc, x: Tensor):
                                                want_pre=True)
         return None, {"x": x, "u1": u1, "u2": u2, "a1s": a1s, "a2s": a2s, "a2h": a2h}
     w1, w2, _, g1, g2 = enc.packed()
-    if kernels.precision() != "fp32":
+    if m.name == "x6":
         e1, e2 = enc.gdn1.effective_params_x6(), enc.gdn2.effective_params_x6()
         a1s, a1, u1 = kernels.conv1x6_gdn(x, enc.packed_conv1_x6(), enc.conv1.bias, e1[0], e1[2],
                                           N, want_f32=True, want_pre=True)
@@ -161,16 +169,18 @@ def conv1_input_grad(enc, g_u1: Tensor) -> Tensor:
 
 
 def analysis_backward(enc, saved: Dict[str, Tensor], g_y: Tensor,
-                      g_y_split: Optional[Tensor] = None, want_dx: bool = False) -> Dict[str, Tensor]:
-    """∂L/∂y (NHWC) → parameter gradients of Analysis_net_17 (analysis_17.py:14-39). In the x6
-    mode the input-gradient contractions run on split-form gradients (g_y_split, or split here)."""
+                      g_y_split: Optional[Tensor] = None, want_dx: bool = False, *,
+                      mode: str) -> Dict[str, Tensor]:
+    """∂L/∂y (NHWC) → parameter gradients of Analysis_net_17 (analysis_17.py:14-39). ``mode``: the
+    one the forward that made ``saved`` ran in. Unless that is fp32 the input-gradient
+    contractions run in x6 on split-form gradients (g_y_split, or split here)."""
     bb1, gb1, _ = enc.gdn1.bounds_f32()
     bb2, gb2, _ = enc.gdn2.bounds_f32()
     w3t, w2t = enc.packed_bwd()
-    x6 = kernels.precision() != "fp32"
+    x6 = mode != "fp32"
     p2 = None if x6 else enc.gdn2.effective_params_bwd()
     p1 = None if x6 else enc.gdn1.effective_params_bwd()
-    if kernels.precision() != "fp32":
+    if x6:
         if g_y_split is None:
             g_y_split = kernels.split_planes(g_y)
         x2, x1 = enc.gdn2.effective_params_bwd_x6(), enc.gdn1.effective_params_bwd_x6()
@@ -181,7 +191,7 @@ def analysis_backward(enc, saved: Dict[str, Tensor], g_y: Tensor,
                                                            g6=x2[3], g6t=x2[4], want_f32=False)
         dW2 = kernels.wgrad_k5_x6(g_u2s, a1s)
         dg2 = kernels.gdn_param_grads(dn2, saved["u2"], dbe2, enc.gdn2.beta,
-                                                     enc.gdn2.gamma, bb2, gb2)
+                                      enc.gdn2.gamma, bb2, gb2, x6=x6)
         g_u1, dn1, db1, dbe1, g_u1s = kernels.bwd_conv_gdn(g_u2, w2t, saved["u1"], *x1[:3],
                                                            g_split=g_u2s, want_split=True,
                                                            g6=x1[3], g6t=x1[4], want_f32=want_dx)
@@ -191,12 +201,12 @@ def analysis_backward(enc, saved: Dict[str, Tensor], g_y: Tensor,
         g_u2, dn2, db2, dbe2 = kernels.bwd_conv_gdn(g_y, w3t, saved["u2"], *p2)
         dW2 = kernels.wgrad_k5(g_u2, saved["a1"])
         dg2 = kernels.gdn_param_grads(dn2, saved["u2"], dbe2, enc.gdn2.beta,
-                                                     enc.gdn2.gamma, bb2, gb2)
+                                      enc.gdn2.gamma, bb2, gb2, x6=x6)
         g_u1, dn1, db1, dbe1 = kernels.bwd_conv_gdn(g_u2, w2t, saved["u1"], *p1)
         dW1 = kernels.wgrad_k9(g_u1, saved["x"])
     dbeta2, dgamma2 = dg2
     dbeta1, dgamma1 = kernels.gdn_param_grads(dn1, saved["u1"], dbe1, enc.gdn1.beta,
-                                                             enc.gdn1.gamma, bb1, gb1)
+                                              enc.gdn1.gamma, bb1, gb1, x6=x6)
     grads = {"conv1.weight": dW1, "conv1.bias": db1, "gdn1.beta": dbeta1, "gdn1.gamma": dgamma1,
              "conv2.weight": dW2, "conv2.bias": db2, "gdn2.beta": dbeta2, "gdn2.gamma": dgamma2,
              "conv3.weight": dW3}
@@ -207,13 +217,14 @@ def analysis_backward(enc, saved: Dict[str, Tensor], g_y: Tensor,
 
 # ----------------------------------------------------------------------------- synthesis
 def synthesis_forward_train(dec, y_nhwc: Tensor, x_ref: Optional[Tensor] = None,
-                            y_split: Optional[Tensor] = None, y_h3: Optional[Tensor] = None):
-    if kernels.precision() == "h3":
+                            y_split: Optional[Tensor] = None, y_h3: Optional[Tensor] = None,
+                            mode: Optional[str] = None):
+    m = _train_mode(mode)
+    if m.name == "h3":
         # the codec's h3 kernels; their x6 outputs are the weight-gradient operands and the
         # pre-activations the IGDN backward's
         if y_h3 is None:   # the Decoder on its own: its chain starts here
-            kernels.h3_chain_begin(y_nhwc.device)
-            y_h3 = kernels.h3_planes(y_nhwc, cm=kernels.DECONV_CM)
+            y_h3 = m.latent_operand(y_nhwc)
         h1, h2 = dec.igdn1.effective_params_h3(), dec.igdn2.effective_params_h3()
         x1, x2, x3 = dec.packed_h3k()
         s1h, _, s1s, v1 = kernels.deconv_igdn_h3(y_h3, x1, dec.deconv1.bias, *h1, want_x6=True,
@@ -224,9 +235,9 @@ def synthesis_forward_train(dec, y_nhwc: Tensor, x_ref: Optional[Tensor] = None,
                                                  want_recon=True, sse_unclipped=x_ref is not None)
         return clipped, recon, sse, {"y": y_nhwc, "v1": v1, "v2": v2, "s1s": s1s, "s2s": s2s}
     d1, d2, d3, q1, q2 = dec.packed()
-    if kernels.precision() != "fp32":
+    if m.name == "x6":
         if y_split is None:
-            y_split = kernels.split_planes(y_nhwc)
+            y_split = m.latent_operand(y_nhwc)
         e1, e2 = dec.igdn1.effective_params_x6(), dec.igdn2.effective_params_x6()
         s1s, s1, v1 = kernels.deconv_igdn_x6(y_split, d1, dec.deconv1.bias, *e1, want_f32=True,
                                              want_pre=True)
@@ -247,12 +258,13 @@ def synthesis_forward_train(dec, y_nhwc: Tensor, x_ref: Optional[Tensor] = None,
 
 def synthesis_backward(dec, saved: Dict[str, Tensor], g_recon: Tensor, g_bpp: Optional[Tensor] = None,
                        rate_packed: Optional[Tensor] = None, count: float = 0.0,
-                       want_split: bool = False):
+                       want_split: bool = False, *, mode: str):
     """∂L/∂recon (NCHW) → (∂L/∂ỹ NHWC incl. the rate term when g_bpp is given, parameter
     gradients of Synthesis_net_17, rate-parameter partials[, ∂L/∂ỹ in split form (x6 mode,
-    else None)]). In the x6 mode the input-gradient contractions run in x6, each kernel handing
-    the next its gradient in split form."""
-    x6 = kernels.precision() != "fp32"
+    else None)]). ``mode``: the one the forward that made ``saved`` ran in. Unless that is fp32 the
+    input-gradient contractions run in x6, each kernel handing the next its gradient in split
+    form."""
+    x6 = mode != "fp32"
     N = dec.out_channel_N
     bq1, gq1, _ = dec.igdn1.bounds_f32()
     bq2, gq2, _ = dec.igdn2.bounds_f32()
@@ -264,9 +276,9 @@ def synthesis_backward(dec, saved: Dict[str, Tensor], g_recon: Tensor, g_bpp: Op
     B, h, w, _ = y.shape
     g_ys = None
     gdn_q2 = lambda: kernels.gdn_param_grads(dnq2, saved["v2"], dbeq2, dec.igdn2.beta,  # noqa: E731
-                                             dec.igdn2.gamma, bq2, gq2)
+                                             dec.igdn2.gamma, bq2, gq2, x6=x6)
     gdn_q1 = lambda: kernels.gdn_param_grads(dnq1, saved["v1"], dbeq1, dec.igdn1.beta,  # noqa: E731
-                                             dec.igdn1.gamma, bq1, gq1)
+                                             dec.igdn1.gamma, bq1, gq1, x6=x6)
     if x6:
         s2s, s1s = _split_of(saved, "s2"), _split_of(saved, "s1")
         ys = saved.get("ys") if saved.get("ys") is not None else kernels.split_planes(y)
@@ -313,11 +325,11 @@ class CodecTrainFn(torch.autograd.Function):
     """ImageCompressor training forward: (clipped, ỹ NCHW-view, bpp, mse of unclipped recon)."""
 
     @staticmethod
-    def forward(ctx, x, noise, net, *params):
+    def forward(ctx, x, noise, net, mode, *params):
         ctx.set_materialize_grads(False)
         enc, dec, be = net.Encoder, net.Decoder, net.bitEstimator
         B, _, H, W = x.shape
-        a2, saved_a = analysis_features_train(enc, x)
+        a2, saved_a = analysis_features_train(enc, x, mode)
         w3 = enc.packed_w3()
         rate = be.packed()
         a2s, a2h, y_h3 = saved_a.get("a2s"), saved_a.get("a2h"), None
@@ -330,10 +342,11 @@ class CodecTrainFn(torch.autograd.Function):
         else:
             (y_tilde, bits_part), y_split = kernels.conv3_quant_rate(a2, w3, rate, noise), None
         clipped, recon, sse_part, saved_s = synthesis_forward_train(dec, y_tilde, x_ref=x,
-                                                                    y_split=y_split, y_h3=y_h3)
+                                                                    y_split=y_split, y_h3=y_h3,
+                                                                    mode=mode)
         _, bpp = kernels.reduce_partials(bits_part, 1.0 / (B * H * W), per_image=False)
         _, mse = kernels.reduce_partials(sse_part, 1.0 / (B * 3 * H * W), per_image=False)
-        ctx.net = net
+        ctx.net, ctx.mode = net, mode
         ctx.saved_a, ctx.saved_s = saved_a, saved_s
         ctx.recon, ctx.x, ctx.rate, ctx.count = recon, x, rate, float(B * H * W)
         return clipped, y_tilde.permute(0, 3, 1, 2), bpp, mse
@@ -348,7 +361,8 @@ class CodecTrainFn(torch.autograd.Function):
         else:
             g_recon = kernels.grad_recon(ctx.recon, ctx.x, g_mse, g_clipped)
         g_y, gs, rpart, g_ys = synthesis_backward(dec, ctx.saved_s, g_recon, g_bpp, ctx.rate,
-                                                  ctx.count, want_split=g_ytilde is None)
+                                                  ctx.count, want_split=g_ytilde is None,
+                                                  mode=ctx.mode)
         red = getattr(net, "_grad_reducer", None)
         red = red if red is not None and red.active else None
         if red is not None:   # the synthesis gradients all-reduce during the analysis backward
@@ -358,7 +372,8 @@ class CodecTrainFn(torch.autograd.Function):
         want_dx = ctx.needs_input_grad[0]
         rg = (kernels.rate_param_grads(rpart, be.params_in_order())
               if g_bpp is not None else [None] * 11)
-        ga = analysis_backward(enc, ctx.saved_a, g_y.contiguous(), g_ys, want_dx=want_dx)
+        ga = analysis_backward(enc, ctx.saved_a, g_y.contiguous(), g_ys, want_dx=want_dx,
+                               mode=ctx.mode)
         grads += _ordered(enc, "Encoder.", ga)
         grads += _ordered(dec, "Decoder.", gs)
         names = [n for n, _ in be.named_parameters()]
@@ -372,7 +387,7 @@ class CodecTrainFn(torch.autograd.Function):
         if dx is not None and g_mse is not None:   # the loss's own x: ∂mse/∂x = −∂mse/∂recon
             dx = dx - kernels.grad_recon(ctx.recon, ctx.x, g_mse, None)
         ctx.saved_a = ctx.saved_s = ctx.recon = None
-        return (dx, None, None, *grads)
+        return (dx, None, None, None, *grads)
 
 
 class MsSsimFn(torch.autograd.Function):
@@ -441,37 +456,37 @@ class AnalysisFn(torch.autograd.Function):
     kernels (``Analysis_net_17.y_nhwc``), so round(y) is the codec's ŷ with grad on or off."""
 
     @staticmethod
-    def forward(ctx, x, enc, *params):
+    def forward(ctx, x, enc, mode, *params):
         ctx.set_materialize_grads(False)
-        _, saved = analysis_features_train(enc, x)   # a2s stays: conv3's x6 weight gradient
-        ctx.enc, ctx.saved = enc, saved
-        return enc.y_nhwc(x, feats=saved).permute(0, 3, 1, 2).contiguous()
+        _, saved = analysis_features_train(enc, x, mode)   # a2s stays: conv3's x6 weight gradient
+        ctx.enc, ctx.saved, ctx.mode = enc, saved, mode
+        return enc.y_nhwc(x, mode, feats=saved).permute(0, 3, 1, 2).contiguous()
 
     @staticmethod
     def backward(ctx, g_y):
         if g_y is None:
-            return (None, None) + (None,) * len(list(ctx.enc.parameters()))
+            return (None, None, None) + (None,) * len(list(ctx.enc.parameters()))
         ga = analysis_backward(ctx.enc, ctx.saved, g_y.permute(0, 2, 3, 1).contiguous(),
-                               want_dx=ctx.needs_input_grad[0])
+                               want_dx=ctx.needs_input_grad[0], mode=ctx.mode)
         ctx.saved = None
-        return (ga.get("x"), None, *_ordered(ctx.enc, "", ga))
+        return (ga.get("x"), None, None, *_ordered(ctx.enc, "", ga))
 
 
 class SynthesisFn(torch.autograd.Function):
     """Synthesis_net_17.forward with autograd: unclipped reconstruction (NCHW)."""
 
     @staticmethod
-    def forward(ctx, y, dec, *params):
+    def forward(ctx, y, dec, mode, *params):
         ctx.set_materialize_grads(False)
-        _, recon, _, saved = synthesis_forward_train(dec, dec.to_nhwc(y))
-        ctx.dec, ctx.saved = dec, saved
+        _, recon, _, saved = synthesis_forward_train(dec, dec.to_nhwc(y), mode=mode)
+        ctx.dec, ctx.saved, ctx.mode = dec, saved, mode
         return recon
 
     @staticmethod
     def backward(ctx, g_recon):
         n_params = len(list(ctx.dec.parameters()))
         if g_recon is None:
-            return (None, None) + (None,) * n_params
-        g_y, gs, _ = synthesis_backward(ctx.dec, ctx.saved, g_recon.contiguous())
+            return (None, None, None) + (None,) * n_params
+        g_y, gs, _ = synthesis_backward(ctx.dec, ctx.saved, g_recon.contiguous(), mode=ctx.mode)
         ctx.saved = None
-        return (g_y.permute(0, 3, 1, 2), None, *_ordered(ctx.dec, "", gs))
+        return (g_y.permute(0, 3, 1, 2), None, None, *_ordered(ctx.dec, "", gs))

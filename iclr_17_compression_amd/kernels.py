@@ -13,6 +13,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+import threading
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -59,6 +60,57 @@ def _check_image_dims(H: int, W: int) -> None:
 def _check_channels(N: int) -> None:
     if N not in (128, 192):
         raise Iclr17Error(f"iclr17: channel count N={N} unsupported (kernels are built for 128 and 192)")
+
+
+def _image_dims(x: Tensor, N: int):
+    """The analysis transform's input, an fp32 image batch [B,3,H,W] → (B, H, W)."""
+    _check(x, "image", 4)
+    B, C, H, W = x.shape
+    if C != 3:
+        raise Iclr17Error(f"iclr17: the analysis transform takes 3-channel images (got {C})")
+    _check_image_dims(H, W)
+    _check_channels(N)
+    return B, H, W
+
+
+def _check_act(h: Tensor):
+    """An fp32 NHWC activation; returns (B, h, w, N) like _check_split / _check_h3 / _check_bf16."""
+    _check(h, "activation", 4)
+    return h.shape
+
+
+def _act_dims(dims, stride: int):
+    """(B, h, w, N) of an activation at 1/stride of the image → (B, h, w, N, H, W), checked."""
+    B, h, w, N = dims
+    _check_channels(N)
+    H, W = stride * h, stride * w
+    _check_image_dims(H, W)
+    return B, h, w, N, H, W
+
+
+def _quant_mode(noise: Optional[Tensor], shape):
+    """conv3's quantiser: (ICLR17_QUANT_ROUND, None), or with noise (NCHW, ``shape``)
+    (ICLR17_QUANT_NOISE, the noise contiguous)."""
+    if noise is None:
+        return _lib.ICLR17_QUANT_ROUND, None
+    _check(noise, "noise", 4)
+    if tuple(noise.shape) != shape:
+        raise Iclr17Error(f"iclr17: noise must be {shape} (got {tuple(noise.shape)})")
+    return _lib.ICLR17_QUANT_NOISE, noise.contiguous()
+
+
+def _recon_outputs(B: int, H: int, W: int, device, x_ref: Optional[Tensor], want_recon: bool):
+    """deconv3's outputs → (clipped, recon | None, x_ref contiguous | None, SSE partials | None)."""
+    clipped = torch.empty(B, 3, H, W, device=device, dtype=torch.float32)
+    recon = torch.empty_like(clipped) if want_recon else None
+    partial = None
+    if x_ref is not None:
+        _check(x_ref, "reference image", 4)
+        if tuple(x_ref.shape) != (B, 3, H, W):
+            raise Iclr17Error("iclr17: reference image shape mismatch")
+        x_ref = x_ref.contiguous()
+        partial = torch.empty(B, output_partials_per_image(H, W), device=device, dtype=torch.float64)
+    return clipped, recon, x_ref, partial
 
 
 # ------------------------------------------------------------------------------ packing
@@ -164,12 +216,7 @@ def pack_rate(params: Sequence[Tensor]) -> Tensor:
 def conv1_gdn(x: Tensor, wp: Tensor, bias: Tensor, beta_eff: Tensor, gp: Tensor, N: int,
               want_pre: bool = False):
     """analysis_17.py:14-17,33: x NCHW [B,3,H,W] → NHWC [B,H/4,W/4,N] (+ pre-GDN)."""
-    _check(x, "image", 4)
-    B, C, H, W = x.shape
-    if C != 3:
-        raise Iclr17Error(f"iclr17: the analysis transform takes 3-channel images (got {C})")
-    _check_image_dims(H, W)
-    _check_channels(N)
+    B, H, W = _image_dims(x, N)
     x = x.contiguous()
     out = torch.empty(B, H // 4, W // 4, N, device=x.device, dtype=torch.float32)
     pre = torch.empty_like(out) if want_pre else None
@@ -181,11 +228,7 @@ def conv1_gdn(x: Tensor, wp: Tensor, bias: Tensor, beta_eff: Tensor, gp: Tensor,
 def conv2_gdn(h: Tensor, wp: Tensor, bias: Tensor, beta_eff: Tensor, gp: Tensor,
               want_pre: bool = False):
     """analysis_17.py:18-21,34: NHWC [B,H/4,W/4,N] → [B,H/8,W/8,N]."""
-    _check(h, "activation", 4)
-    B, h4, w4, N = h.shape
-    _check_channels(N)
-    H, W = 4 * h4, 4 * w4
-    _check_image_dims(H, W)
+    B, h4, w4, N, H, W = _act_dims(_check_act(h), 4)
     out = torch.empty(B, h4 // 2, w4 // 2, N, device=h.device, dtype=torch.float32)
     pre = torch.empty_like(out) if want_pre else None
     call("iclr17_analysis_conv2_gdn", _p(h.contiguous()), B, H, W, N, _p(wp), _p(bias),
@@ -195,11 +238,7 @@ def conv2_gdn(h: Tensor, wp: Tensor, bias: Tensor, beta_eff: Tensor, gp: Tensor,
 
 def conv3(h: Tensor, wp: Tensor) -> Tensor:
     """analysis_17.py:22,35 (no quantiser): NHWC [B,H/8,W/8,N] → y NHWC [B,H/16,W/16,N]."""
-    _check(h, "activation", 4)
-    B, h8, w8, N = h.shape
-    _check_channels(N)
-    H, W = 8 * h8, 8 * w8
-    _check_image_dims(H, W)
+    B, h8, w8, N, H, W = _act_dims(_check_act(h), 8)
     y = torch.empty(B, h8 // 2, w8 // 2, N, device=h.device, dtype=torch.float32)
     call("iclr17_analysis_conv3", _p(h.contiguous()), B, H, W, N, _p(wp), _p(y), _stream(h))
     return y
@@ -215,18 +254,8 @@ def conv3_quant_rate(h: Tensor, wp: Tensor, rate_packed: Tensor, noise: Optional
 
     noise (training) is NCHW [B,N,H/16,W/16], the shape model.py:48 draws. rtab (``rate_table``
     of rate_packed, round mode): bits of the integer latents by lookup."""
-    _check(h, "activation", 4)
-    B, h8, w8, N = h.shape
-    _check_channels(N)
-    H, W = 8 * h8, 8 * w8
-    _check_image_dims(H, W)
-    mode = _lib.ICLR17_QUANT_ROUND
-    if noise is not None:
-        _check(noise, "noise", 4)
-        if tuple(noise.shape) != (B, N, h8 // 2, w8 // 2):
-            raise Iclr17Error(f"iclr17: noise must be {(B, N, h8 // 2, w8 // 2)} (got {tuple(noise.shape)})")
-        noise = noise.contiguous()
-        mode = _lib.ICLR17_QUANT_NOISE
+    B, h8, w8, N, H, W = _act_dims(_check_act(h), 8)
+    mode, noise = _quant_mode(noise, (B, N, h8 // 2, w8 // 2))
     y_hat = torch.empty(B, h8 // 2, w8 // 2, N, device=h.device, dtype=torch.float32)
     y = torch.empty_like(y_hat) if want_y else None
     T = rate_partials_per_image(H, W, N)
@@ -252,6 +281,7 @@ def deconv_igdn(h: Tensor, wp: Tensor, bias: Tensor, beta_eff: Tensor, gp: Tenso
 # ------------------------------------------------------------- x6 (bf16x6) precision mode
 PRECISIONS = ("x6", "h3", "fp32", "bf16")
 _precision = os.environ.get("ICLR17_PRECISION", "h3")
+_scoped = threading.local()   # .mode: the thread's innermost precision_scope, if any
 
 
 def precision() -> str:
@@ -263,17 +293,40 @@ def precision() -> str:
     "fp32" (exact-f32 MFMA products) or "bf16" (the throughput mode: bf16 activations and weights,
     one bf16 product per MAC, fp32 accumulation — no parity claim). Training: in the h3 mode the
     forward runs the h3 kernels and the backward the x6 ones; the x6 and bf16 modes train on the
-    x6 kernels, the fp32 mode on the exact-f32 ones."""
+    x6 kernels, the fp32 mode on the exact-f32 ones.
+
+    This is the process default (``set_precision``), or the calling thread's innermost
+    ``precision_scope``. A public call reads it once and carries it; an autograd backward runs in
+    the mode its forward recorded."""
+    scoped = getattr(_scoped, "mode", None)
+    if scoped is not None:
+        return scoped
     if _precision not in PRECISIONS:
         raise Iclr17Error(f"iclr17: ICLR17_PRECISION must be one of {PRECISIONS} (got {_precision!r})")
     return _precision
 
 
 def set_precision(mode: str) -> None:
+    """Set the process default (not what a thread inside a ``precision_scope`` reads)."""
     global _precision
     if mode not in PRECISIONS:
         raise Iclr17Error(f"iclr17: precision must be one of {PRECISIONS} (got {mode!r})")
     _precision = mode
+
+
+@contextlib.contextmanager
+def precision_scope(mode: str):
+    """Override ``precision()`` for the calling thread until the block ends (nests; the previous
+    state comes back on exit, also on an exception). Other threads and the process default are
+    untouched."""
+    if mode not in PRECISIONS:
+        raise Iclr17Error(f"iclr17: precision must be one of {PRECISIONS} (got {mode!r})")
+    outer = getattr(_scoped, "mode", None)
+    _scoped.mode = mode
+    try:
+        yield
+    finally:
+        _scoped.mode = outer
 
 
 # A split-form activation is an int16 tensor [3, B, h, w, N]: the bf16 bit patterns of the exact
@@ -285,6 +338,7 @@ def _check_split(s: Tensor, what: str):
         raise Iclr17Error(f"iclr17: {what} must be a device tensor (there is no CPU path)")
     if not s.is_contiguous():
         raise Iclr17Error(f"iclr17: {what} must be contiguous")
+    return s.shape[1:]
 
 
 def split_planes(x: Tensor) -> Tensor:
@@ -325,12 +379,7 @@ def conv1_gdn_x6(x: Tensor, wp: Tensor, bias: Tensor, beta_eff: Tensor, gp: Tens
                  want_f32: bool = False, want_pre: bool = False, g6: Optional[Tensor] = None):
     """conv1_gdn with the output in split form (+ fp32 / pre-GDN on request); with g6
     (split_packed of gp) the GDN contraction runs in x6 too."""
-    _check(x, "image", 4)
-    B, C, H, W = x.shape
-    if C != 3:
-        raise Iclr17Error(f"iclr17: the analysis transform takes 3-channel images (got {C})")
-    _check_image_dims(H, W)
-    _check_channels(N)
+    B, H, W = _image_dims(x, N)
     x = x.contiguous()
     split = torch.empty(3, B, H // 4, W // 4, N, device=x.device, dtype=torch.int16)
     out = torch.empty(B, H // 4, W // 4, N, device=x.device) if want_f32 else None
@@ -344,12 +393,7 @@ def conv1x6_gdn(x: Tensor, w_split: Tensor, bias: Tensor, beta_eff: Tensor, g6: 
                 want_f32: bool = False, want_pre: bool = False):
     """analysis_17.py:14-17 with both contractions in x6 (w_split: ``pack_conv1_x6``).
     Returns (split, fp32 | None, pre | None) like ``conv1_gdn_x6``."""
-    _check(x, "image", 4)
-    B, C, H, W = x.shape
-    if C != 3:
-        raise Iclr17Error(f"iclr17: the analysis transform takes 3-channel images (got {C})")
-    _check_image_dims(H, W)
-    _check_channels(N)
+    B, H, W = _image_dims(x, N)
     if w_split.dtype != torch.int16 or w_split.numel() != 3 * 256 * N:
         raise Iclr17Error("iclr17: conv1x6_gdn needs the split ICLR17_W_CONV1_X6 packing")
     x = x.contiguous()
@@ -370,11 +414,7 @@ def conv2_gdn_x6(hs: Tensor, wp: Tensor, bias: Tensor, beta_eff: Tensor, gp: Ten
                  g6: Tensor, want_f32: bool = False, want_pre: bool = False):
     """conv2_gdn on a split-form input (g6: split_packed γ); returns (split, fp32 | None,
     pre | None)."""
-    _check_split(hs, "activation")
-    _, B, h4, w4, N = hs.shape
-    _check_channels(N)
-    H, W = 4 * h4, 4 * w4
-    _check_image_dims(H, W)
+    B, h4, w4, N, H, W = _act_dims(_check_split(hs, "activation"), 4)
     split = torch.empty(3, B, h4 // 2, w4 // 2, N, device=hs.device, dtype=torch.int16)
     out = torch.empty(B, h4 // 2, w4 // 2, N, device=hs.device) if want_f32 else None
     pre = torch.empty(B, h4 // 2, w4 // 2, N, device=hs.device) if want_pre else None
@@ -389,18 +429,8 @@ def conv3_quant_rate_x6(hs: Tensor, wp: Tensor, rate_packed: Tensor,
     """conv3_quant_rate on a split-form input. Returns (y_hat, bits_partial, y | None,
     y_hat_split). rtab as ``conv3_quant_rate``. w_split (``split_packed(wp, 25, N, N)``, cached by
     ``Analysis_net_17.packed_w3_split``): the weights pre-split, bit-identical results."""
-    _check_split(hs, "activation")
-    _, B, h8, w8, N = hs.shape
-    _check_channels(N)
-    H, W = 8 * h8, 8 * w8
-    _check_image_dims(H, W)
-    mode = _lib.ICLR17_QUANT_ROUND
-    if noise is not None:
-        _check(noise, "noise", 4)
-        if tuple(noise.shape) != (B, N, h8 // 2, w8 // 2):
-            raise Iclr17Error(f"iclr17: noise must be {(B, N, h8 // 2, w8 // 2)} (got {tuple(noise.shape)})")
-        noise = noise.contiguous()
-        mode = _lib.ICLR17_QUANT_NOISE
+    B, h8, w8, N, H, W = _act_dims(_check_split(hs, "activation"), 8)
+    mode, noise = _quant_mode(noise, (B, N, h8 // 2, w8 // 2))
     y_hat = torch.empty(B, h8 // 2, w8 // 2, N, device=hs.device, dtype=torch.float32)
     y_hat_split = torch.empty(3, B, h8 // 2, w8 // 2, N, device=hs.device, dtype=torch.int16)
     y = torch.empty_like(y_hat) if want_y else None
@@ -639,12 +669,7 @@ def conv1_gdn_h3(x: Tensor, w_h3: Tensor, bias: Tensor, beta_eff: Tensor, gh3: T
     GDN.effective_params_h3's γ). Returns (h3 | None — chunk-major [2,B,N/out_cm,H/4,W/4,out_cm],
     conv2's input —, fp32 | None), and with ``want_x6`` / ``want_pre`` (training) also (x6 split |
     None, GDN1 input conv1 + bias | None)."""
-    _check(x, "image", 4)
-    B, C, H, W = x.shape
-    if C != 3:
-        raise Iclr17Error(f"iclr17: the analysis transform takes 3-channel images (got {C})")
-    _check_image_dims(H, W)
-    _check_channels(N)
+    B, H, W = _image_dims(x, N)
     if w_h3.dtype != torch.int16 or w_h3.numel() != query("iclr17_h3k_weight_size", _lib.ICLR17_H3K_CONV1, N):
         raise Iclr17Error("iclr17: conv1_gdn_h3 needs pack_conv1_h3 weights")
     if gh3.dtype != torch.int16 or gh3.numel() != query("iclr17_split_packed_h3_size", 1, N, N):
@@ -671,10 +696,7 @@ def conv2_gdn_h3(hs: Tensor, wk: Tensor, bias: Tensor, beta_eff: Tensor, gh3: Te
     fp32 | None, x6 split | None). wk:
     ``pack_h3k(ICLR17_H3K_CONV5, w)``; gh3: GDN.effective_params_h3's γ. With ``want_pre``
     (training) a fourth result: GDN2's input conv2 + bias (fp32 NHWC)."""
-    B, h4, w4, N = _check_h3(hs, "activation", CONV_CM)
-    _check_channels(N)
-    H, W = 4 * h4, 4 * w4
-    _check_image_dims(H, W)
+    B, h4, w4, N, H, W = _act_dims(_check_h3(hs, "activation", CONV_CM), 4)
     if wk.numel() != query("iclr17_h3k_weight_size", _lib.ICLR17_H3K_CONV5, N):
         raise Iclr17Error("iclr17: conv2_gdn_h3 needs pack_h3k(ICLR17_H3K_CONV5) weights")
     if gh3.dtype != torch.int16 or gh3.numel() != query("iclr17_split_packed_h3_size", 1, N, N):
@@ -700,19 +722,10 @@ def conv3_quant_rate_h3(hs: Tensor, wh: Tensor, rate_packed: Tensor,
     ``pack_h3k(ICLR17_H3K_CONV5, conv3.weight)``), input chunk-major 8. Returns (y_hat NHWC,
     bits_partial [B, iclr17_conv3_h3_partials_per_image], y | None, y_hat h3 | None — layout
     out_cm, deconv1's input)."""
-    B, h8, w8, N = _check_h3(hs, "activation", CONV_CM)
-    _check_channels(N)
-    H, W = 8 * h8, 8 * w8
-    _check_image_dims(H, W)
+    B, h8, w8, N, H, W = _act_dims(_check_h3(hs, "activation", CONV_CM), 8)
     if wh.dtype != torch.int16 or wh.numel() != query("iclr17_h3k_weight_size", _lib.ICLR17_H3K_CONV5, N):
         raise Iclr17Error("iclr17: conv3_quant_rate_h3 needs pack_h3k(ICLR17_H3K_CONV5) weights")
-    mode = _lib.ICLR17_QUANT_ROUND
-    if noise is not None:
-        _check(noise, "noise", 4)
-        if tuple(noise.shape) != (B, N, h8 // 2, w8 // 2):
-            raise Iclr17Error(f"iclr17: noise must be {(B, N, h8 // 2, w8 // 2)} (got {tuple(noise.shape)})")
-        noise = noise.contiguous()
-        mode = _lib.ICLR17_QUANT_NOISE
+    mode, noise = _quant_mode(noise, (B, N, h8 // 2, w8 // 2))
     y_hat = torch.empty(B, h8 // 2, w8 // 2, N, device=hs.device, dtype=torch.float32)
     y_hat_h3 = _h3_out(B, h8 // 2, w8 // 2, N, out_cm, hs.device) if want_h3 else None
     y = torch.empty_like(y_hat) if want_y else None
@@ -757,15 +770,19 @@ def deconv_igdn_h3(hs: Tensor, wh: Tensor, bias: Tensor, beta_eff: Tensor, gh3: 
     return h3, out, x6
 
 
-def ms_ssim(x: Tensor, y: Tensor, data_range: float = 1.0) -> Tensor:
-    """Per-image MS-SSIM [B] of NCHW fp32 image batches (models/ms_ssim_torch.py:123-196 as
-    train.py:178 calls it), on the GPU."""
+def _image_pair(x: Tensor, y: Tensor, what: str):
     _check(x, "image", 4)
     _check(y, "image", 4)
     if x.shape != y.shape or x.shape[1] != 3:
-        raise Iclr17Error(f"iclr17: ms_ssim needs two [B,3,H,W] batches of one shape "
+        raise Iclr17Error(f"iclr17: {what} needs two [B,3,H,W] batches of one shape "
                           f"(got {tuple(x.shape)} and {tuple(y.shape)})")
-    B, _, H, W = x.shape
+    return x.shape[0], x.shape[2], x.shape[3]
+
+
+def ms_ssim(x: Tensor, y: Tensor, data_range: float = 1.0) -> Tensor:
+    """Per-image MS-SSIM [B] of NCHW fp32 image batches (models/ms_ssim_torch.py:123-196 as
+    train.py:178 calls it), on the GPU."""
+    B, H, W = _image_pair(x, y, "ms_ssim")
     nbytes = query("iclr17_ms_ssim_workspace_size", B, H, W)
     if nbytes == 0:
         raise Iclr17Error(f"iclr17: ms_ssim: {H}x{W} is too small for 5 levels of an 11-tap window")
@@ -779,12 +796,7 @@ def ms_ssim(x: Tensor, y: Tensor, data_range: float = 1.0) -> Tensor:
 def ssim(x: Tensor, y: Tensor, data_range: float = 1.0):
     """Per-image single-scale SSIM and cs means ([B], [B]) of NCHW fp32 batches
     (models/ms_ssim_torch.py:36-83 with size_average=False, full=True), on the GPU."""
-    _check(x, "image", 4)
-    _check(y, "image", 4)
-    if x.shape != y.shape or x.shape[1] != 3:
-        raise Iclr17Error(f"iclr17: ssim needs two [B,3,H,W] batches of one shape "
-                          f"(got {tuple(x.shape)} and {tuple(y.shape)})")
-    B, _, H, W = x.shape
+    B, H, W = _image_pair(x, y, "ssim")
     nbytes = query("iclr17_ssim_workspace_size", B, H, W)
     if nbytes == 0:
         raise Iclr17Error(f"iclr17: ssim: {H}x{W} is smaller than the 11-tap window")
@@ -874,20 +886,8 @@ def deconv3(h: Tensor, wp: Tensor, bias: Tensor, x_ref: Optional[Tensor] = None,
     """synthesis_17.py:23-25 + model.py:59: NHWC [B,H/4,W/4,N] → clipped NCHW [B,3,H,W].
 
     Returns (clipped, recon_unclipped | None, sse_partial [B,T] | None)."""
-    _check(h, "activation", 4)
-    B, h4, w4, N = h.shape
-    _check_channels(N)
-    H, W = 4 * h4, 4 * w4
-    _check_image_dims(H, W)
-    clipped = torch.empty(B, 3, H, W, device=h.device, dtype=torch.float32)
-    recon = torch.empty_like(clipped) if want_recon else None
-    partial = None
-    if x_ref is not None:
-        _check(x_ref, "reference image", 4)
-        if tuple(x_ref.shape) != (B, 3, H, W):
-            raise Iclr17Error("iclr17: reference image shape mismatch")
-        x_ref = x_ref.contiguous()
-        partial = torch.empty(B, output_partials_per_image(H, W), device=h.device, dtype=torch.float64)
+    B, h4, w4, N, H, W = _act_dims(_check_act(h), 4)
+    clipped, recon, x_ref, partial = _recon_outputs(B, H, W, h.device, x_ref, want_recon)
     call("iclr17_synthesis_deconv3", _p(h.contiguous()), B, H, W, N, _p(wp), _p(bias), _p(x_ref),
          _p(clipped), _p(recon), _p(partial), int(sse_unclipped), _stream(h))
     return clipped, recon, partial
@@ -946,18 +946,22 @@ def deconv3_h3(hs: Tensor, w_h3: Tensor, bias: Tensor, x_ref: Optional[Tensor] =
     if (not isinstance(w_h3, Tensor) or w_h3.dtype != torch.int16
             or w_h3.numel() != query("iclr17_split_packed_h3_size", 9, N, 48)):
         raise Iclr17Error("iclr17: deconv3_h3 takes split_packed_h3 of the deconv3 packing")
-    _check_channels(N)
-    H, W = 4 * h4, 4 * w4
-    _check_image_dims(H, W)
-    clipped = torch.empty(B, 3, H, W, device=hs.device, dtype=torch.float32)
-    recon = torch.empty_like(clipped) if want_recon else None
-    partial = None
-    if x_ref is not None:
-        _check(x_ref, "reference image", 4)
-        if tuple(x_ref.shape) != (B, 3, H, W):
-            raise Iclr17Error("iclr17: reference image shape mismatch")
-        x_ref = x_ref.contiguous()
-        partial = torch.empty(B, output_partials_per_image(H, W), device=hs.device, dtype=torch.float64)
+    return _deconv3_halo("iclr17_synthesis_deconv3_h3", hs, B, h4, w4, N, w_h3, bias, x_ref,
+                         want_recon, sse_unclipped, bits, bits_per_image, h3_range_flag(hs.device))
+
+
+def _deconv3_halo(fn, hs, B, h4, w4, N, wp, bias, x_ref, want_recon, sse_unclipped, bits=None,
+                  bits_per_image=False, flag=None):
+    """The halo-tiled deconv3 kernels. Without ``flag`` (x6, bf16) the entry ``fn`` has a
+    ``_bits`` twin that also reduces the bit partials; the h3 entry is one function that always
+    takes the bit arguments and, last, the chain's range flag."""
+    B, h4, w4, N, H, W = _act_dims((B, h4, w4, N), 4)
+    clipped, recon, x_ref, partial = _recon_outputs(B, H, W, hs.device, x_ref, want_recon)
+    head = (_p(hs), B, H, W, N, _p(wp), _p(bias), _p(x_ref), _p(clipped), _p(recon), _p(partial),
+            int(sse_unclipped))
+    if bits is None and flag is None:
+        call(fn, *head, _stream(hs))
+        return clipped, recon, partial
     bp, scale, total, per = None, 0.0, None, None
     if bits is not None:
         bp, scale = bits
@@ -968,41 +972,14 @@ def deconv3_h3(hs: Tensor, w_h3: Tensor, bias: Tensor, x_ref: Optional[Tensor] =
         total = torch.empty((), device=hs.device, dtype=torch.float32)
         if bits_per_image:
             per = torch.empty(B, device=hs.device, dtype=torch.float64)
-    call("iclr17_synthesis_deconv3_h3", _p(hs), B, H, W, N, _p(w_h3), _p(bias), _p(x_ref),
-         _p(clipped), _p(recon), _p(partial), int(sse_unclipped), _p(bp),
-         bp.shape[1] if bp is not None else 0, _p(per), _p(total), ctypes.c_double(scale),
-         _p(h3_range_flag(hs.device)), _stream(hs))
+    tail = (_p(bp), bp.shape[1] if bp is not None else 0, _p(per), _p(total), ctypes.c_double(scale))
+    if flag is None:
+        call(fn + "_bits", *head, *tail, _stream(hs))
+    else:
+        call(fn, *head, *tail, _p(flag), _stream(hs))
     if bits is None:
         return clipped, recon, partial
     return (clipped, recon, partial, total, per) if bits_per_image else (clipped, recon, partial, total)
-
-
-def _deconv3_halo(fn, hs, B, h4, w4, N, wp, bias, x_ref, want_recon, sse_unclipped, bits=None):
-    _check_channels(N)
-    H, W = 4 * h4, 4 * w4
-    _check_image_dims(H, W)
-    clipped = torch.empty(B, 3, H, W, device=hs.device, dtype=torch.float32)
-    recon = torch.empty_like(clipped) if want_recon else None
-    partial = None
-    if x_ref is not None:
-        _check(x_ref, "reference image", 4)
-        if tuple(x_ref.shape) != (B, 3, H, W):
-            raise Iclr17Error("iclr17: reference image shape mismatch")
-        x_ref = x_ref.contiguous()
-        partial = torch.empty(B, output_partials_per_image(H, W), device=hs.device, dtype=torch.float64)
-    if bits is None:
-        call(fn, _p(hs), B, H, W, N, _p(wp), _p(bias), _p(x_ref), _p(clipped), _p(recon),
-             _p(partial), int(sse_unclipped), _stream(hs))
-        return clipped, recon, partial
-    bp, scale = bits
-    _check_f64(bp)
-    if bp.shape[0] != B:
-        raise Iclr17Error("iclr17: bit partials are not [B, T]")
-    total = torch.empty((), device=hs.device, dtype=torch.float32)
-    call(fn + "_bits", _p(hs), B, H, W, N, _p(wp), _p(bias), _p(x_ref), _p(clipped), _p(recon),
-         _p(partial), int(sse_unclipped), _p(bp.contiguous()), bp.shape[1], None, _p(total),
-         ctypes.c_double(scale), _stream(hs))
-    return clipped, recon, partial, total
 
 
 # ------------------------------------------------------------ bf16 throughput precision mode
@@ -1015,6 +992,7 @@ def _check_bf16(t: Tensor, what: str):
         raise Iclr17Error(f"iclr17: {what} must be a device tensor (there is no CPU path)")
     if not t.is_contiguous():
         raise Iclr17Error(f"iclr17: {what} must be contiguous")
+    return t.shape
 
 
 def to_bf16(x: Tensor) -> Tensor:
@@ -1058,12 +1036,7 @@ def conv1_gdn_bf16(x: Tensor, w_bf: Tensor, bias: Tensor, beta_eff: Tensor, g_bf
                    N: int) -> Tensor:
     """analysis_17.py:14-17 in bf16: x NCHW fp32 → bf16 NHWC [B,H/4,W/4,N]. w_bf: round_packed
     of the ICLR17_W_CONV1_X6 packing (1, 256, N); g_bf: round_packed of γ's gp (1, N, N)."""
-    _check(x, "image", 4)
-    B, C, H, W = x.shape
-    if C != 3:
-        raise Iclr17Error(f"iclr17: the analysis transform takes 3-channel images (got {C})")
-    _check_image_dims(H, W)
-    _check_channels(N)
+    B, H, W = _image_dims(x, N)
     out = torch.empty(B, H // 4, W // 4, N, device=x.device, dtype=torch.int16)
     call("iclr17_analysis_conv1_gdn_bf16", _p(x.contiguous()), B, H, W, N, _p(w_bf), _p(bias),
          _p(beta_eff), _p(g_bf), _p(out), _stream(x))
@@ -1072,11 +1045,7 @@ def conv1_gdn_bf16(x: Tensor, w_bf: Tensor, bias: Tensor, beta_eff: Tensor, g_bf
 
 def conv2_gdn_bf16(h: Tensor, w_bf: Tensor, bias: Tensor, beta_eff: Tensor, g_bf: Tensor) -> Tensor:
     """analysis_17.py:18-21 in bf16: bf16 NHWC [B,H/4,W/4,N] → [B,H/8,W/8,N]."""
-    _check_bf16(h, "activation")
-    B, h4, w4, N = h.shape
-    _check_channels(N)
-    H, W = 4 * h4, 4 * w4
-    _check_image_dims(H, W)
+    B, h4, w4, N, H, W = _act_dims(_check_bf16(h, "activation"), 4)
     out = torch.empty(B, h4 // 2, w4 // 2, N, device=h.device, dtype=torch.int16)
     call("iclr17_analysis_conv2_gdn_bf16", _p(h), B, H, W, N, _p(w_bf), _p(bias), _p(beta_eff),
          _p(g_bf), _p(out), _stream(h))
@@ -1098,11 +1067,7 @@ def conv3_quant_rate_bf16(h: Tensor, w_bf: Tensor, rate_packed: Tensor, rtab: Op
     """analysis_17.py:22 + model.py:56,71-73 (round mode) in bf16 → (ŷ fp32 NHWC, bits partials
     [B,T] float64, y fp32 | None, ŷ bf16 NHWC). rtab: ``rate_table`` of rate_packed (made here
     when not given)."""
-    _check_bf16(h, "activation")
-    B, h8, w8, N = h.shape
-    _check_channels(N)
-    H, W = 8 * h8, 8 * w8
-    _check_image_dims(H, W)
+    B, h8, w8, N, H, W = _act_dims(_check_bf16(h, "activation"), 8)
     y_hat = torch.empty(B, h8 // 2, w8 // 2, N, device=h.device, dtype=torch.float32)
     y_hat_bf = torch.empty(B, h8 // 2, w8 // 2, N, device=h.device, dtype=torch.int16)
     y = torch.empty_like(y_hat) if want_y else None
@@ -1233,18 +1198,21 @@ def gdn(x: Tensor, beta_eff: Tensor, gp: Tensor, inverse: bool) -> Tensor:
     _check(x, "input", 4)
     B, C, H, W = x.shape
     _check_channels(C)
-    if x.is_contiguous():
-        layout, src = _lib.ICLR17_LAYOUT_NCHW, x
-        y = torch.empty_like(x)
-    elif x.is_contiguous(memory_format=torch.channels_last):
-        layout, src = _lib.ICLR17_LAYOUT_NHWC, x
-        y = torch.empty_like(x, memory_format=torch.channels_last)
-    else:
-        layout, src = _lib.ICLR17_LAYOUT_NCHW, x.contiguous()
-        y = torch.empty_like(src)
+    layout, src = _layout_of(x)
+    y = torch.empty_like(src)   # keeps src's memory format
     call("iclr17_gdn", _p(src), B, C, H, W, layout, int(bool(inverse)), _p(beta_eff), _p(gp),
          _p(y), _stream(x))
     return y
+
+
+def _layout_of(x: Tensor):
+    """(ICLR17_LAYOUT_*, the 4-D tensor as the kernels read it): NCHW-contiguous or channels-last
+    as it is, anything else copied to NCHW."""
+    if x.is_contiguous():
+        return _lib.ICLR17_LAYOUT_NCHW, x
+    if x.is_contiguous(memory_format=torch.channels_last):
+        return _lib.ICLR17_LAYOUT_NHWC, x
+    return _lib.ICLR17_LAYOUT_NCHW, x.contiguous()
 
 
 def _layout_inner(x: Tensor) -> Tuple[Tensor, int]:
@@ -1289,12 +1257,7 @@ def gdn_backward(x: Tensor, g: Tensor, beta_eff: Tensor, gp: Tensor, gpt: Tensor
     _check(x, "input", 4)
     B, C, H, W = x.shape
     _check_channels(C)
-    if x.is_contiguous():
-        layout, src = _lib.ICLR17_LAYOUT_NCHW, x
-    elif x.is_contiguous(memory_format=torch.channels_last):
-        layout, src = _lib.ICLR17_LAYOUT_NHWC, x
-    else:
-        layout, src = _lib.ICLR17_LAYOUT_NCHW, x.contiguous()
+    layout, src = _layout_of(x)
     mf = torch.channels_last if layout == _lib.ICLR17_LAYOUT_NHWC else torch.contiguous_format
     gs = g.contiguous(memory_format=mf)
     dx = torch.empty_like(src, memory_format=mf)
@@ -1350,12 +1313,7 @@ def rate_bits(z: Tensor, rate_packed: Tensor) -> Tensor:
     """model.py:71-73 on a 4-D latent: per-image Σ bits partials [B, T] (float64)."""
     _check(z, "latent", 4)
     B, C, h, w = z.shape
-    if z.is_contiguous():
-        layout, src = _lib.ICLR17_LAYOUT_NCHW, z
-    elif z.is_contiguous(memory_format=torch.channels_last):
-        layout, src = _lib.ICLR17_LAYOUT_NHWC, z
-    else:
-        layout, src = _lib.ICLR17_LAYOUT_NCHW, z.contiguous()
+    layout, src = _layout_of(z)
     T = query("iclr17_rate_bits_partials", C, h, w)
     partial = torch.empty(B, T, device=z.device, dtype=torch.float64)
     call("iclr17_rate_bits", _p(src), B, C, h, w, layout, _p(rate_packed), _p(partial), _stream(z))
@@ -1564,11 +1522,13 @@ def gdn_wgrad(dn: Tensor, u: Tensor, x6: Optional[bool] = None) -> Tensor:
 
 
 def gdn_param_grads(dn: Tensor, u: Tensor, dbe: Tensor, beta: Tensor, gamma: Tensor,
-                    beta_bound: float = DEFAULT_BETA_BOUND, gamma_bound: float = DEFAULT_GAMMA_BOUND):
+                    beta_bound: float = DEFAULT_BETA_BOUND, gamma_bound: float = DEFAULT_GAMMA_BOUND,
+                    x6: Optional[bool] = None):
     """GDN parameter gradients (dβ, dγ) in the raw-parameter space (through GDN.py:73-79);
-    dbe = ∂β_eff (Σ dn, from the backward kernel's column sums)."""
+    dbe = ∂β_eff (Σ dn, from the backward kernel's column sums). x6 as ``gdn_wgrad``: a backward
+    passes what its forward's mode asks for."""
     C = dn.shape[-1]
-    dge = gdn_wgrad(dn, u)
+    dge = gdn_wgrad(dn, u, x6)
     db = torch.empty_like(dbe)
     dg = torch.empty_like(dge)
     call("iclr17_gdn_param_chain", _p(beta.detach().contiguous()), _p(gamma.detach().contiguous()),

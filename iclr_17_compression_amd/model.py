@@ -22,7 +22,7 @@ import numpy as np  # noqa: F401  (re-exported, train.py:117)
 import torch
 import torch.nn as nn
 
-from . import kernels
+from . import chain, kernels
 from .models import *  # noqa: F401,F403
 from .models import Analysis_net_17, BitEstimator, Synthesis_net_17
 
@@ -60,113 +60,72 @@ class ImageCompressor(nn.Module):
 
     def run(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None, training: Optional[bool] = None,
             x_ref_sse: bool = False, want_recon: bool = False,
-            want_y: bool = False) -> Dict[str, torch.Tensor]:
+            want_y: bool = False, mode: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """The fused forward. Returns a dict with ``clipped`` (NCHW), ``y_hat`` (NHWC), bits
-        partials and, on request, per-image SSE partials (vs x) and the unclipped recon."""
+        partials and, on request, per-image SSE partials (vs x) and the unclipped recon; in a mode
+        whose deconv3 sums the bits per image (h3) also ``bits_per_image``. ``mode``: the
+        precision mode (default: kernels.precision(), read once here)."""
         training = self.training if training is None else training
         x = x.contiguous()
-        q = self.encode_latents(x, noise, training, want_y)
-        y_hat, bits_partial, y_split = q["y_hat"], q["bits_partial"], q["y_split"]
-        out = {"y_hat": y_hat, "bits_partial": bits_partial, "y": q["y"]}
-        if q.get("y_h3") is not None:
-            # h3: the per-image bit sums folded into deconv3's kernel, which writes them (and every
-            # other result) as NaN when a value of the chain did not fit the h3 form
-            B, _, H, W = x.shape
-            clipped, recon, sse_partial, _, out["bits_per_image"] = self.Decoder.decode(
-                y_hat, x_ref=x if x_ref_sse else None, want_recon=want_recon,
-                y_integral=not training, y_h3=q["y_h3"], bits=(bits_partial, 1.0 / (B * H * W)),
-                bits_per_image=True)
-        else:
-            clipped, recon, sse_partial = self.Decoder.decode(y_hat, x_ref=x if x_ref_sse else None,
-                                                              want_recon=want_recon, y_split=y_split,
-                                                              y_bf16=q.get("y_bf16"),
-                                                              y_integral=not training)
-        out.update({"clipped": clipped, "sse_partial": sse_partial, "recon": recon})
+        q = self.encode_latents(x, noise, training, want_y, mode or kernels.precision())
+        B, _, H, W = x.shape
+        # h3: the per-image bit sums folded into deconv3's kernel, which writes them (and every
+        # other result) as NaN when a value of the chain did not fit the h3 form
+        res = self.Decoder.decode(q["y_hat"], x_ref=x if x_ref_sse else None, want_recon=want_recon,
+                                  y_split=q["y_split"], y_bf16=q["y_bf16"], y_h3=q["y_h3"],
+                                  y_integral=not training,
+                                  bits=(q["bits_partial"], 1.0 / (B * H * W)), bits_per_image=True)
+        out = {"y_hat": q["y_hat"], "bits_partial": q["bits_partial"], "y": q["y"],
+               "clipped": res[0], "recon": res[1], "sse_partial": res[2]}
+        if len(res) == 5:
+            out["bits_per_image"] = res[4]
         return out
 
     def encode_latents(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None,
-                       training: bool = False, want_y: bool = False) -> Dict[str, torch.Tensor]:
-        """The analysis half of ``run``: conv1+GDN → conv2+GDN → conv3+quantise+rate. Returns
-        ``y_hat`` (NHWC), the bits partials, ``y_split`` (x6 split form, or None), ``y_h3`` (the
-        h3 form in the h3 mode, or None) and ``y``."""
+                       training: bool = False, want_y: bool = False,
+                       mode: Optional[str] = None) -> Dict[str, torch.Tensor]:
+        """The analysis half of ``run``: conv1+GDN → conv2+GDN → conv3+quantise+rate in ``mode``
+        (default: kernels.precision()). Returns ``y_hat`` (NHWC), the bits partials, ``y`` and the
+        latent in the form the mode's synthesis reads: ``y_split`` (x6), ``y_h3`` (h3) or
+        ``y_bf16`` (bf16), the others None."""
         kernels._check(x, "image", 4)
         if training and noise is None:
             noise = self._latent_noise(x)
         if not training:
             noise = None
-        x = x.contiguous()
-        w1, w2, w3, g1, g2 = self.Encoder.packed()
-        N = self.out_channel_N
-        if kernels.precision() == "bf16" and noise is None:
-            # the throughput mode: bf16 activations and weights, one bf16 product per MAC
-            w1b, w2b, w3b = self.Encoder.packed_bf16()
-            e1 = self.Encoder.gdn1.effective_params_bf16()
-            e2 = self.Encoder.gdn2.effective_params_bf16()
-            h = kernels.conv1_gdn_bf16(x, w1b, self.Encoder.conv1.bias, *e1, N)
-            h = kernels.conv2_gdn_bf16(h, w2b, self.Encoder.conv2.bias, *e2)
-            y_hat, bits, y, ybf = kernels.conv3_quant_rate_bf16(h, w3b, self.bitEstimator.packed(),
-                                                                self.bitEstimator.rate_table(),
-                                                                want_y=want_y)
-            return {"y_hat": y_hat, "bits_partial": bits, "y_split": None, "y_bf16": ybf, "y": y}
-        if kernels.precision() == "h3":
-            # the parity mode on the f16 MFMA: conv1, conv2 and conv3 (and the GDN contractions)
-            # in the h3 form (three fp16 part products per MAC), ŷ handed on in the h3 form
-            kernels.h3_chain_begin(x.device)
-            e1 = self.Encoder.gdn1.effective_params_h3()
-            e2 = self.Encoder.gdn2.effective_params_h3()
-            w2h, w3h = self.Encoder.packed_h3()
-            hs, _ = kernels.conv1_gdn_h3(x, self.Encoder.packed_conv1_h3(), self.Encoder.conv1.bias,
-                                         *e1, N)
-            hs, _, _ = kernels.conv2_gdn_h3(hs, w2h, self.Encoder.conv2.bias, *e2)
-            rt = self.bitEstimator.rate_table() if noise is None else None
-            q = kernels.conv3_quant_rate_h3(hs, w3h, self.bitEstimator.packed(), noise, want_y=want_y,
-                                            rtab=rt)
-            return {"y_hat": q[0], "bits_partial": q[1], "y_split": None, "y_h3": q[3],
-                    "y": q[2] if want_y else None}
-        if kernels.precision() != "fp32":
-            e1 = self.Encoder.gdn1.effective_params_x6()
-            e2 = self.Encoder.gdn2.effective_params_x6()
-            hs, _, _ = kernels.conv1x6_gdn(x, self.Encoder.packed_conv1_x6(), self.Encoder.conv1.bias,
-                                           e1[0], e1[2], N)
-            hs, _, _ = kernels.conv2_gdn_x6(hs, w2, self.Encoder.conv2.bias, *e2)
-            rt = self.bitEstimator.rate_table() if noise is None else None
-            q = kernels.conv3_quant_rate_x6(hs, w3, self.bitEstimator.packed(), noise, want_y=want_y,
-                                            rtab=rt, w_split=self.Encoder.packed_w3_split())
-            y_split = q[3]
-        else:
-            h = kernels.conv1_gdn(x, w1, self.Encoder.conv1.bias, g1[0], g1[1], N)
-            h = kernels.conv2_gdn(h, w2, self.Encoder.conv2.bias, g2[0], g2[1])
-            rt = self.bitEstimator.rate_table() if noise is None else None
-            q = kernels.conv3_quant_rate(h, w3, self.bitEstimator.packed(), noise, want_y=want_y,
-                                         rtab=rt)
-            y_split = None
-        return {"y_hat": q[0], "bits_partial": q[1], "y_split": y_split,
-                "y": q[2] if want_y else None}
+        rtab = self.bitEstimator.rate_table() if noise is None else None
+        r = chain.MODES[mode or kernels.precision()].analysis(
+            self.Encoder, x.contiguous(), self.bitEstimator.packed(), rtab, noise, want_y)
+        out = {"y_hat": r["y_hat"], "bits_partial": r["bits_partial"], "y": r["y"],
+               "y_split": None, "y_h3": None, "y_bf16": None}
+        if r["latent"] is not None:
+            out[r["operand"]] = r["latent"]
+        return out
 
     def forward(self, input_image, noise: Optional[torch.Tensor] = None):
         """model.py:47-80 → (clipped_recon, ŷ or ỹ, bpp). In training mode with autograd on, the
         fused training kernels run and every output is differentiable."""
-        from .autograd import CodecTrainFn, needs_grad, no_backward
+        from .autograd import needs_grad, no_backward
         params = list(self.parameters())
+        mode = kernels.precision()
         if self.training and needs_grad(input_image, params):
-            clipped, y_tilde, bpp, _ = self._train_outputs(input_image, noise, params)
+            clipped, y_tilde, bpp, _ = self._train_outputs(input_image, noise, params, mode)
             return clipped, y_tilde, bpp
         B, _, H, W = input_image.shape
         if not self.training and needs_grad(input_image, params):
-            return self._eval_autograd(input_image)
+            return self._eval_autograd(input_image, mode)
         # run() with bpp's reduction (model.py:71-78) folded into deconv3's kernel
-        q = self.encode_latents(input_image.contiguous(), noise, self.training)
+        q = self.encode_latents(input_image.contiguous(), noise, self.training, mode=mode)
         clipped, _, _, bpp = self.Decoder.decode(q["y_hat"], want_recon=False, y_split=q["y_split"],
-                                                 y_bf16=q.get("y_bf16"), y_integral=not self.training,
+                                                 y_bf16=q["y_bf16"], y_integral=not self.training,
                                                  bits=(q["bits_partial"], 1.0 / (B * H * W)),
-                                                 y_h3=q.get("y_h3"))
-        out = {"clipped": clipped, "y_hat": q["y_hat"]}
-        y_hat = out["y_hat"].permute(0, 3, 1, 2).contiguous()   # NCHW like model.py:56
-        clipped = no_backward(out["clipped"], "ImageCompressor (training mode, no grad)", params,
+                                                 y_h3=q["y_h3"])
+        y_hat = q["y_hat"].permute(0, 3, 1, 2).contiguous()   # NCHW like model.py:56
+        clipped = no_backward(clipped, "ImageCompressor (training mode, no grad)", params,
                               input_image)
         return clipped, y_hat, bpp
 
-    def _eval_autograd(self, x):
+    def _eval_autograd(self, x, mode):
         """model.py:47-80 in eval mode with autograd on. torch.round (model.py:56) has a zero
         gradient, so nothing flows back into the encoder or the image; the reconstruction is
         differentiable in the synthesis parameters (the fused synthesis forward/backward,
@@ -175,7 +134,7 @@ class ImageCompressor(nn.Module):
         where torch would give zeros."""
         B, _, H, W = x.shape
         with torch.no_grad():
-            y_hat = self.encode_latents(x)["y_hat"].permute(0, 3, 1, 2).contiguous()
+            y_hat = self.encode_latents(x, mode=mode)["y_hat"].permute(0, 3, 1, 2).contiguous()
         recon = self.Decoder(y_hat)
         clipped = recon.clamp(0., 1.)                                        # model.py:59
         prob = self.bitEstimator(y_hat + 0.5) - self.bitEstimator(y_hat - 0.5)   # model.py:71-72
@@ -183,13 +142,13 @@ class ImageCompressor(nn.Module):
         bpp = total_bits / (B * H * W)                                       # model.py:76-78
         return clipped, y_hat, bpp
 
-    def _train_outputs(self, x, noise, params):
+    def _train_outputs(self, x, noise, params, mode):
         from .autograd import CodecTrainFn
         kernels._check(x, "image", 4)
         if noise is None:
             noise = self._latent_noise(x)
-        self._warm_packs(backward=True)   # one batched pack per parameter update
-        return CodecTrainFn.apply(x.contiguous(), noise.contiguous(), self, *params)
+        self._warm_packs(backward=True, mode=mode)   # one batched pack per parameter update
+        return CodecTrainFn.apply(x.contiguous(), noise.contiguous(), self, mode, *params)
 
     def forward_train(self, input_image, noise: Optional[torch.Tensor] = None,
                       distortion: str = "mse"):
@@ -203,7 +162,8 @@ class ImageCompressor(nn.Module):
         if distortion not in ("mse", "ms-ssim"):
             raise kernels.Iclr17Error(f"iclr17: distortion must be 'mse' or 'ms-ssim' "
                                       f"(got {distortion!r})")
-        clipped, _, bpp, mse = self._train_outputs(input_image, noise, list(self.parameters()))
+        clipped, _, bpp, mse = self._train_outputs(input_image, noise, list(self.parameters()),
+                                                   kernels.precision())
         if distortion == "ms-ssim":
             from .losses import ms_ssim_diff
             return clipped, 1 - ms_ssim_diff(clipped, input_image, data_range=1.0), bpp
@@ -217,16 +177,14 @@ class ImageCompressor(nn.Module):
         factorised BitEstimator (the model the reference uses only to estimate bpp). Per image:
         P little-endian uint32 stream word counts, then the stream words (uint16 LE).
         Returns {"strings": [bytes] * B, "shape": (h, w), "streams_per_image": P, "K": K}."""
-        y_hat = self.encode_latents(x)["y_hat"]
-        if kernels.precision() == "h3" and kernels.h3_range_overflowed(x.device):
+        mode = kernels.precision()
+        y_hat = self.encode_latents(x, mode=mode)["y_hat"]
+        if mode == "h3" and kernels.h3_range_overflowed(x.device):
             # an activation did not fit the h3 form (conv3 wrote ŷ as NaN): encode from the x6
             # chain's ŷ instead (full fp32 operands). The flag read is one synchronisation, and
             # the stream sizes below synchronise anyway.
-            kernels.set_precision("x6")
-            try:
+            with kernels.precision_scope("x6"):
                 y_hat = self.encode_latents(x)["y_hat"]
-            finally:
-                kernels.set_precision("h3")
         B, h, w, N = y_hat.shape
         P = streams_per_image
         words, offsets = kernels.rans_encode(y_hat, self.bitEstimator.entropy_tables(K), K, P)
@@ -262,13 +220,9 @@ class ImageCompressor(nn.Module):
         offsets = torch.from_numpy(off).to(device)
         y_hat = kernels.rans_decode(words, offsets, self.bitEstimator.entropy_tables(K), B, h, w, N,
                                     K, P)
-        split = kernels.split_planes(y_hat) if kernels.precision() == "x6" else None
-        if kernels.precision() == "h3":
-            kernels.h3_chain_begin(y_hat.device)
-        yh3 = kernels.h3_planes(y_hat, cm=kernels.DECONV_CM) if kernels.precision() == "h3" else None
-        ybf = kernels.to_bf16(y_hat) if kernels.precision() == "bf16" else None
-        clipped, _, _ = self.Decoder.decode(y_hat, want_recon=False, y_split=split, y_bf16=ybf,
-                                            y_integral=True, y_h3=yh3)
+        m = chain.MODES[kernels.precision()]
+        clipped, _, _ = m.synthesis(self.Decoder, y_hat, m.latent_operand(y_hat), None, False, True,
+                                    None, False)
         return {"y_hat": y_hat.permute(0, 3, 1, 2).contiguous(), "x_hat": clipped}
 
     @torch.no_grad()
@@ -286,21 +240,18 @@ class ImageCompressor(nn.Module):
         if h3_overflow not in ("nan", "raise", "x6"):
             raise kernels.Iclr17Error(f"iclr17: h3_overflow must be 'nan', 'raise' or 'x6' "
                                       f"(got {h3_overflow!r})")
-        res = self._evaluate(x, want_y, want_msssim)
-        if h3_overflow != "nan" and kernels.precision() == "h3" and \
-                kernels.h3_range_overflowed(x.device):
+        mode = kernels.precision()
+        res = self._evaluate(x, want_y, want_msssim, mode)
+        if h3_overflow != "nan" and mode == "h3" and kernels.h3_range_overflowed(x.device):
             if h3_overflow == "raise":
                 raise kernels.Iclr17Error(kernels.H3_RANGE_MESSAGE)
-            kernels.set_precision("x6")
-            try:
-                res = self._evaluate(x, want_y, want_msssim)
-            finally:
-                kernels.set_precision("h3")
+            with kernels.precision_scope("x6"):
+                res = self._evaluate(x, want_y, want_msssim, kernels.precision())
         return res
 
-    def _evaluate(self, x, want_y, want_msssim):
+    def _evaluate(self, x, want_y, want_msssim, mode):
         B, _, H, W = x.shape
-        out = self.run(x, training=False, x_ref_sse=True, want_y=want_y)
+        out = self.run(x, training=False, x_ref_sse=True, want_y=want_y, mode=mode)
         bits = out.get("bits_per_image")
         if bits is None:
             bits, _ = kernels.reduce_partials(out["bits_partial"])
@@ -318,54 +269,19 @@ class ImageCompressor(nn.Module):
             res["ms_ssim_db"] = -10 * (torch.log(1 - ms) / math.log(10))
         return res
 
-    def _warm_packs(self, backward: bool = False) -> None:
-        """Build (or refresh) every derived parameter layout ``run`` reads (with ``backward``
-        also those of the training backward) on the current stream, the stale ones as one
-        batched packing launch pair (kernels.batched_packs)."""
-        x6 = kernels.precision() != "fp32"
-        gdns = (self.Encoder.gdn1, self.Encoder.gdn2, self.Decoder.igdn1, self.Decoder.igdn2)
-        h3 = kernels.precision() == "h3"
+    def _warm_packs(self, backward: bool = False, mode: Optional[str] = None) -> None:
+        """Build (or refresh) every derived parameter layout ``run`` reads in ``mode`` (default:
+        kernels.precision(); with ``backward`` also those of the training backward) on the current
+        stream, the stale ones as one batched packing launch pair (kernels.batched_packs)."""
+        m = chain.MODES[mode or kernels.precision()]
         with kernels.batched_packs():
-            if h3 and backward:   # an h3 training step reads only these fp32 packings
-                self.Encoder.packed_w3()
-                self.Decoder.packed_d3()
-                for g in gdns:
-                    g.effective_params()
-            else:
-                self.Encoder.packed()
-                self.Decoder.packed()
-            self.bitEstimator.packed()
-            if x6:
-                if not (h3 and backward):   # the x6 forward's (an h3 training step has none)
-                    self.Encoder.packed_conv1_x6()
-                    self.Encoder.packed_w3_split()
-                    self.Decoder.packed_x6()
-                    for g in gdns:
-                        g.effective_params_x6()
-            if backward:
-                self.Encoder.packed_bwd()
-                self.Decoder.packed_bwd(x6)
-                for g in gdns:
-                    if x6:
-                        g.effective_params_bwd_x6()
-                    else:
-                        g.effective_params_bwd()
-        if h3:
-            # the h3 layouts (the codec's, and the training forward's in this mode) split the
-            # packs above, which the batch writes only at its exit; they form a batch of their own
-            with kernels.batched_h3_packs():
-                self.Decoder.packed_h3k()
-                self.Encoder.packed_h3()
-                self.Encoder.packed_conv1_h3()
-                for g in gdns:
-                    g.effective_params_h3()
+            m.warm(self, backward)
+        # the h3 layouts (the codec's, and the training forward's in this mode) split the packs
+        # above, which the batch writes only at its exit; they form a batch of their own
+        with kernels.batched_h3_packs():
+            m.warm_h3(self)
         if not backward:   # eval: the rate table of the round quantiser (+ the bf16 layouts)
-            self.bitEstimator.rate_table()
-            if kernels.precision() == "bf16":
-                self.Encoder.packed_bf16()
-                self.Decoder.packed_bf16()
-                for g in gdns:
-                    g.effective_params_bf16()
+            m.warm_eval(self)
 
     def evaluate_many(self, batches, want_y: bool = False,
                       want_msssim: bool = False):

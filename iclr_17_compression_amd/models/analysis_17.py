@@ -12,7 +12,7 @@ import math
 import torch
 import torch.nn as nn
 
-from .. import _lib, kernels
+from .. import _lib, chain, kernels
 from ..packcache import PackCache
 from .GDN import GDN
 
@@ -125,52 +125,22 @@ class Analysis_net_17(nn.Module):
         from ..autograd import AnalysisFn, needs_grad
         kernels._check(x, "image", 4)
         params = list(self.parameters())
+        mode = kernels.precision()
         if needs_grad(x, params):
-            return AnalysisFn.apply(x.contiguous(), self, *params)
-        return self.y_nhwc(x.contiguous()).permute(0, 3, 1, 2).contiguous()
+            return AnalysisFn.apply(x.contiguous(), self, mode, *params)
+        return self.y_nhwc(x.contiguous(), mode).permute(0, 3, 1, 2).contiguous()
 
-    def y_nhwc(self, x, feats=None):
-        """y (NHWC) through the codec's analysis kernels. ``feats``: the training forward's
-        conv2+GDN2 output (autograd.analysis_features_train), reused for conv3 where it is the
-        codec's own operand (x6: its split form; fp32: the fp32 activation; h3: its h3 form — the
-        training forward runs the codec's h3 kernels). In the bf16 mode the codec's own chain runs
-        again (its y is what the codec rounds) while the gradient is the training kernels' x6
-        one, a different function at bf16 precision (≈0.3 % of the rounded latents, §3 of
-        DESIGN.md)."""
+    def y_nhwc(self, x, mode, feats=None):
+        """y (NHWC) through the analysis kernels of the codec's chain in ``mode`` (chain.MODES).
+        ``feats``: the training forward's features of x (autograd.analysis_features_train in the
+        same mode), whose conv2+GDN2 output is reused for conv3 where it is the codec's own
+        operand (x6: its split form; fp32: the fp32 activation; h3: its h3 form — the training
+        forward runs the codec's h3 kernels). In the bf16 mode the codec's own chain runs again
+        (its y is what the codec rounds) while the gradient is the training kernels' x6 one, a
+        different function at bf16 precision (≈0.3 % of the rounded latents, §3 of DESIGN.md)."""
         N = self.out_channel_N
-        w1, w2, w3, g1, g2 = self.packed()
         # the rate epilogue needs a model: a zero one (its bits are discarded, y is all we keep)
         z = torch.zeros(11 * N, device=x.device)
         ztab = torch.zeros(N, 65, device=x.device)
-        if feats is not None and kernels.precision() == "h3" and feats.get("a2h") is not None:
-            return kernels.conv3_quant_rate_h3(feats["a2h"], self.packed_h3()[1], z, want_y=True,
-                                               rtab=ztab, want_h3=False)[2]
-        if feats is not None and kernels.precision() == "x6" and feats.get("a2s") is not None:
-            return kernels.conv3_quant_rate_x6(feats["a2s"], w3, z, want_y=True, rtab=ztab,
-                                               w_split=self.packed_w3_split())[2]
-        if feats is not None and kernels.precision() == "fp32":
-            return kernels.conv3_quant_rate(feats["a2"], w3, z, want_y=True, rtab=ztab)[2]
-        if kernels.precision() == "bf16":
-            w1b, w2b, w3b = self.packed_bf16()
-            e1, e2 = self.gdn1.effective_params_bf16(), self.gdn2.effective_params_bf16()
-            h = kernels.conv1_gdn_bf16(x, w1b, self.conv1.bias, *e1, N)
-            h = kernels.conv2_gdn_bf16(h, w2b, self.conv2.bias, *e2)
-            y = kernels.conv3_quant_rate_bf16(h, w3b, z, ztab, want_y=True)[2]
-        elif kernels.precision() == "h3":
-            kernels.h3_chain_begin(x.device)
-            e1, e2 = self.gdn1.effective_params_h3(), self.gdn2.effective_params_h3()
-            w2h, w3h = self.packed_h3()
-            hs, _ = kernels.conv1_gdn_h3(x, self.packed_conv1_h3(), self.conv1.bias, *e1, N)
-            hs, _, _ = kernels.conv2_gdn_h3(hs, w2h, self.conv2.bias, *e2)
-            y = kernels.conv3_quant_rate_h3(hs, w3h, z, want_y=True, rtab=ztab, want_h3=False)[2]
-        elif kernels.precision() == "x6":
-            e1, e2 = self.gdn1.effective_params_x6(), self.gdn2.effective_params_x6()
-            hs, _, _ = kernels.conv1x6_gdn(x, self.packed_conv1_x6(), self.conv1.bias, e1[0], e1[2], N)
-            hs, _, _ = kernels.conv2_gdn_x6(hs, w2, self.conv2.bias, *e2)
-            y = kernels.conv3_quant_rate_x6(hs, w3, z, want_y=True, rtab=ztab,
-                                            w_split=self.packed_w3_split())[2]
-        else:
-            h = kernels.conv1_gdn(x, w1, self.conv1.bias, g1[0], g1[1], N)
-            h = kernels.conv2_gdn(h, w2, self.conv2.bias, g2[0], g2[1])
-            y = kernels.conv3_quant_rate(h, w3, z, want_y=True, rtab=ztab)[2]
-        return y
+        return chain.MODES[mode].analysis(self, x, z, ztab, None, True, feats=feats,
+                                          want_latent=False)["y"]

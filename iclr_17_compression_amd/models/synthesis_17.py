@@ -12,7 +12,7 @@ import math
 import torch
 import torch.nn as nn
 
-from .. import _lib, kernels
+from .. import _lib, chain, kernels
 from ..packcache import PackCache
 from .GDN import GDN
 
@@ -114,42 +114,21 @@ class Synthesis_net_17(nn.Module):
         """NHWC latent → (clipped NCHW, unclipped NCHW | None, SSE partials | None).
         With ``y_split`` (the latent in x6 split form) the three layers run in the x6 mode, with
         ``y_h3`` (the h3 form) the three layers run in the h3 form, with
-        ``y_bf16`` (bf16 bit patterns) in the bf16 throughput mode. ``y_integral``: the latent
+        ``y_bf16`` (bf16 bit patterns) in the bf16 throughput mode (chain.MODES[...].synthesis;
+        ``chain.MODES[mode].latent_operand(y_nhwc)`` makes the form). ``y_integral``: the latent
         is ŷ = round(y) (model.py:56), so the h3 deconv1 takes its integer-input form.
         ``bits`` = (conv3's bit partials, scale): a fourth output, ``reduce_partials``' 0-dim total,
         computed inside deconv3's kernel in the h3, x6 and bf16 modes (one launch fewer); h3 with
-        ``bits_per_image``: a fifth, the per-image sums. In the h3 mode every output is NaN when a
-        value of the chain (since the last kernels.h3_chain_begin) did not fit the h3 form."""
-        d1, d2, d3, g1, g2 = self.packed()
-        if y_bf16 is not None:
-            b1, b2, b3 = self.packed_bf16()
-            q1, q2 = self.igdn1.effective_params_bf16(), self.igdn2.effective_params_bf16()
-            h = kernels.deconv_igdn_bf16(y_bf16, b1, self.deconv1.bias, *q1)
-            h = kernels.deconv_igdn_bf16(h, b2, self.deconv2.bias, *q2)
-            return kernels.deconv3_bf16(h, b3, self.deconv3.bias, x_ref=x_ref, want_recon=want_recon,
-                                        bits=bits)
-        if y_h3 is not None:
-            q1, q2 = self.igdn1.effective_params_h3(), self.igdn2.effective_params_h3()
-            w1, w2, w3 = self.packed_h3k()
-            # on ŷ the integer-input form skips the lo products (the same bits: Decoder(round(y))
-            # reproduces the codec's reconstruction without knowing its input is ŷ)
-            hs, _, _ = kernels.deconv_igdn_h3(y_h3, w1, self.deconv1.bias, *q1, int_in=y_integral)
-            hs, _, _ = kernels.deconv_igdn_h3(hs, w2, self.deconv2.bias, *q2, chunk_major=True)
-            return kernels.deconv3_h3(hs, w3, self.deconv3.bias, x_ref=x_ref, want_recon=want_recon,
-                                      bits=bits, bits_per_image=bits_per_image)
-        if y_split is not None:
-            q1, q2 = self.igdn1.effective_params_x6(), self.igdn2.effective_params_x6()
-            hs, _, _ = kernels.deconv_igdn_x6(y_split, d1, self.deconv1.bias, *q1)
-            hs, _, _ = kernels.deconv_igdn_x6(hs, d2, self.deconv2.bias, *q2, chunk_major=True)
-            return kernels.deconv3_x6(hs, self.packed_x6(), self.deconv3.bias, x_ref=x_ref,
-                                      want_recon=want_recon, bits=bits)
-        else:
-            h = kernels.deconv_igdn(y_nhwc, d1, self.deconv1.bias, g1[0], g1[1])
-            h = kernels.deconv_igdn(h, d2, self.deconv2.bias, g2[0], g2[1])
-        out = kernels.deconv3(h, d3, self.deconv3.bias, x_ref=x_ref, want_recon=want_recon)
-        if bits is None:
-            return out
-        return (*out, kernels.reduce_partials(bits[0], bits[1], per_image=False)[1])
+        ``bits_per_image``: a fifth, the per-image sums (the other modes then fold nothing and
+        return the three values). In the h3 mode every output is NaN when a value of the chain
+        (since the last kernels.h3_chain_begin) did not fit the h3 form. A ``y_h3`` the caller
+        made with kernels.h3_planes belongs to the chain begun by the last
+        kernels.h3_chain_begin on that stream: begin one first (``latent_operand`` does), or the
+        decode inherits the range flag of whatever ran before."""
+        mode, latent = (("bf16", y_bf16) if y_bf16 is not None else ("h3", y_h3) if y_h3 is not None
+                        else ("x6", y_split) if y_split is not None else ("fp32", y_nhwc))
+        return chain.MODES[mode].synthesis(self, y_nhwc, latent, x_ref, want_recon, y_integral,
+                                           bits, bits_per_image)
 
     def forward(self, x):
         from ..autograd import SynthesisFn, needs_grad
@@ -157,13 +136,10 @@ class Synthesis_net_17(nn.Module):
         if x.shape[1] != self.out_channel_N:
             raise kernels.Iclr17Error(f"iclr17: Synthesis_net_17 expects {self.out_channel_N} channels")
         params = list(self.parameters())
+        mode = kernels.precision()
         if needs_grad(x, params):
-            return SynthesisFn.apply(x, self, *params)
+            return SynthesisFn.apply(x, self, mode, *params)
         y = self.to_nhwc(x)
-        split = kernels.split_planes(y) if kernels.precision() == "x6" else None
-        if kernels.precision() == "h3":
-            kernels.h3_chain_begin(y.device)
-        yh3 = kernels.h3_planes(y, cm=kernels.DECONV_CM) if kernels.precision() == "h3" else None
-        ybf = kernels.to_bf16(y) if kernels.precision() == "bf16" else None
-        _, recon, _ = self.decode(y, want_recon=True, y_split=split, y_bf16=ybf, y_h3=yh3)
+        m = chain.MODES[mode]
+        _, recon, _ = m.synthesis(self, y, m.latent_operand(y), None, True, False, None, False)
         return recon
