@@ -6,8 +6,6 @@
 
 namespace iclr17 {
 
-void deconv_phase_taps(int K, int s, int p, int ry, int rx, int* kh_out, int* kw_out, int* count);
-
 namespace {
 
 hipStream_t S(void* s) { return (hipStream_t)s; }

@@ -19,9 +19,34 @@ typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 
 namespace iclr17 {
 
-// ----------------------------------------------------------------------------- errors
+// ----------------------------------------------------------------------------- errors (runtime.hip)
 void set_error(int code, const char* fmt, ...);
 int check_launch(const char* what);
+// Shape checks of the entry points: an image B×H×W (H, W multiples of 16) with N channels, or, for
+// the entries that take a layer's grid directly, B×h×w. Both set the error and return its code.
+int check_image(int B, int H, int W, int N);
+int check_grid(const char* what, int B, int h, int w, int N);
+
+// ConvTranspose2d(K, stride s, pad p): output o = s·q + r receives input q + d through kernel
+// tap k = r + p − s·d (0 ≤ k < K). f(dy, dx, kh, kw) for every tap of output phase (ry, rx), in the
+// order both the engine's tap table and the weight packing use; returns their number.
+template <class F>
+inline int for_each_deconv_tap(int K, int s, int p, int ry, int rx, F&& f) {
+  int n = 0;
+  for (int dy = 2; dy >= -2; --dy) {
+    const int kh = ry + p - s * dy;
+    if (kh < 0 || kh >= K) continue;
+    for (int dx = 2; dx >= -2; --dx) {
+      const int kw = rx + p - s * dx;
+      if (kw < 0 || kw >= K) continue;
+      f(dy, dx, kh, kw);
+      ++n;
+    }
+  }
+  return n;
+}
+// the kernel taps (kh, kw) of one phase as arrays, for the packing code (aux.hip)
+void deconv_phase_taps(int K, int s, int p, int ry, int rx, int* kh_out, int* kw_out, int* count);
 
 #define ICLR17_REQUIRE(cond, code, ...)          \
   do {                                           \

@@ -1,42 +1,19 @@
-// Implicit-GEMM convolution engine for the Ballé-2017 codec on gfx950 (fp32 parity mode).
-//
-// One engine covers every layer of the hot path:
-//   analysis  conv2/conv3 (k5 s2 p2)            — forward conv, 25 taps, base grid = output grid
-//   synthesis deconv1/deconv2 (k5 s2 p2 op1)    — stride-phase decomposition: 4 dense sub-convs
-//                                                 (3×3 / 3×2 / 2×3 / 2×2 taps), no zero insertion
-//   synthesis deconv3 (k9 s4 p4 op3, N→3)       — "all-phase" GEMM: the 16 output phases × 3
-//                                                 channels share one 3×3 input neighbourhood, so
-//                                                 they form a dense N = 48 GEMM (K = 9·N)
-//   analysis  conv1 (3→N, k9 s4)                — own A-loader (NCHW patch staged in LDS, K = 243)
-//
-// Tile: 64 output pixels (an 8×8 block of the base grid) × BN output channels per 256-thread
-// workgroup (4 waves). GEMM mapping: M = pixels, N = output channels, K = (tap, input channel).
-// MFMA: v_mfma_f32_16x16x4_f32 (exact f32). Both operands are staged in LDS by LDS-DMA
-// (global_load_lds): the A tile (input pixels × 32 channels of one tap; out-of-image taps DMA
-// from a zero line) and the B tile (packed weights [tap][Cin/4][Cout][4] of the same step),
-// double buffered, one barrier per k-step.
-//
-// "float4 k-trick": a lane loads 4 consecutive input channels of its pixel with one 16-byte
-// read and feeds them to 4 successive MFMAs; MFMA e of a 16-deep k-block therefore covers
-// channels {16kb + 4g + e : g = 0..3}. The weight packing [Cin/4][Cout][4] makes the matching B
-// fragment a 16-byte read as well.
-//
-// Epilogues are fused: bias + GDN/IGDN (a second channel-contraction GEMM over an LDS x² tile
-// and the packed γ, then x/√n or x·√n), conv3's quantiser + factorised rate (per-tile bit sums),
-// and deconv3's bias + clamp (+ per-tile SSE against the input image). Outputs leave through
-// LDS as coalesced 16-byte row stores.
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <type_traits>
-
-#include "common.h"
+// The 8×8-tile engine's instantiations and entry points (gfx950), in its two operand flavours:
+//   fp32  exact-f32 MFMA (v_mfma_f32_16x16x4_f32), the parity mode
+//   x6    activations and weights as three bf16 planes, six v_mfma_f32_16x16x32_bf16 per MAC
+// forward (conv2/conv3, deconv1/deconv2, the fp32 deconv3) and the fused backward epilogues
+// (engine.h: engine_body), plus the two conv1 kernels with their own A-loaders (conv1_gdn_kernel,
+// conv1_x6_kernel; forward, and as the adjoint of deconv3 in the backward pass) and the fp32 →
+// x6 plane splitters (iclr17_split_planes, iclr17_split_packed).
+// The stand-alone GDN / IGDN kernels (gdn_kernel, gdn_bwd_kernel) are here too, on purpose: compiled
+// in a unit of their own, gdn_kernel and the fp32 engine_kernel<N, N, N, 1, 4, EPI_IGDN> both came
+// out with 4 more VGPRs and another schedule (they share the gdn_core instantiations), so the
+// family stays with the engine instantiations (profiles/engine_split_isa.txt).
+// The halo deconv3 kernels of the x6, h3 and bf16 modes are in deconv3_halo.hip, the error state
+// and shape checks in runtime.hip.
+#include "engine.h"
 
 namespace iclr17 {
-
-constexpr int BM = 64;        // output pixels per tile
-
 
 // conv3 (+ quantiser) output columns per workgroup: 96 at N = 192, 64 at N = 128
 constexpr int conv3_bn(int N) { return N % 96 == 0 ? 96 : 64; }
@@ -45,1641 +22,6 @@ constexpr int conv3_bn(int N) { return N % 96 == 0 ? 96 : 64; }
 // partials per image follow (tiles × N/48): iclr17_conv3_x6_partials_per_image.
 inline bool conv3_narrow(int N, int tiles, int B, int qmode) {
   return N == 192 && qmode == ICLR17_QUANT_NOISE && (long)tiles * B < 256;
-}
-
-enum Epi : int {
-  EPI_GDN = 0, EPI_IGDN = 1, EPI_QUANT = 2, EPI_OUT3 = 3, EPI_PLAIN = 4,
-  EPI_GDN_BWD = 5, EPI_IGDN_BWD = 6, EPI_RATE_BWD = 7
-};
-
-struct TapTable {
-  int npx;            // phases along x
-  int nph;            // total phases
-  int begin[17];      // taps of phase p: [begin[p], begin[p+1])
-  int dydx[64];       // (dy + 128) | (dx + 128) << 8 — dword entries so the wave-uniform lookup
-                      // is a scalar kernarg load (a byte array becomes a VMEM load + vmcnt(0))
-};
-
-__host__ __device__ inline int pack_tap(int dy, int dx) { return (dy + 128) | ((dx + 128) << 8); }
-
-struct EngineArgs {
-  const float* in;      // NHWC [B][Hin][Win][CI]   (conv1: NCHW image)
-  const float* w;       // packed weights
-  const float* bias;    // [CO] or nullptr
-  const float* gbeta;   // GDN effective beta [CO]
-  const float* ggamma;  // GDN effective gamma, packed [CO/4][CO][4]
-  float* out;           // NHWC [B][Hout][Wout][CO]   (deconv3: clipped NCHW image)
-  float* pre;           // optional pre-activation output (same layout as out)
-  int B, Hin, Win, Hout, Wout;
-  int gh, gw;           // base grid per phase
-  int tiles_x, tiles_y;
-  int sin, sout;        // input / output stride applied to base coordinates
-  TapTable tt;
-  // conv3 quantiser + rate
-  int qmode;
-  const float* noise;   // NCHW [B][CO][Hout][Wout]
-  const float* rate;    // packed [11][CO]
-  const float* rtab;    // round mode, nullable: element_bits of the integer latents −32..32 [CO][65]
-  float* yhat;          // NHWC
-  double* partial;      // per-tile partial sums
-  int partials_per_image;
-  // deconv3
-  const float* xref;    // NCHW input image (SSE) or nullptr
-  float* recon;         // unclipped NCHW or nullptr
-  int sse_unclipped;    // SSE of (recon − x) instead of (clipped − x) (training MSE, model.py:61)
-  // backward epilogues
-  const float* saved;   // GDN/IGDN bwd: the layer's saved pre-activation u (NHWC, output grid);
-                        // rate bwd: ỹ (NHWC)
-  const float* ggammaT; // γ packed transposed: packed[q][j][e] = γ[4q+e][j]
-  float* tout;          // GDN bwd: dn = ∂L/∂n (NHWC) for the parameter gradients
-  const float* gscale;  // rate bwd: device scalar ∂L/∂bpp (nullptr → no rate term)
-  float count;          // rate bwd: B·H·W (bpp denominator, model.py:78)
-  float* rpart;         // rate bwd: per-tile parameter partials [tiles][11][CO]
-  float* colsum_out;    // GDN bwd: per-tile column sums of ∂u (the conv bias gradient) [tiles][CO]
-  float* colsum_t;      // GDN bwd: per-tile column sums of dn (∂β_eff) [tiles][CO]
-  // x6 mode: activations as three bf16 planes (hi, mid, lo; x = hi + mid + lo exactly)
-  const unsigned short* in_split;   // [3][B][Hin][Win][CI]
-  long in_plane;                    // plane stride (elements)
-  unsigned short* out_split;        // [3][B][Hout][Wout][CO] or nullptr
-  long out_plane;
-  // chunk-major split form [3][B][C/32][h][w][32] (deconv2 → deconv3 x6: a 32-channel chunk of a
-  // patch row is contiguous, so the halo kernel's chunks do not share cache lines). out_cm: the
-  // writer (store_tile_rows_split), in_cm: the reader (deconv3_x6_kernel)
-  int out_cm, in_cm;
-  const unsigned short* ggamma6;    // x6: γ_eff split, [3][CO/8][CO][8] bf16 (plane CO·CO)
-  const unsigned short* ggammaT6;   // x6 backward: the transposed packing of γ_eff, split
-  // deconv3 (x6 / bf16): conv3's bit partials [B][fold_T] reduced by workgroup 0 before its tile
-  // (fold_bits: reduce_partials_kernel's arithmetic and order), or nullptr
-  const double* fold_partial;
-  int fold_T;
-  double* fold_per_image;   // [B] or nullptr
-  // x6 conv3 (W6 instantiation): the weights pre-split into three bf16 planes
-  // (iclr17_split_packed(w_packed, 25, CI, CO): [3][25][CI/8][CO][8]) instead of split per k-step
-  const unsigned short* w6;
-  long w6_plane;
-  float* fold_total;        // scale · Σ, 0-dim
-  double fold_scale;
-  // deconv3 in the h3 form (deconv3_x6_kernel<CI, true>): the input as two fp16 planes
-  // (in_split) and the weights pre-split into two fp16 planes whose packing trailer holds
-  // 2⁻¹¹/(σ_a·σ_w) at wscale[1]; range: the chain's h3 range flag (read only, the NaN poison)
-  const float* wscale;
-  int* range;
-};
-
-// iclr17_reduce_partials inside the last kernel of the eval chain (deconv3): the per-image sums of
-// conv3's T bit partials and scale · their total, by workgroup 0 before its own tile, which saves
-// the chain a kernel launch and boundary. Arithmetic and order are reduce_partials_kernel's
-// (csrc/aux.hip): per image a lane-strided sum over t ≡ lane (mod 64) in t order, a fixed xor
-// butterfly, then the images added in order by thread 0 — so the results are bit-identical.
-// The loads of a wave's images go out together (one memory latency for the common T ≤ 64).
-// poison: the h3 range flag was set upstream (deconv3_x6_kernel<CI, true>); every total is NaN.
-template <int NTHR>
-__device__ __forceinline__ void fold_bits(const EngineArgs& a, double* img /* LDS, 64 doubles */,
-                                          bool poison = false) {
-  constexpr int NW = NTHR / 64, KI = (64 + NW - 1) / NW;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int T = a.fold_T;
-  double acc = 0.0;
-  for (int b0 = 0; b0 < a.B; b0 += 64) {
-    const int nb = a.B - b0 < 64 ? a.B - b0 : 64;
-    double v[KI];
-#pragma unroll
-    for (int k = 0; k < KI; ++k) {
-      const int b = wave + k * NW;
-      v[k] = b < nb && lane < T ? a.fold_partial[(long)(b0 + b) * T + lane] : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < KI; ++k) {
-      const int b = wave + k * NW;
-      if (b >= nb) continue;
-      double s = 0.0 + v[k];
-      for (int t = lane + 64; t < T; t += 64) s += a.fold_partial[(long)(b0 + b) * T + t];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-      if (poison) s = __builtin_nan("");
-      if (lane == 0) {
-        img[b] = s;
-        if (a.fold_per_image) a.fold_per_image[b0 + b] = s;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-      for (int b = 0; b < nb; ++b) acc += img[b];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && a.fold_total) *a.fold_total = (float)(acc * a.fold_scale);
-}
-
-struct TileInfo {
-  int b, ty, tx, py, px, nb;
-  int th;   // tile height in base-grid rows (tile = th × 8 base pixels)
-};
-
-template <int TH = 8>
-__device__ __forceinline__ TileInfo decode_tile(const EngineArgs& a) {
-  TileInfo t;
-  t.th = TH;
-  int bid = blockIdx.x;
-  // stride phases in dispatch order 0..3 (9, 6, 6, 4 taps): longest workgroups first
-  const int per_ph = a.tiles_x * a.tiles_y * a.B;
-  const int ph = bid / per_ph;
-  bid -= ph * per_ph;
-  t.tx = bid % a.tiles_x;
-  bid /= a.tiles_x;
-  t.ty = bid % a.tiles_y;
-  bid /= a.tiles_y;
-  t.b = bid;
-  t.py = ph / a.tt.npx;
-  t.px = ph % a.tt.npx;
-  t.nb = blockIdx.y;
-  return t;
-}
-
-// Row m of a tile → output pixel (NHWC row offset in pixels) or -1 when outside the grid.
-__device__ __forceinline__ long out_pixel(const EngineArgs& a, const TileInfo& t, int m) {
-  const int gy = t.ty * t.th + (m >> 3), gx = t.tx * 8 + (m & 7);
-  if (gy >= a.gh || gx >= a.gw) return -1;
-  const int oy = gy * a.sout + t.py, ox = gx * a.sout + t.px;
-  return ((long)t.b * a.Hout + oy) * a.Wout + ox;
-}
-
-// Store an [R][BN] tile held in LDS (row stride ld) to NHWC rows of CO floats at column
-// offset col0, 16 bytes per lane, rows outside the grid skipped (T threads).
-template <int BN, int R = BM, int T = 256>
-__device__ __forceinline__ void store_tile_rows(const EngineArgs& a, const TileInfo& t,
-                                                const float* s, int ld, float* dst, int CO,
-                                                int col0) {
-  constexpr int C4 = BN / 4;
-  for (int idx = threadIdx.x; idx < R * C4; idx += T) {
-    const int m = idx / C4, c4 = idx % C4;
-    const long p = out_pixel(a, t, m);
-    if (p < 0) continue;
-    const f4 v = *(const f4*)(s + m * ld + c4 * 4);
-    *(f4*)(dst + p * CO + col0 + c4 * 4) = v;
-  }
-}
-
-// Inverse of store_tile_rows: NHWC rows of the tile's pixels → LDS (zeros outside the grid).
-template <int BN>
-__device__ __forceinline__ void load_tile_rows(const EngineArgs& a, const TileInfo& t,
-                                               const float* __restrict__ src, float* s, int ld,
-                                               int CO, int col0) {
-  constexpr int C4 = BN / 4;
-  for (int idx = threadIdx.x; idx < BM * C4; idx += 256) {
-    const int m = idx / C4, c4 = idx % C4;
-    const long p = out_pixel(a, t, m);
-    const f4 v = p < 0 ? f4{0.f, 0.f, 0.f, 0.f} : *(const f4*)(src + p * CO + col0 + c4 * 4);
-    *(f4*)(s + m * ld + c4 * 4) = v;
-  }
-}
-
-// Store a [BM][BN] LDS tile (row stride ld) as the three bf16 planes of the x6 activation
-// format (rows of CO channels, columns col0 ..), 8 channels (16 bytes per plane) per lane.
-template <int BN, int R = BM, int T = 256>
-__device__ __forceinline__ void store_tile_rows_split(const EngineArgs& a, const TileInfo& t,
-                                                      const float* s, int ld, int CO, int col0) {
-  constexpr int C8 = BN / 8;
-  for (int idx = threadIdx.x; idx < R * C8; idx += T) {
-    const int m = idx / C8, c8 = idx % C8;
-    const long p = out_pixel(a, t, m);
-    if (p < 0) continue;
-    u4 hi, mi, lo;
-    split8(*(const f4*)(s + m * ld + c8 * 8), *(const f4*)(s + m * ld + c8 * 8 + 4), hi, mi, lo);
-    unsigned short* d = a.out_split + p * CO + col0 + c8 * 8;
-    if (a.out_cm) {   // [B][C/32][h][w][32]: image b, chunk c, pixel q of the image
-      const long hw = (long)a.Hout * a.Wout, b = p / hw, q = p - b * hw;
-      const int c = col0 + c8 * 8;
-      d = a.out_split + ((b * (CO / 32) + (c >> 5)) * hw + q) * 32 + (c & 31);
-    }
-    *(u4*)d = hi;
-    *(u4*)(d + a.out_plane) = mi;
-    *(u4*)(d + 2 * a.out_plane) = lo;
-  }
-}
-
-// Column sums of an LDS tile [BM][ld] over the rows inside the output grid → dst[blockIdx.x][CO],
-// fixed row order (deterministic). Feeds bias / β gradients without another pass over HBM.
-template <int CO>
-__device__ __forceinline__ void tile_colsum(const EngineArgs& a, const TileInfo& t, const float* s,
-                                            int ld, float* dst) {
-  const int gy0 = t.ty * 8, gx0 = t.tx * 8;
-  const int rows = a.gh - gy0 < 8 ? a.gh - gy0 : 8, cols = a.gw - gx0 < 8 ? a.gw - gx0 : 8;
-  for (int c = threadIdx.x; c < CO; c += 256) {
-    float acc = 0.f;
-    for (int my = 0; my < rows; ++my)
-      for (int mx = 0; mx < cols; ++mx) acc += s[(my * 8 + mx) * ld + c];
-    dst[(long)blockIdx.x * CO + c] = acc;
-  }
-}
-
-// Load the B fragments of one 32-deep k-step: packed weights [.][CIq][CO][4], quad rows
-// q0 .. q0+7, columns ncol0 + nt*16 + (lane & 15).
-template <int NT, int CO>
-__device__ __forceinline__ void load_bfrag(f4 (&bf)[2][NT], const float* __restrict__ wp, int q0,
-                                           int ncol0, int lane) {
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-    const int q = q0 + kk * 4 + (lane >> 4);
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const int n = ncol0 + nt * 16 + (lane & 15);
-      bf[kk][nt] = *(const f4*)(wp + ((long)q * CO + n) * 4);
-    }
-  }
-}
-
-template <int MT, int NT>
-__device__ __forceinline__ void mfma_block(f4 (&acc)[MT][NT], const f4 (&af)[MT], const f4 (&bf)[NT]) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma16(af[mt][e], bf[nt][e], acc[mt][nt]);
-}
-
-// Two-level accumulation of the exact-f32 contractions (common.h): a 32-deep
-// k-block (two mfma_block calls) is summed from zero into `part`, then added to acc.
-template <int MT, int NT>
-__device__ __forceinline__ void zero_tile(f4 (&t)[MT][NT]) {
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) t[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-}
-template <int MT, int NT>
-__device__ __forceinline__ void add_tile(f4 (&acc)[MT][NT], const f4 (&t)[MT][NT]) {
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] += t[mt][nt];
-}
-
-// ----------------------------------------------------------------------------- GDN epilogue
-// Channel contraction of an LDS tile: out[m][i] = Σ_j sX[m][j] · B[j][i], B packed
-// [CO/4][CO][4] (packed[q][i][e] = B[4q+e][i]) and read straight from L2, one k-block ahead.
-template <int CO, int MT, int NT, bool SQ = false>
-__device__ __forceinline__ void chan_gemm(f4 (&acc)[MT][NT], const float* sX,
-                                          const float* __restrict__ bp, int wm, int ncol0,
-                                          int lane) {
-  constexpr int XS = CO + 8;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-  f4 g[NT], gn[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-    g[nt] = *(const f4*)(bp + ((long)(lane >> 4) * CO + ncol0 + nt * 16 + (lane & 15)) * 4);
-  constexpr int KB = CO / 16;
-#pragma unroll 2
-  for (int kb = 0; kb < KB; ++kb) {
-    if (kb + 1 < KB) {
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-        gn[nt] = *(const f4*)(bp + ((long)((kb + 1) * 4 + (lane >> 4)) * CO + ncol0 + nt * 16 +
-                                    (lane & 15)) * 4);
-    }
-    f4 af[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      af[mt] = *(const f4*)(sX + (wm * MT * 16 + mt * 16 + (lane & 15)) * XS + kb * 16 +
-                            4 * (lane >> 4));
-      if (SQ) af[mt] = af[mt] * af[mt];
-    }
-    mfma_block<MT, NT>(acc, af, g);
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) g[nt] = gn[nt];
-  }
-}
-
-// s_waitcnt vmcnt(N) (exp/lgkm counters untouched) + workgroup barrier; the empty asm statements
-// keep the compiler from moving LDS accesses across it.
-template <int N>
-__device__ __forceinline__ void wait_vmcnt_barrier() {
-  static_assert(N >= 0 && N < 64, "vmcnt field");
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-// Zero source for glds lanes whose tap falls outside the image (padding).
-__device__ __attribute__((aligned(16))) float g_zero16[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void glds16(const float* src, float* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// The same contraction with γ streamed through LDS by LDS-DMA: 16-row k-blocks ([4][CO][4],
-// contiguous in the packed layout), two stages at sG, one barrier per k-block. Entry: the
-// caller's sX writes are complete in program order (the first loop barrier publishes them);
-// exit: no barrier after the last k-block (callers add one before reusing sX or sG).
-constexpr int GSTAGE_FLOATS(int CO) { return 2 * 16 * CO; }
-
-template <int CO, int MT, int NT, bool SQ = false, int NW = 4>
-__device__ __forceinline__ void chan_gemm_lds(f4 (&acc)[MT][NT], const float* sX,
-                                              const float* __restrict__ bp, float* sG, int wm,
-                                              int ncol0, int lane, int wave) {
-  constexpr int XS = CO + 8;
-  constexpr int GST = 16 * CO;          // floats per stage
-  constexpr int NGI = GST * 4 / 1024;   // glds wave-instructions per stage
-  constexpr int GI_W = (NGI + NW - 1) / NW;
-  constexpr int KB = CO / 16;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-  auto issue = [&](int kb, int buf) {
-    const float* src = bp + kb * GST + lane * 4;
-#pragma unroll
-    for (int j = 0; j < GI_W; ++j) {
-      const int i = wave + NW * j;
-      if (NGI % NW == 0 || i < NGI) glds16(src + i * 256, sG + buf * GST + i * 256);
-    }
-  };
-  const int goff = ((lane >> 4) * CO + ncol0 + (lane & 15)) * 4;
-  const float* xrow = sX + (wm * MT * 16 + (lane & 15)) * XS + 4 * (lane >> 4);
-  issue(0, 0);
-#pragma unroll 2
-  for (int kb = 0; kb < KB; ++kb) {
-    dma_barrier();
-    if (kb + 1 < KB) issue(kb + 1, (kb + 1) & 1);
-    const float* g = sG + (kb & 1) * GST + goff;
-    f4 bf[NT], af[MT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) bf[nt] = *(const f4*)(g + nt * 64);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      af[mt] = *(const f4*)(xrow + mt * 16 * XS + kb * 16);
-      if (SQ) af[mt] = af[mt] * af[mt];
-    }
-    mfma_block<MT, NT>(acc, af, bf);
-  }
-}
-
-// x6 channel contraction: acc[m][i] = Σ_j sX[m][j]·Γ[j][i], sX fp32 in LDS (split in VALU, one
-// 8-channel fragment per (mt, 32-deep k-block)), Γ pre-split [3][CO/8][CO][8] bf16 — the
-// B-fragment layout of v_mfma_f32_16x16x32_bf16 — read from L2 (221 KB at CO = 192; there is
-// no LDS left beside the x² tile at two workgroups per CU), one k-block ahead. Entry: the sX
-// writes of every wave are published (caller's barrier).
-template <int CO, int MT, int NT, bool SQ = false>
-__device__ __forceinline__ void chan_gemm_x6(f4 (&acc)[MT][NT], const float* sX,
-                                             const unsigned short* __restrict__ g6, int wm,
-                                             int ncol0, int lane) {
-  constexpr int XS = CO + 8;
-  constexpr int KB = CO / 32;
-  constexpr long GP = (long)CO * CO;   // plane stride
-  static_assert(KB % 2 == 0, "k-blocks in pairs (ping-pong B registers)");
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-  const float* xrow = sX + (wm * MT * 16 + (lane & 15)) * XS + 8 * (lane >> 4);
-  const unsigned short* gb = g6 + ((lane >> 4) * CO + ncol0 + (lane & 15)) * 8;
-  u4 b0[3][NT], b1[3][NT];
-  auto load = [&](int kb, u4 (&b)[3][NT]) {
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-        b[p][nt] = *(const u4*)(gb + p * GP + (long)kb * 4 * CO * 8 + nt * 128);
-  };
-  auto block = [&](int kb, const u4 (&b)[3][NT]) {
-    X6Acc st;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      u4 ah, am, al;
-      f4 x0 = *(const f4*)(xrow + mt * 16 * XS + kb * 32);
-      f4 x1 = *(const f4*)(xrow + mt * 16 * XS + kb * 32 + 4);
-      if (SQ) {   // u² rounded to fp32 first, as the fp32 contraction (and conv2d(x², γ)) does
-        x0 = x0 * x0;
-        x1 = x1 * x1;
-      }
-      split8(x0, x1, ah, am, al);
-      const bf8 Ah = __builtin_bit_cast(bf8, ah), Am = __builtin_bit_cast(bf8, am),
-                Al = __builtin_bit_cast(bf8, al);
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const bf8 Bh = __builtin_bit_cast(bf8, b[0][nt]), Bm = __builtin_bit_cast(bf8, b[1][nt]),
-                  Bl = __builtin_bit_cast(bf8, b[2][nt]);
-        mfma_x6<false>(acc, st, mt, nt, Ah, Am, Al, Bh, Bm, Bl);
-      }
-    }
-    x6_flush<false>(acc, st);
-  };
-  load(0, b0);
-  for (int kb = 0; kb < KB; kb += 2) {
-    load(kb + 1, b1);
-    block(kb, b0);
-    if (kb + 2 < KB) load(kb + 2, b0);
-    block(kb + 1, b1);
-  }
-}
-
-// The same x6 contraction with the A operand already split in LDS: three bf16 planes
-// [3][R][CO+8] (u16), written once by the producing waves, so no wave splits rows in VALU (with
-// one wave row every wave used to split the whole x² tile for itself).
-template <int CO, int MT, int NT, int R>
-__device__ __forceinline__ void chan_gemm_x6p(f4 (&acc)[MT][NT], const unsigned short* sP,
-                                              const unsigned short* __restrict__ g6, int wm,
-                                              int ncol0, int lane) {
-  constexpr int PS = CO + 8;
-  constexpr int KB = CO / 32;
-  constexpr long GP = (long)CO * CO;
-  static_assert(KB % 2 == 0, "k-blocks in pairs (ping-pong B registers)");
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-  const unsigned short* arow = sP + (wm * MT * 16 + (lane & 15)) * PS + 8 * (lane >> 4);
-  const unsigned short* gb = g6 + ((lane >> 4) * CO + ncol0 + (lane & 15)) * 8;
-  u4 b0[3][NT], b1[3][NT];
-  auto load = [&](int kb, u4 (&b)[3][NT]) {
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-        b[p][nt] = *(const u4*)(gb + p * GP + (long)kb * 4 * CO * 8 + nt * 128);
-  };
-  auto block = [&](int kb, const u4 (&b)[3][NT]) {
-    X6Acc st;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const unsigned short* a = arow + mt * 16 * PS + kb * 32;
-      const bf8 Ah = __builtin_bit_cast(bf8, *(const u4*)(a));
-      const bf8 Am = __builtin_bit_cast(bf8, *(const u4*)(a + R * PS));
-      const bf8 Al = __builtin_bit_cast(bf8, *(const u4*)(a + 2 * R * PS));
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const bf8 Bh = __builtin_bit_cast(bf8, b[0][nt]), Bm = __builtin_bit_cast(bf8, b[1][nt]),
-                  Bl = __builtin_bit_cast(bf8, b[2][nt]);
-        mfma_x6<false>(acc, st, mt, nt, Ah, Am, Al, Bh, Bm, Bl);
-      }
-    }
-    x6_flush<false>(acc, st);
-  };
-  load(0, b0);
-  for (int kb = 0; kb < KB; kb += 2) {
-    load(kb + 1, b1);
-    block(kb, b0);
-    if (kb + 2 < KB) load(kb + 2, b0);
-    block(kb + 1, b1);
-  }
-}
-
-// LDS floats the GDN core needs for an R-row tile (fp32 x² tile + γ stages, or, for the x6
-// contraction, the three split planes of x²).
-constexpr int gdn_lds_floats(int R, int CO, bool G6) {
-  return G6 ? (3 * R * (CO + 8) + 1) / 2 : R * (CO + 8) + GSTAGE_FLOATS(CO);
-}
-
-// x (bias already added) in accumulator layout → GDN(x) (or IGDN) left in LDS sX[BM][CO+4].
-// models/GDN.py:83-90: n = conv2d(x², γ, β) = β + Σ_j γ[i][j]·x_j²;  y = x / √n | x·√n.
-// The caller guarantees smem is free on entry; on return every wave has passed a barrier after
-// the last sX write.
-template <int CO, int MT, int NT, bool INVERSE, int R = BM, int T = 256, bool G6 = false>
-__device__ __forceinline__ void gdn_core(const f4 (&x)[MT][NT], float* sX,
-                                         const float* __restrict__ gbeta,
-                                         const float* __restrict__ gp, int wm, int ncol0,
-                                         int lane, const unsigned short* g6 = nullptr) {
-  constexpr int XS = CO + 8;
-  f4 nacc[MT][NT];
-  if constexpr (G6) {
-    // x² (rounded to fp32, as conv2d(x², γ) sees it) split once into three bf16 planes
-    unsigned short* sP = (unsigned short*)sX;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-          const int col = ncol0 + nt * 16 + (lane & 15);
-          const float v = x[mt][nt][r] * x[mt][nt][r];
-          const unsigned h = __float_as_uint(v) & 0xffff0000u;
-          const float rr = v - __uint_as_float(h);
-          const unsigned m = __float_as_uint(rr) & 0xffff0000u;
-          const unsigned l = __float_as_uint(rr - __uint_as_float(m));
-          sP[row * XS + col] = (unsigned short)(h >> 16);
-          sP[(R + row) * XS + col] = (unsigned short)(m >> 16);
-          sP[(2 * R + row) * XS + col] = (unsigned short)(l >> 16);
-        }
-    __syncthreads();   // planes of every wave published
-    chan_gemm_x6p<CO, MT, NT, R>(nacc, sP, g6, wm, ncol0, lane);
-  } else {
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-        const int col = ncol0 + nt * 16 + (lane & 15);
-        const float v = x[mt][nt][r];
-        sX[row * XS + col] = v * v;
-      }
-    chan_gemm_lds<CO, MT, NT, false, T / 64>(nacc, sX, gp, sX + R * XS, wm, ncol0, lane,
-                                             __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
-  }
-  __syncthreads();  // all reads of x² done
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-        const int col = ncol0 + nt * 16 + (lane & 15);
-        const float n = nacc[mt][nt][r] + gbeta[col];
-        const float s = sqrtf(n);
-        sX[row * XS + col] = INVERSE ? x[mt][nt][r] * s : x[mt][nt][r] / s;
-      }
-  __syncthreads();
-}
-
-// Accumulator-layout values → LDS tile [BM][ld] (caller synchronises).
-template <int MT, int NT>
-__device__ __forceinline__ void acc_to_lds(const f4 (&v)[MT][NT], float* s, int ld, int wm,
-                                           int col0, int lane) {
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-        s[row * ld + col0 + nt * 16 + (lane & 15)] = v[mt][nt][r];
-      }
-}
-
-template <int CO, int MT, int NT, bool INVERSE, int R = BM, int T = 256, bool G6 = false>
-__device__ __forceinline__ void gdn_epilogue(f4 (&x)[MT][NT], float* smem, const EngineArgs& a,
-                                             const TileInfo& t, int wm, int ncol0, int lane) {
-  constexpr int XS = CO + 8;
-  gdn_core<CO, MT, NT, INVERSE, R, T, G6>(x, smem, a.gbeta, a.ggamma, wm, ncol0, lane,
-                                          a.ggamma6);
-  if (a.out != nullptr) store_tile_rows<CO, R, T>(a, t, smem, XS, a.out, CO, 0);
-  if (a.out_split != nullptr) store_tile_rows_split<CO, R, T>(a, t, smem, XS, CO, 0);
-  if (a.pre != nullptr) {
-    __syncthreads();
-    acc_to_lds<MT, NT>(x, smem, XS, wm, ncol0, lane);
-    __syncthreads();
-    store_tile_rows<CO, R, T>(a, t, smem, XS, a.pre, CO, 0);
-  }
-}
-
-// ------------------------------------------------------------------ GDN / IGDN backward epilogue
-// g = ∂L/∂(GDN output) in accumulator layout (the dgrad GEMM of the NEXT layer); u = the saved
-// GDN input (pre-activation). Mirrors the autograd of models/GDN.py:83-90 op for op:
-//   n = β + γ·u², s = √n
-//   GDN : ∂u = g/s + 2u·(γᵀ dn),  dn = ((−g·u)/(s·s)) / (2s)      (div, sqrt backward)
-//   IGDN: ∂u = g·s + 2u·(γᵀ dn),  dn = (g·u) / (2s)               (mul, sqrt backward)
-// Stores ∂u (a.out) and dn (a.tout; dγ = Σ_p dn ⊗ u², dβ = Σ_p dn are reduced later).
-template <int CO, int MT, int NT, bool INVERSE>
-__device__ __forceinline__ void gdn_bwd_epilogue(f4 (&g)[MT][NT], float* smem, const EngineArgs& a,
-                                                 const TileInfo& t, int wm, int ncol0, int lane) {
-  constexpr int XS = CO + 8;
-  float* sX = smem;
-  float* sG = smem + BM * XS;
-  const int wave = threadIdx.x >> 6;
-  load_tile_rows<CO>(a, t, a.saved, sX, XS, CO, 0);   // u, kept in LDS through GEMM 1
-  f4 acc2[MT][NT];
-  if (a.ggamma6 != nullptr) {   // x6: γ and γᵀ pre-split, from L2 (no LDS stages)
-    __syncthreads();            // u tile published
-    chan_gemm_x6<CO, MT, NT, true>(acc2, sX, a.ggamma6, wm, ncol0, lane);
-  } else {
-    chan_gemm_lds<CO, MT, NT, true>(acc2, sX, a.ggamma, sG, wm, ncol0, lane, wave);  // Σ_j γ[i][j] u_j²
-  }
-  __syncthreads();
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int col = ncol0 + nt * 16 + (lane & 15);
-        const int idx = (wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r) * XS + col;
-        const float uu = sX[idx];  // read, then rewritten by the same lane: no barrier needed
-        const float n = acc2[mt][nt][r] + a.gbeta[col];
-        const float sq = sqrtf(n);
-        const float gg = g[mt][nt][r];
-        float dn;
-        if (INVERSE) {
-          g[mt][nt][r] = gg * sq;
-          dn = (gg * uu) / (2.0f * sq);
-        } else {
-          g[mt][nt][r] = gg / sq;
-          dn = ((-gg * uu) / (sq * sq)) / (2.0f * sq);
-        }
-        sX[idx] = dn;
-      }
-  if (a.ggammaT6 != nullptr) {
-    __syncthreads();            // dn tile published
-    chan_gemm_x6<CO, MT, NT>(acc2, sX, a.ggammaT6, wm, ncol0, lane);
-  } else {
-    chan_gemm_lds<CO, MT, NT>(acc2, sX, a.ggammaT, sG, wm, ncol0, lane, wave);  // w_j = Σ_i γ[i][j] dn_i
-  }
-  store_tile_rows<CO>(a, t, sX, XS, a.tout, CO, 0);
-  if (a.colsum_t != nullptr) tile_colsum<CO>(a, t, sX, XS, a.colsum_t);
-  __syncthreads();
-  // u again, from HBM/L2 rather than held in 48 VGPRs through both contractions (that kept
-  // the kernel at one wave per SIMD)
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-      const long p = out_pixel(a, t, row);
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const int col = ncol0 + nt * 16 + (lane & 15);
-        const float uu = p < 0 ? 0.f : a.saved[p * CO + col];
-        sX[row * XS + col] = g[mt][nt][r] + acc2[mt][nt][r] * (2.0f * uu);
-      }
-    }
-  __syncthreads();
-  // the fp32 ∂u is optional beside its split form (the x6 backward hands only the split on)
-  if (a.out != nullptr) store_tile_rows<CO>(a, t, sX, XS, a.out, CO, 0);
-  if (a.out_split != nullptr) store_tile_rows_split<CO>(a, t, sX, XS, CO, 0);   // x6 consumer
-  if (a.colsum_out != nullptr) tile_colsum<CO>(a, t, sX, XS, a.colsum_out);
-}
-
-// ------------------------------------------------------------------------- rate backward epilogue
-// ∂L/∂ỹ = (decoder dgrad in acc) + ∂L/∂bpp / (B·H·W) · ∂bits/∂ỹ, and the per-channel parameter
-// gradients of the factorised model, as the autograd of model.py:71-78 / bitEstimator.py:20-25
-// evaluates them (per element; summed per tile here, over tiles later).
-__device__ __forceinline__ float rate_bwd_element(float z, const float* __restrict__ rp, int C,
-                                                  int c, float gsc, float (&pg)[11]) {
-  float xs[2][4], Ts[2][3], F[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    float x = h == 0 ? z + 0.5f : z - 0.5f;
-    xs[h][0] = x;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float t = x * rp[(3 * k) * C + c] + rp[(3 * k + 1) * C + c];
-      const float T = tanhf(t);
-      x = t + T * rp[(3 * k + 2) * C + c];
-      Ts[h][k] = T;
-      xs[h][k + 1] = x;
-    }
-    const float t4 = x * rp[9 * C + c] + rp[10 * C + c];
-    F[h] = 1.0f / (1.0f + expf(-t4));
-  }
-  const float prob = F[0] - F[1];
-  const float raw = (-1.0f * logf(prob + 1e-10f)) / 0.693147182464599609375f;
-  const bool pass = raw >= 0.0f && raw <= 50.0f;          // clamp(·, 0, 50) backward mask
-  const float g0 = pass ? gsc : 0.0f;
-  const float gl = ((g0 / 0.693147182464599609375f) * -1.0f) / (prob + 1e-10f);
-  float dz = 0.0f;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const float gF = h == 0 ? gl : -gl;
-    const float gt4 = (gF * (1.0f - F[h])) * F[h];        // sigmoid backward
-    pg[10] += gt4;                                          // b4
-    pg[9] += gt4 * xs[h][3];                                // softplus(h4)
-    float gx = gt4 * rp[9 * C + c];
-#pragma unroll
-    for (int k = 2; k >= 0; --k) {
-      const float T = Ts[h][k];
-      const float gT = gx * rp[(3 * k + 2) * C + c];
-      pg[3 * k + 2] += gx * T;                              // tanh(a_k)
-      const float gt = gx + gT * (1.0f - T * T);            // tanh backward
-      pg[3 * k + 1] += gt;                                  // b_k
-      pg[3 * k] += gt * xs[h][k];                           // softplus(h_k)
-      gx = gt * rp[(3 * k) * C + c];
-    }
-    dz += gx;
-  }
-  return dz;
-}
-
-template <int CO, int BN, int MT, int NT>
-__device__ __forceinline__ void rate_bwd_epilogue(f4 (&acc)[MT][NT], float* smem, const EngineArgs& a,
-                                                  const TileInfo& t, int wm, int ncol0, int lane) {
-  constexpr int OS = BN + 4;
-  float* sO = smem;
-  const int cbase = t.nb * BN;
-  const bool rate = a.gscale != nullptr;
-  if (rate) load_tile_rows<BN>(a, t, a.saved, sO, OS, CO, cbase);
-  __syncthreads();
-  const float gsc = rate ? a.gscale[0] / a.count : 0.0f;
-  float pg[NT][11];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int k = 0; k < 11; ++k) pg[nt][k] = 0.0f;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-        const int lcol = ncol0 - cbase + nt * 16 + (lane & 15);
-        float v = acc[mt][nt][r];
-        if (rate && out_pixel(a, t, row) >= 0)
-          v += rate_bwd_element(sO[row * OS + lcol], a.rate, CO, cbase + lcol, gsc, pg[nt]);
-        sO[row * OS + lcol] = v;
-      }
-  __syncthreads();
-  store_tile_rows<BN>(a, t, sO, OS, a.out, CO, cbase);
-  if (a.out_split != nullptr) store_tile_rows_split<BN>(a, t, sO, OS, CO, cbase);
-  if (rate) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        float v = pg[nt][k];
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        // row = the tile's linear index
-        const long row = ((long)t.b * a.tiles_y + t.ty) * a.tiles_x + t.tx;
-        if (lane < 16) a.rpart[(row * 11 + k) * CO + ncol0 + nt * 16 + lane] = v;
-      }
-  }
-}
-
-// ------------------------------------------------------------------- quantiser + rate epilogue
-// model.py:48-56 (ŷ = round(y) | y + noise) and model.py:71-73 (bits per element), summed per
-// tile; y and ŷ stored NHWC.
-template <int CO, int BN, int MT, int NT, int WN>
-__device__ __forceinline__ void quant_epilogue(f4 (&acc)[MT][NT], float* smem, const EngineArgs& a,
-                                               const TileInfo& t, int wm, int ncol0, int lane,
-                                               int wave) {
-  constexpr int OS = BN + 4;
-  float* sO = smem;
-  float bits = 0.f;
-  const int cbase = t.nb * BN;
-  // Integer latents: the per-channel table of the same element_bits, read for every element
-  // (index clamped, loads all in flight); the others (noise mode, |ŷ| > 32, no table) are
-  // evaluated in one block after them — a per-element `table ? lookup : element_bits` branch
-  // skipped 2 KB of inlined element_bits per element, an instruction-cache miss each time.
-  // The bits are added in the same element order either way.
-  float yv[MT][NT][4], bv[MT][NT][4];
-  bool slow = false;
-  const bool table = a.rtab != nullptr && a.qmode == ICLR17_QUANT_ROUND;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-        const int lcol = ncol0 - cbase + nt * 16 + (lane & 15);
-        const int col = cbase + lcol;
-        const int gy = t.ty * 8 + (row >> 3), gx = t.tx * 8 + (row & 7);
-        const bool ok = gy < a.gh && gx < a.gw;
-        const float y = acc[mt][nt][r];
-        float yh;
-        if (a.qmode == ICLR17_QUANT_ROUND) {
-          yh = rintf(y);
-        } else {
-          const float u = ok ? a.noise[(((long)t.b * CO + col) * a.Hout + gy) * a.Wout + gx] : 0.f;
-          yh = y + u;
-        }
-        yv[mt][nt][r] = yh;
-        bv[mt][nt][r] = table ? a.rtab[col * 65 + (int)fminf(fmaxf(yh, -32.f), 32.f) + 32] : 0.f;
-        slow |= ok && !(table && fabsf(yh) <= 32.f);
-        sO[row * OS + lcol] = yh;
-      }
-  if (slow) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float yh = yv[mt][nt][r];
-          if (!(table && fabsf(yh) <= 32.f))
-            bv[mt][nt][r] = element_bits(yh, a.rate, CO, ncol0 + nt * 16 + (lane & 15));
-        }
-  }
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-        const int gy = t.ty * 8 + (row >> 3), gx = t.tx * 8 + (row & 7);
-        if (gy < a.gh && gx < a.gw) bits += bv[mt][nt][r];
-      }
-  __syncthreads();
-  store_tile_rows<BN>(a, t, sO, OS, a.yhat, CO, cbase);
-  if (a.out_split != nullptr) store_tile_rows_split<BN>(a, t, sO, OS, CO, cbase);   // ŷ, x6 form
-  if (a.out != nullptr) {
-    __syncthreads();
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-          const int lcol = ncol0 - cbase + nt * 16 + (lane & 15);
-          sO[row * OS + lcol] = acc[mt][nt][r];
-        }
-    __syncthreads();
-    store_tile_rows<BN>(a, t, sO, OS, a.out, CO, cbase);
-  }
-  // deterministic tile sum: lanes → wave (xor tree) → waves in order
-  bits = wave_sum(bits);
-  __syncthreads();
-  if (lane == 0) sO[wave] = bits;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int w = 0; w < 4; ++w) s += (double)sO[w];
-    const int tile = (t.ty * a.tiles_x + t.tx) * gridDim.y + t.nb;
-    a.partial[(long)t.b * a.partials_per_image + tile] = s;
-  }
-}
-
-// --------------------------------------------------------------- deconv3 (all-phase) epilogue
-// Column n = co*16 + ry*4 + rx; row m = base pixel q (8×8 block). Output pixel
-// (4·qy + ry, 4·qx + rx) of channel co. synthesis_17.py:23 + model.py:59 clamp(0, 1).
-template <int MT, int NT>
-__device__ __forceinline__ void out3_epilogue(f4 (&acc)[MT][NT], float* smem, const EngineArgs& a,
-                                              const TileInfo& t, int wm, int lane, int wave) {
-  constexpr int SS = 33;  // padded row of the 32×32 output block
-  float* sO = smem;       // [3][32][33]
-  const int H = a.Hout, W = a.Wout;  // image dims
-  float vals[MT][NT][4];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) vals[mt][nt][r] = acc[mt][nt][r] + a.bias[nt];
-  float sse = 0.f;
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 1 && a.recon == nullptr) break;
-    float* dst = pass == 0 ? a.out : a.recon;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-          const int ph = lane & 15;
-          const int oyl = (m >> 3) * 4 + (ph >> 2), oxl = (m & 7) * 4 + (ph & 3);
-          float v = vals[mt][nt][r];
-          if (pass == 0) v = fminf(fmaxf(v, 0.0f), 1.0f);
-          sO[(nt * 32 + oyl) * SS + oxl] = v;
-        }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < 3 * 32 * 8; idx += 256) {
-      const int c4 = idx & 7, row = (idx >> 3) & 31, co = idx >> 8;
-      const int oy = t.ty * 32 + row, ox = t.tx * 32 + c4 * 4;
-      if (oy >= H || ox >= W) continue;
-      const float* s = sO + (co * 32 + row) * SS + c4 * 4;
-      const f4 v = f4{s[0], s[1], s[2], s[3]};
-      const long off = (((long)t.b * 3 + co) * H + oy) * W + ox;
-      *(f4*)(dst + off) = v;
-      if (pass == (a.sse_unclipped ? 1 : 0) && a.xref != nullptr) {
-        const f4 xr = *(const f4*)(a.xref + off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = v[e] - xr[e];
-          sse += d * d;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (a.xref != nullptr) {
-    sse = wave_sum(sse);
-    if (lane == 0) sO[wave] = sse;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double s = 0.0;
-      for (int w = 0; w < 4; ++w) s += (double)sO[w];
-      a.partial[(long)t.b * a.partials_per_image + t.ty * a.tiles_x + t.tx] = s;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------- the engine kernel
-// Main loop: both operands reach LDS by LDS-DMA (global_load_lds_dwordx4), so no staging VGPRs
-// and no ds_write pass. A step is 32 input channels of one tap:
-//   A image [BM][32] floats, 128-byte rows, 16-byte chunk c stored at c ^ (row & 7) — the swizzle
-//     lives in the per-lane SOURCE address (glds writes lane-linear), and makes the fragment
-//     reads (16 rows × one chunk per lane group) bank-conflict free;
-//   B image [8 quads][BN][4] floats: the packed weights of the step, copied linearly.
-// Two LDS stages, one barrier per step: the DMA of step s+1 is in flight while step s computes.
-//
-// X6 (the bf16x6 mode): the A operand arrives as three bf16 planes (hi, mid, lo — the exact split
-// written by the producing layer's epilogue), A image [3][BM][32] bf16 with 64-byte rows whose
-// 16-byte piece g sits at g ^ ((row >> 1) & 3); B stays fp32 in LDS and each wave splits its own
-// columns in VALU. One 32-deep step = per 16×16 tile six v_mfma_f32_16x16x32_bf16:
-// lo·hi + hi·lo + mid·mid + mid·hi + hi·mid + hi·hi (the dropped mid·lo, lo·mid, lo·lo terms are
-// below 2^-24 of the product), accumulated in fp32.
-// W6 (x6 conv3): B arrives pre-split, [3 planes][4 k-groups][BN][8] bf16 per stage (a.w6), and
-// the fragments are read as they are: conv3's 2×2 waves split each weight column for only two
-// row tiles, so the per-step split was 3.7 VALU instructions per MFMA. Same bf16 operands (the
-// split is iclr17_split_packed's, i.e. the same split8 on the same quads): bit-identical output.
-// (The h3 form's convolutions run on the h3 engine, csrc/engine_h3.hip.)
-template <int CI, int CO, int BN, int WM, int WN, int EPI, bool X6, int BMT = BM, bool W6 = false>
-__device__ __forceinline__ void engine_body(const EngineArgs& a) {
-  constexpr bool XS = X6;                        // 16-bit split-form A planes
-  constexpr int APL = 3;                         // A / pre-split B planes
-  constexpr int NWV = WM * WN;                   // waves (4, or 8 for the 128-row tiles)
-  constexpr int MT = BMT / WM / 16;
-  constexpr int NT = BN / WN / 16;
-  constexpr int KCH = 32;                        // input channels per k-step
-  constexpr int NCH = CI / KCH;
-  static_assert(!W6 || (X6 && EPI == EPI_QUANT), "pre-split weights: x6 conv3");
-  constexpr int SA = XS ? APL * BMT * KCH / 2 : BMT * KCH;   // A image floats per stage
-  constexpr int SB = W6 ? APL * 4 * BN * 8 / 2   // W6: [3][4][BN][8] bf16
-                        : KCH * BN;              // B image floats per stage: [8 quads][BN][4]
-  constexpr int STAGE = SA + SB;
-  constexpr int NAI = SA * 4 / 1024;             // A glds wave-instructions per step (8 | 12)
-  constexpr int NBI = SB * 4 / 1024;             // B glds wave-instructions per step
-  constexpr int AI_W = NAI / NWV;                // per wave
-  constexpr int BI_W = (NBI + NWV - 1) / NWV;
-  constexpr int API = BMT / 16;                  // x6: A wave-instructions per plane (16 rows each)
-  // DMA ring depth: conv3 (+ quantiser) has a third of conv2's MFMAs per step, too few to hide
-  // an L2-miss DMA issued one step ahead, so it runs NS stages with a counted vmcnt wait.
-  // x6 IGDN layers (deconv1 / deconv2): halo-patch A operand (see the main loop)
-  constexpr bool HALO = X6 && EPI == EPI_IGDN && BMT == BM;
-  // per-tap two-level accumulation for the encoder layers whose latents are rounded (conv2+GDN2,
-  // conv3+quantiser): their accuracy decides the ŷ flips against the reference
-  constexpr bool TAPSEP = kSepAcc && !HALO && (EPI == EPI_GDN || EPI == EPI_QUANT);
-  constexpr int HALO_NI = (3 * 100 * 64 + 1023) / 1024;   // patch DMA wave-instructions (19)
-  constexpr int HALO_PF = HALO_NI * 256;                  // patch floats
-  constexpr int LDS_A = HALO ? HALO_PF + 2 * SB
-                             : 2 * STAGE;   // two-stage ring (3, 4 stages measured slower: DESIGN.md §5)
-  constexpr int LDS_XF = BMT * (CO + 8) + GSTAGE_FLOATS(CO);
-  constexpr int LDS_XP = gdn_lds_floats(BMT, CO, XS);
-  constexpr int LDS_X = (EPI == EPI_GDN || EPI == EPI_IGDN) ? (LDS_XF > LDS_XP ? LDS_XF : LDS_XP)
-                        : (EPI == EPI_GDN_BWD || EPI == EPI_IGDN_BWD) ? LDS_XF : 0;
-  constexpr int LDS_O = BMT * (BN + 4) + 8;
-  constexpr int LDS_3 = 3 * 32 * 33 + 8;
-  constexpr int L1 = LDS_A > LDS_X ? LDS_A : LDS_X;
-  constexpr int L2 = LDS_O > LDS_3 ? LDS_O : LDS_3;
-  constexpr int LDS_FLOATS = L1 > L2 ? L1 : L2;
-  static_assert(MT * WM * 16 == BMT && NT * WN * 16 == BN, "tile shape");
-  static_assert(BMT == BM || (X6 && (EPI == EPI_GDN || EPI == EPI_IGDN) && NWV == 8),
-                "128-row tiles: the x6 GDN / IGDN layers on 8 waves");
-  static_assert(NWV == 4 || NWV == 8, "4 or 8 waves");
-  static_assert(CI % KCH == 0 && NAI % NWV == 0, "k-step split");
-  static_assert(BN == CO || BN % 16 == 0, "B image: quad rows of BN columns");
-  static_assert((SB * 4) % 1024 == 0, "B image in whole wave-instructions");
-  __shared__ __attribute__((aligned(16))) float smem[LDS_FLOATS];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform (scalar branches)
-  const int wm = wave / WN, wn = wave % WN;
-  TileInfo t = decode_tile<BMT / 8>(a);
-  const int ph = t.py * a.tt.npx + t.px;
-  const int ncol0 = t.nb * BN + wn * (BN / WN);
-
-  // A DMA. fp32: wave-instruction i covers rows 8i .. 8i+7; lane → (row, physical chunk
-  // lane & 7), fetching logical chunk (lane & 7) ^ (row & 7). X6: instruction i covers plane
-  // i >> 2, rows 16(i & 3) .. +15; lane → (row, physical piece lane & 3), fetching logical piece
-  // (lane & 3) ^ ((row >> 1) & 3) (8 bf16 channels).
-  int iy0[AI_W], ix0[AI_W], pbase[AI_W];
-  bool rval[AI_W];
-#pragma unroll
-  for (int j = 0; j < AI_W; ++j) {
-    const int i = wave * AI_W + j;
-    const int row = XS ? 16 * (i % API) + (lane >> 2) : i * 8 + (lane >> 3);
-    const int c = XS ? (lane & 3) ^ ((row >> 1) & 3) : (lane & 7) ^ (row & 7);
-    const int gy = t.ty * (BMT / 8) + (row >> 3), gx = t.tx * 8 + (row & 7);
-    rval[j] = gy < a.gh && gx < a.gw;
-    iy0[j] = gy * a.sin;
-    ix0[j] = gx * a.sin;
-    pbase[j] = (iy0[j] * a.Win + ix0[j]) * CI + c * (XS ? 8 : 4);
-  }
-  const long img = (long)t.b * a.Hin * a.Win * CI;
-  const float* __restrict__ inb = a.in + img;
-  const unsigned short* __restrict__ inb6 = a.in_split + img;
-  // B DMA: wave-instruction i copies 1 KB; source offset (floats) within the step's slice
-  int bsrc[BI_W];
-#pragma unroll
-  for (int j = 0; j < BI_W; ++j) {
-    const int i = wave + NWV * j;
-    if constexpr (W6) {   // u16 offset in the pre-split planes: (plane, k-group, column) of the slot
-      const int o2 = i * 512 + lane * 8;   // u16 offset in the LDS image [3][4][BN][8]
-      const int pl = o2 / (32 * BN), r = o2 - pl * 32 * BN;
-      const int gg = r / (BN * 8), col = (r - gg * BN * 8) / 8;
-      bsrc[j] = (int)(pl * a.w6_plane) + (gg * CO + t.nb * BN + col) * 8;
-    } else {
-      const int o = i * 256 + lane * 4;   // offset in the LDS image [8 quads][BN][4]
-      bsrc[j] = (BN == CO) ? o : ((o / (BN * 4)) * CO + t.nb * BN) * 4 + o % (BN * 4);
-    }
-  }
-
-  int t0 = 0, ntaps = 1;
-  // Step order: tap-major (the 6 channel chunks of a tap in a row). Chunk-major order keeps a
-  // workgroup's input footprint to one chunk and cuts the HBM refetch 3-5x, but measured 3-6 %
-  // slower on the same box: these layers are bound by MFMA issue, and the
-  // Infinity Cache absorbs the L2 misses.
-  auto issue = [&](int s, int buf) {
-    const int tap = t0 + s / NCH, cc = s - (s / NCH) * NCH;
-    const int td = a.tt.dydx[tap];
-    const int dy = (td & 0xff) - 128, dx = ((td >> 8) & 0xff) - 128;
-    const int so = (dy * a.Win + dx) * CI + cc * KCH;
-    float* sa = smem + buf * STAGE;
-#pragma unroll
-    for (int j = 0; j < AI_W; ++j) {
-      const bool ok = rval[j] && (unsigned)(iy0[j] + dy) < (unsigned)a.Hin &&
-                      (unsigned)(ix0[j] + dx) < (unsigned)a.Win;
-      const int i = wave * AI_W + j;
-      if constexpr (XS) {
-        const unsigned short* src = inb6 + (i / API) * a.in_plane + pbase[j] + so;
-        glds16(ok ? (const float*)src : g_zero16, sa + i * 256);
-      } else {
-        glds16(ok ? inb + pbase[j] + so : g_zero16, sa + i * 256);
-      }
-    }
-    float* sb = sa + SA;
-    if constexpr (W6) {
-      const unsigned short* __restrict__ ws6 = a.w6 + ((long)tap * (CI / 8) + cc * 4) * CO * 8;
-#pragma unroll
-      for (int j = 0; j < BI_W; ++j) {
-        const int i = wave + NWV * j;
-        if (NBI % NWV == 0 || i < NBI) glds16((const float*)(ws6 + bsrc[j]), sb + i * 256);
-      }
-    } else {
-      const float* __restrict__ ws = a.w + ((long)tap * CI + cc * KCH) * CO;   // uniform base
-#pragma unroll
-      for (int j = 0; j < BI_W; ++j) {
-        const int i = wave + NWV * j;
-        if (NBI % NWV == 0 || i < NBI) glds16(ws + bsrc[j], sb + i * 256);
-      }
-    }
-  };
-
-  f4 acc[MT][NT];
-  // fragment read offsets (floats) within a stage
-  int aoff[2][MT];
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int row = wm * MT * 16 + mt * 16 + (lane & 15);
-      aoff[kk][mt] = row * KCH + (((kk * 4 + (lane >> 4)) ^ (row & 7)) * 4);
-    }
-  const int boff0 = ((lane >> 4) * BN + wn * (BN / WN) + (lane & 15)) * 4;
-
-  // X6 fragment offsets: A piece (bf16 elements) per mt; B quads 2g, 2g+1 (floats)
-  int aoff6[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int row = wm * MT * 16 + mt * 16 + (lane & 15);
-    aoff6[mt] = (row * 4 + ((lane >> 4) ^ ((row >> 1) & 3))) * 8;
-  }
-  const int boff6 = (2 * (lane >> 4) * BN + wn * (BN / WN) + (lane & 15)) * 4;
-
-  auto compute6 = [&](int buf) {
-    X6Acc st;
-    const unsigned short* sa = (const unsigned short*)(smem + buf * STAGE);
-    const float* sb = smem + buf * STAGE + SA + boff6;
-    bf8 Bh[NT], Bm[NT], Bl[NT];
-    if constexpr (W6) {   // [3][4][BN][8]: lane (k-group lane >> 4, column) reads 16 bytes per plane
-      const unsigned short* sb6 = (const unsigned short*)(smem + buf * STAGE + SA) +
-                                  ((lane >> 4) * BN + wn * (BN / WN) + (lane & 15)) * 8;
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        Bh[nt] = __builtin_bit_cast(bf8, *(const u4*)(sb6 + nt * 128));
-        Bm[nt] = __builtin_bit_cast(bf8, *(const u4*)(sb6 + 32 * BN + nt * 128));
-        Bl[nt] = __builtin_bit_cast(bf8, *(const u4*)(sb6 + 64 * BN + nt * 128));
-      }
-    } else {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      u4 bh, bm, bl;
-      split8(*(const f4*)(sb + nt * 64), *(const f4*)(sb + BN * 4 + nt * 64), bh, bm, bl);
-      Bh[nt] = __builtin_bit_cast(bf8, bh);
-      Bm[nt] = __builtin_bit_cast(bf8, bm);
-      Bl[nt] = __builtin_bit_cast(bf8, bl);
-    }
-    }
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const bf8 Ah = __builtin_bit_cast(bf8, *(const u4*)(sa + aoff6[mt]));
-      const bf8 Am = __builtin_bit_cast(bf8, *(const u4*)(sa + BMT * KCH + aoff6[mt]));
-      const bf8 Al = __builtin_bit_cast(bf8, *(const u4*)(sa + 2 * BMT * KCH + aoff6[mt]));
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        mfma_x6<false>(acc, st, mt, nt, Ah, Am, Al, Bh[nt], Bm[nt], Bl[nt]);
-      }
-    }
-    x6_flush<false>(acc, st);
-  };
-
-  auto compute = [&](int buf) {
-    if constexpr (X6) {
-      compute6(buf);
-      return;
-    }
-    const float* sa = smem + buf * STAGE;
-    const float* sb = sa + SA + boff0;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      f4 af[MT], bf[NT];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) bf[nt] = *(const f4*)(sb + kk * 16 * BN + nt * 64);
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) af[mt] = *(const f4*)(sa + aoff[kk][mt]);
-      mfma_block<MT, NT>(acc, af, bf);
-    }
-  };
-
-  t0 = a.tt.begin[ph];
-  ntaps = a.tt.begin[ph + 1] - t0;
-  const int nsteps = ntaps * NCH;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-
-  if constexpr (HALO) {
-    // x6 deconv (IGDN layers, input stride 1, taps dy, dx ∈ {−1, 0, 1}): chunk-major steps. The
-    // 10×10 input patch of the 8×8 base tile (three bf16 planes, 64 bytes per pixel, 19 KB) is
-    // staged ONCE per 32-channel chunk and every tap reads its shifted window from it, instead
-    // of each (tap, chunk) step DMA-ing its own 64 rows again (100 vs 64·taps staged pixels).
-    // The patch is single-buffered (the chunk boundary is a barrier-bounded refill that the
-    // co-resident workgroup covers); the weight stages stay double-buffered. 16-byte piece g of
-    // patch pixel q sits at g ^ 2·((q / 10) & 1): conflict-free ds_read_b128 lane groups for every
-    // tap offset (checked exhaustively).
-    unsigned short* const sp = (unsigned short*)smem;
-    float* const sbw = smem + HALO_PF;
-    const int gy0 = t.ty * 8 - 1, gx0 = t.tx * 8 - 1;   // patch origin (input coordinates)
-    auto issue_patch = [&](int cc) {
-#pragma unroll
-      for (int j = 0; j < (HALO_NI + 3) / 4; ++j) {
-        const int i = wave + 4 * j;
-        if (i >= HALO_NI) break;   // wave-uniform
-        const int qq = 16 * i + (lane >> 2);            // plane · 100 + patch pixel
-        const int pl = qq / 100, q = qq - pl * 100;
-        const int iy = gy0 + q / 10, ix = gx0 + q % 10;
-        const bool ok = pl < 3 && (unsigned)iy < (unsigned)a.Hin && (unsigned)ix < (unsigned)a.Win;
-        const int g = (lane & 3) ^ (2 * ((q / 10) & 1));
-        const unsigned short* src =
-            inb6 + (long)(pl < 3 ? pl : 0) * a.in_plane + ((long)iy * a.Win + ix) * CI + cc * KCH + g * 8;
-        glds16(ok ? (const float*)src : g_zero16, (float*)sp + i * 256);
-      }
-    };
-    auto issue_b = [&](int s, int buf) {   // weights of step s = (chunk, tap) into stage buf
-      const int cc = s / ntaps, tap = t0 + (s - cc * ntaps);
-      float* sb = sbw + buf * SB;
-      const float* __restrict__ ws = a.w + ((long)tap * CI + cc * KCH) * CO;
-#pragma unroll
-      for (int j = 0; j < BI_W; ++j) {
-        const int i = wave + NWV * j;
-        if (NBI % NWV == 0 || i < NBI) glds16(ws + bsrc[j], sb + i * 256);
-      }
-    };
-    // tile pixel of fragment row mt: (ty, tx) = (r >> 3, r & 7); patch pixel at tap (0, 0)
-    int hq[MT], hy[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int r = wm * MT * 16 + mt * 16 + (lane & 15);
-      hy[mt] = (r >> 3) + 1;
-      hq[mt] = hy[mt] * 10 + (r & 7) + 1;
-    }
-    auto compute_halo = [&](int buf, int dy, int dx) {
-      X6Acc st;
-      const float* sb = sbw + buf * SB + boff6;
-      bf8 Bh[NT], Bm[NT], Bl[NT];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        u4 bh, bm, bl;
-        split8(*(const f4*)(sb + nt * 64), *(const f4*)(sb + BN * 4 + nt * 64), bh, bm, bl);
-        Bh[nt] = __builtin_bit_cast(bf8, bh);
-        Bm[nt] = __builtin_bit_cast(bf8, bm);
-        Bl[nt] = __builtin_bit_cast(bf8, bl);
-      }
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const int q = hq[mt] + dy * 10 + dx;
-        const int g = (lane >> 4) ^ (2 * ((hy[mt] + dy) & 1));
-        const unsigned short* pa = sp + q * 32 + g * 8;
-        const bf8 Ah = __builtin_bit_cast(bf8, *(const u4*)(pa));
-        const bf8 Am = __builtin_bit_cast(bf8, *(const u4*)(pa + 100 * 32));
-        const bf8 Al = __builtin_bit_cast(bf8, *(const u4*)(pa + 200 * 32));
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-          mfma_x6<false>(acc, st, mt, nt, Ah, Am, Al, Bh[nt], Bm[nt], Bl[nt]);
-        }
-      }
-      x6_flush<false>(acc, st);
-    };
-    issue_patch(0);
-    issue_b(0, 0);
-    for (int cc = 0; cc < NCH; ++cc) {
-      for (int k = 0; k < ntaps; ++k) {
-        const int s = cc * ntaps + k;
-        dma_barrier();   // weights of step s landed (and, at k = 0, chunk cc's patch)
-        if (k + 1 < ntaps) issue_b(s + 1, (s + 1) & 1);
-        const int td = a.tt.dydx[t0 + k];
-        compute_halo(s & 1, (td & 0xff) - 128, ((td >> 8) & 0xff) - 128);
-        if (k + 1 == ntaps && cc + 1 < NCH) {
-          __syncthreads();   // every wave is done with this chunk's patch
-          issue_patch(cc + 1);
-          issue_b(s + 1, (s + 1) & 1);
-        }
-      }
-    }
-  } else {
-    issue(0, 0);
-    if constexpr (TAPSEP) {
-      // two-level accumulation (common.h): each tap's NCH steps accumulate in
-      // place from zero, and the tap sum is added to `total` with one correctly rounded add
-      static_assert(NCH % 2 == 0, "stage parity = chunk parity");
-      f4 total[MT][NT];
-      zero_tile<MT, NT>(total);
-      for (int tp = 0; tp < ntaps; ++tp) {
-        zero_tile<MT, NT>(acc);
-#pragma unroll
-        for (int cc = 0; cc < NCH; ++cc) {
-          const int s = tp * NCH + cc;
-          dma_barrier();   // step s landed for every wave; stage (s+1)&1 is free
-          if (s + 1 < nsteps) issue(s + 1, (cc + 1) & 1);
-          compute(cc & 1);
-        }
-        add_tile<MT, NT>(total, acc);
-      }
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = total[mt][nt];
-    } else {
-      for (int s = 0; s < nsteps; ++s) {
-        dma_barrier();   // step s landed for every wave; stage (s+1)&1 is free
-        if (s + 1 < nsteps) issue(s + 1, (s + 1) & 1);
-        compute(s & 1);
-      }
-    }
-  }
-  __syncthreads();     // last stage reads done before the epilogue reuses LDS
-
-  if constexpr (EPI == EPI_GDN || EPI == EPI_IGDN) {
-    static_assert(BN == CO, "GDN fusion needs every channel of a pixel in the workgroup");
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[mt][nt][r] += a.bias[ncol0 + nt * 16 + (lane & 15)];
-    gdn_epilogue<CO, MT, NT, EPI == EPI_IGDN, BMT, NWV * 64, XS>(acc, smem, a, t, wm, ncol0,
-                                                                lane);
-  } else if constexpr (EPI == EPI_QUANT) {
-    quant_epilogue<CO, BN, MT, NT, WN>(acc, smem, a, t, wm, ncol0, lane, wave);
-  } else if constexpr (EPI == EPI_OUT3) {
-    out3_epilogue<MT, NT>(acc, smem, a, t, wm, lane, wave);
-  } else if constexpr (EPI == EPI_GDN_BWD || EPI == EPI_IGDN_BWD) {
-    static_assert(BN == CO, "GDN backward needs every channel of a pixel in the workgroup");
-    gdn_bwd_epilogue<CO, MT, NT, EPI == EPI_IGDN_BWD>(acc, smem, a, t, wm, ncol0, lane);
-  } else if constexpr (EPI == EPI_RATE_BWD) {
-    rate_bwd_epilogue<CO, BN, MT, NT>(acc, smem, a, t, wm, ncol0, lane);
-  } else {
-    constexpr int OS = BN + 4;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = wm * MT * 16 + mt * 16 + 4 * (lane >> 4) + r;
-          const int lcol = wn * (BN / WN) + nt * 16 + (lane & 15);
-          float v = acc[mt][nt][r];
-          if (a.bias != nullptr) v += a.bias[t.nb * BN + lcol];
-          smem[row * OS + lcol] = v;
-        }
-    __syncthreads();
-    store_tile_rows<BN>(a, t, smem, OS, a.out, CO, t.nb * BN);
-  }
-}
-
-template <int CI, int CO, int BN, int WM, int WN, int EPI, bool X6 = false, bool W6 = false>
-__global__ void __launch_bounds__(256) engine_kernel(const EngineArgs a) {
-  engine_body<CI, CO, BN, WM, WN, EPI, X6, BM, W6>(a);
-}
-
-// The same kernel held to 256 VGPRs (2 waves per SIMD) where the compiler would otherwise just
-// exceed it (the x6 GDN / IGDN backward instances).
-template <int CI, int CO, int BN, int WM, int WN, int EPI, bool X6 = false>
-__global__ void __launch_bounds__(256, 2) engine_kernel_occ2(const EngineArgs a) {
-  engine_body<CI, CO, BN, WM, WN, EPI, X6>(a);
-}
-
-// --------------------------------------------------------------- deconv3, x6 halo kernel
-// synthesis_17.py:23 deconv3 (ConvTranspose2d(N, 3, 9, s4, p4, op3)) + model.py:59 clamp, on the
-// x6 activation format. The all-phase GEMM of the engine (M = base pixels, N = 48 = 3 channels ×
-// 16 output phases, K = 9 taps × CI) with two changes that cut the bytes staged per MFMA:
-//   - a 16×16 base block per workgroup (M = 256; each wave 64 rows = 4 base rows × 16), so one
-//     6 KB weight stage feeds 4× the pixels of the 8×8 engine tile;
-//   - per 32-channel chunk, the 18×18 input patch (the block plus its 3×3 halo) is staged ONCE
-//     in LDS (three bf16 planes, 62 KB) and the 9 taps read shifted windows of it, instead of
-//     DMA-ing each tap's 64 rows again (324 vs 9·256 staged pixels).
-// Patch layout: slot = plane·324 + p (p = r·18 + c), 64 bytes per slot; 16-byte piece g of slot
-// p sits at g ^ 2·((p >> 2) & 1), conflict-free for ds_read_b128 lane groups at every window
-// offset (checked exhaustively). One A stage (single-buffered: the chunk boundary is a
-// barrier-bounded refill the co-resident workgroup covers) + two 6 KB B stages = 73 KB, two
-// workgroups per CU. Epilogue: bias, clamp, 64×64 output block through LDS, per-8×8-quadrant SSE
-// partials in the engine's partial layout (iclr17_output_partials_per_image).
-constexpr int D3_BS = 16;                       // base block side
-constexpr int D3_PS = D3_BS + 2;                // patch side
-constexpr int D3_PPX = D3_PS * D3_PS;           // 324 patch pixels per plane
-constexpr int D3_NAI = (3 * D3_PPX + 15) / 16;  // 61 A wave-instructions per chunk
-constexpr int D3_SA = D3_NAI * 256;             // A stage floats (976 slots × 16)
-constexpr int D3_SB6 = 3 * 32 * 48 / 2;         // x6 B stage floats: [3 planes][4 k8][48][8] u16
-constexpr int D3_LDS = D3_SA + 2 * D3_SB6;      // 80,896 B: two workgroups per CU
-// deconv3 epilogue tile [3][64][64] fp32 (channel, output row, output column): row stride D3_ES,
-// channel stride D3_EC floats. A write instruction's 16 lanes of a group hold 16 (channel, ry, rx)
-// columns of one base pixel (d3_col order) and the lane groups base columns 16 floats apart; the
-// earlier [3][64][65] tile put those columns on ≈5 banks (6.7 LDS cycles per 32-lane group, 88 %
-// of the kernel's bank-conflict cycles); rows of 67 and channels of 64·67 + 11 floats spread them
-// (1.7 cycles, the best of the strides 64..99 × 64·stride + 0..39), and the store phase's reads
-// (8 columns × 4 rows per group) stay conflict-free.
-constexpr int D3_ES = 67, D3_EC = 64 * D3_ES + 11;
-
-// first weight block (tile-tap) of tap t in the compact per-chunk weight stage: taps 0-2 touch
-// one column tile, taps 3 and 6 two, the others three (see d3_col)
-__host__ __device__ constexpr int d3_boff(int t) {
-  return t <= 3 ? t : (t == 4 ? 5 : (t == 5 ? 8 : (t == 6 ? 11 : (t == 7 ? 13 : (t == 8 ? 16 : 19)))));
-}
-
-// Column order of the in-loop-split path: logical column j (tile j / 16, lane j % 16) reads packed
-// column co·16 + ry·4 + rx, taking first the 12 columns with ry = 0, then the 9 with rx = 0 < ry,
-// then the rest, each (ry, rx, co)-lexicographic. A tap with dy = −1 feeds only phase ry = 0 and
-// one with dx = −1 only rx = 0 (the packed weights are zero elsewhere), so with this order the
-// three dy = −1 taps need tile 0 alone and the two other dx = −1 taps tiles 0–1: 19 tile-taps
-// per chunk instead of 27. The skipped products are exact zeros, so results are unchanged.
-__device__ __forceinline__ int d3_col(int j) {
-  int ry, rx, co;
-  if (j < 12) {          // ry = 0
-    ry = 0; rx = j / 3; co = j % 3;
-  } else if (j < 21) {   // rx = 0 < ry
-    ry = 1 + (j - 12) / 3; rx = 0; co = (j - 12) % 3;
-  } else {
-    const int k = j - 21;
-    ry = 1 + k / 9; rx = 1 + (k / 3) % 3; co = k % 3;
-  }
-  return co * 16 + ry * 4 + rx;
-}
-
-// H3: the input in the h3 form (two fp16 planes, chunk-major from the h3 deconv2) and the
-// weights as iclr17_split_packed_h3's two planes; three v_mfma_f32_16x16x32_f16 per tile and tap
-// (lo_a·hi_w, hi_a·lo_w, hi_a·(hi_w·2¹¹)) instead of six bf16 ones, scaled back exactly before
-// the bias. Two thirds of the x6 stage bytes per step (41 A and 6 / 4 B pieces).
-template <int CI, bool H3 = false>
-__global__ void __launch_bounds__(256, 2) deconv3_x6_kernel(const EngineArgs a) {
-  constexpr int KCH = 32, NCH = CI / KCH;
-  constexpr int MT = 4, NT = 3;
-  constexpr int NPL = H3 ? 2 : 3;                         // input (and weight) planes
-  // A wave-instructions per chunk (x6: 61; h3: 41, rounded up to whole rounds of the 4 waves:
-  // the 41-piece form hit a compiler fault, "Operand has incorrect register class"; the three
-  // padding pieces load the zero line)
-  constexpr int NAI = H3 ? ((NPL * D3_PPX + 15) / 16 + 3) / 4 * 4 : (NPL * D3_PPX + 15) / 16;
-  constexpr int AI_W = (NAI + 3) / 4;   // x6: 16 (wave 0..3 takes i = w + 4j, i < 61)
-  static_assert(3 * D3_EC <= D3_LDS, "epilogue block fits the stages");
-  __shared__ __attribute__((aligned(16))) float smem[D3_LDS];
-  // H3: the range flag of the chain (set by an upstream h3 kernel whose output did not fit the
-  // form, |x| ≥ 2²²) makes every result of this last kernel NaN — the reconstruction, the SSE
-  // partials and the folded bit totals — so an out-of-range input can never pass for a result.
-  // The upstream kernels all completed before this launch, so the flag is final here.
-  const bool poison = H3 && a.range != nullptr && *(const volatile int*)a.range != 0;
-  if (a.fold_partial != nullptr && blockIdx.x == 0) fold_bits<256>(a, (double*)smem, poison);
-  float* const sA = smem;
-  float* const sB = smem + D3_SA;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int bid = blockIdx.x;
-  const int tx = bid % a.tiles_x;
-  bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int b = bid / a.tiles_y;
-
-  // A DMA sources: per instruction j of this wave, slot q = 16i + lane/4 (plane, patch pixel),
-  // physical piece lane & 3 ← logical piece (lane & 3) ^ swizzle(p). -1: zero line.
-  int asrc[AI_W];
-#pragma unroll
-  for (int j = 0; j < AI_W; ++j) {
-    const int i = wave + 4 * j;
-    const int q = i * 16 + (lane >> 2);
-    const int pl = q / D3_PPX, p = q - pl * D3_PPX;
-    const int r = p / D3_PS, c = p - r * D3_PS;
-    const int iy = ty * D3_BS - 1 + r, ix = tx * D3_BS - 1 + c;
-    const bool ok = i < NAI && pl < NPL && (unsigned)iy < (unsigned)a.Hin &&
-                    (unsigned)ix < (unsigned)a.Win;
-    const int g = (lane & 3) ^ (((p >> 2) & 1) << 1);
-    // pixel stride: CI (NHWC planes) or 32 (chunk-major planes, a.in_cm)
-    asrc[j] = ok ? (iy * a.Win + ix) * (a.in_cm ? KCH : CI) + g * 8 : -1;
-  }
-  const unsigned short* __restrict__ inb = a.in_split + (long)b * a.Hin * a.Win * CI;
-  const long cstride = a.in_cm ? (long)a.Hin * a.Win * KCH : KCH;   // chunk stride (elements)
-  auto issue_a = [&](int cc) {
-#pragma unroll
-    for (int j = 0; j < AI_W; ++j) {
-      const int i = wave + 4 * j;
-      if (i < NAI) {
-        const int q = i * 16 + (lane >> 2);
-        const int pl = q / D3_PPX;
-        const unsigned short* src = inb + (long)(pl < NPL ? pl : 0) * a.in_plane + asrc[j] + cc * cstride;
-        glds16(asrc[j] >= 0 ? (const float*)src : g_zero16, sA + i * 256);
-      }
-    }
-  };
-  // B DMA: the weights arrive pre-split (iclr17_split_packed of the ICLR17_W_DECONV9 packing:
-  // [3][9][CI/8][48][8] bf16), so no wave splits them in the loop. A tap stages only the column
-  // tiles it touches (the others hold exact zeros for it, see d3_col): tap t's block is
-  // [plane 3][k8 4][16·ntt(t)][8], slot = logical column (the d3_col order the fragment reads
-  // walk), so a 16-lane group reads 16 consecutive 16-byte slots (conflict-free). The three
-  // one-tile taps (dy = −1) share one step: 7 steps of 9 / 6 / 9 / 9 / 6 / 9 / 9 KB per chunk
-  // instead of 9 of 9 KB, 57 DMA pieces instead of 81 and 7 barriers instead of 9.
-  const unsigned short* __restrict__ w6 = (const unsigned short*)a.w;
-  constexpr long WPL = 9L * CI * 48;   // u16 per weight plane
-  // taps of step st: st = 0 → taps 0, 1, 2; else tap st + 2
-  auto issue_b = [&](int cc, int st, int buf) {
-    float* sb = sB + buf * D3_SB6;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int piece = wave + 4 * k;
-      if (piece >= 3 * NPL || ((st == 1 || st == 4) && piece >= 2 * NPL)) break;   // wave-uniform
-      const int slot = piece * 64 + lane;
-      int tap, pl, k8, col;
-      if (st == 0) {
-        tap = slot / (64 * NPL);
-        const int r = slot - tap * 64 * NPL;
-        pl = r / 64; k8 = (r >> 4) & 3; col = r & 15;
-      } else {
-        tap = st + 2;
-        const int nc = st == 1 || st == 4 ? 32 : 48;   // 16·ntt
-        pl = slot / (4 * nc);
-        const int r = slot - pl * 4 * nc;
-        k8 = r / nc; col = r - k8 * nc;
-      }
-      const unsigned short* src =
-          w6 + pl * WPL + (((long)tap * (CI / 8) + cc * 4 + k8) * 48 + d3_col(col)) * 8;
-      glds16((const float*)src, sb + piece * 256);
-    }
-  };
-
-  f4 acc[MT][NT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-  const int g = lane >> 4;
-  const int prow = (4 * wave + 1) * D3_PS + 1 + (lane & 15);   // window origin for mt = 0
-  int pcol[NT];   // packed column of this lane in tile nt
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-    pcol[nt] = d3_col(nt * 16 + (lane & 15));
-
-  // tap `tap` from its block at u16 offset `boff` of stage buf: [plane][k8][16·NTT][8]
-  auto compute = [&](int buf, int tap, int boff, auto ntt) {
-    X6Acc st;
-    constexpr int NTT = decltype(ntt)::value;   // tiles this tap touches
-    constexpr int NC = 16 * NTT;
-    const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-    const unsigned short* sb = (const unsigned short*)(sB + buf * D3_SB6) + boff + g * NC * 8;
-    if constexpr (H3) {
-      u4 Bh[NTT], Bl[NTT], Bh11[NTT];
-#pragma unroll
-      for (int nt = 0; nt < NTT; ++nt) {
-        const int jc = nt * 16 + (lane & 15);
-        Bh[nt] = *(const u4*)(sb + jc * 8);
-        Bl[nt] = *(const u4*)(sb + 4 * NC * 8 + jc * 8);
-        Bh11[nt] = h3_x2048(Bh[nt]);
-      }
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const int p = prow + (mt + dy) * D3_PS + dx;
-        const unsigned short* sa =
-            (const unsigned short*)(sA + p * 16 + ((g ^ (((p >> 2) & 1) << 1)) * 4));
-        const h8v Ah = __builtin_bit_cast(h8v, *(const u4*)(sa));
-        const h8v Al = __builtin_bit_cast(h8v, *(const u4*)(sa + D3_PPX * 32));
-#pragma unroll
-        for (int nt = 0; nt < NTT; ++nt) {
-          f4 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, __builtin_bit_cast(h8v, Bh[nt]), acc[mt][nt], 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, __builtin_bit_cast(h8v, Bl[nt]), c, 0, 0, 0);
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, __builtin_bit_cast(h8v, Bh11[nt]), c, 0, 0, 0);
-        }
-      }
-    } else {
-    bf8 Bh[NTT], Bm[NTT], Bl[NTT];
-#pragma unroll
-    for (int nt = 0; nt < NTT; ++nt) {
-      const int jc = nt * 16 + (lane & 15);
-      Bh[nt] = __builtin_bit_cast(bf8, *(const u4*)(sb + jc * 8));
-      Bm[nt] = __builtin_bit_cast(bf8, *(const u4*)(sb + 4 * NC * 8 + jc * 8));
-      Bl[nt] = __builtin_bit_cast(bf8, *(const u4*)(sb + 8 * NC * 8 + jc * 8));
-    }
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int p = prow + (mt + dy) * D3_PS + dx;
-      const unsigned short* sa =
-          (const unsigned short*)(sA + p * 16 + ((g ^ (((p >> 2) & 1) << 1)) * 4));
-      const bf8 Ah = __builtin_bit_cast(bf8, *(const u4*)(sa));
-      const bf8 Am = __builtin_bit_cast(bf8, *(const u4*)(sa + D3_PPX * 32));
-      const bf8 Al = __builtin_bit_cast(bf8, *(const u4*)(sa + 2 * D3_PPX * 32));
-#pragma unroll
-      for (int nt = 0; nt < NTT; ++nt) {
-        mfma_x6<false>(acc, st, mt, nt, Ah, Am, Al, Bh[nt], Bm[nt], Bl[nt]);
-      }
-    }
-    x6_flush<false>(acc, st);
-    }
-  };
-
-  issue_a(0);
-  issue_b(0, 0, 0);
-  // steps unrolled inside the chunk loop: each tap's code is specialised (no joins between the
-  // three tile counts, whose register shuffles cost more VALU than the split itself). The
-  // accumulation order (chunk, tap 0..8) is that of the per-tap schedule.
-  for (int cc = 0; cc < NCH; ++cc) {
-#pragma unroll
-    for (int st = 0; st < 7; ++st) {
-      const int s = cc * 7 + st;
-      dma_barrier();   // A (at a chunk start) and B of step s landed
-      if (st != 6) issue_b(cc, st + 1, (s + 1) & 1);
-      if (st == 0) {
-        compute(s & 1, 0, 0, std::integral_constant<int, 1>{});
-        compute(s & 1, 1, 64 * NPL * 8, std::integral_constant<int, 1>{});
-        compute(s & 1, 2, 2 * 64 * NPL * 8, std::integral_constant<int, 1>{});
-      } else if (st == 1 || st == 4) {
-        compute(s & 1, st + 2, 0, std::integral_constant<int, 2>{});
-      } else {
-        compute(s & 1, st + 2, 0, std::integral_constant<int, 3>{});
-      }
-      if (st == 6 && cc + 1 < NCH) {
-        __syncthreads();   // every wave is done with this chunk's patch
-        issue_a(cc + 1);
-        issue_b(cc + 1, 0, (s + 1) & 1);
-      }
-    }
-  }
-  __syncthreads();     // stage reads done before the epilogue reuses LDS
-  if constexpr (H3) {   // 2¹¹·σ_a·σ_w off, exactly
-    const float dsc = a.wscale[1];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = acc[mt][nt] * dsc;
-  }
-
-  // epilogue: column n = co·16 + ry·4 + rx of row m = (by, bx) → output (4by + ry, 4bx + rx)
-  constexpr int OS = 4 * D3_BS;
-  float* sO = smem;   // [3][64][64], strides D3_EC / D3_ES
-  const int H = a.Hout, W = a.Wout;
-  float sse = 0.f;
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 1 && a.recon == nullptr) break;
-    float* dst = pass == 0 ? a.out : a.recon;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int by = 4 * wave + mt, bx = 4 * g + r;
-          const int co = pcol[nt] >> 4, ph = pcol[nt] & 15;
-          float v = acc[mt][nt][r] + a.bias[co];
-          if (pass == 0) v = fminf(fmaxf(v, 0.0f), 1.0f);
-          if (poison) v = __builtin_nanf("");
-          sO[co * D3_EC + (by * 4 + (ph >> 2)) * D3_ES + bx * 4 + (ph & 3)] = v;
-        }
-    __syncthreads();
-    // wave w stores output quadrant (qy, qx) = (w >> 1, w & 1): 3 × 32 rows × 8 float4
-    const int qy = wave >> 1, qx = wave & 1;
-    const bool sse_pass = pass == (a.sse_unclipped ? 1 : 0) && a.xref != nullptr;
-    for (int k = lane; k < 3 * 32 * 8; k += 64) {
-      const int c4 = k & 7, row = (k >> 3) & 31, co = k >> 8;
-      const int oyl = qy * 32 + row, oxl = qx * 32 + c4 * 4;
-      const int oy = ty * OS + oyl, ox = tx * OS + oxl;
-      if (oy >= H || ox >= W) continue;
-      const float* sp = sO + co * D3_EC + oyl * D3_ES + oxl;
-      const f4 v = f4{sp[0], sp[1], sp[2], sp[3]};
-      const long off = (((long)b * 3 + co) * H + oy) * W + ox;
-      *(f4*)(dst + off) = v;
-      if (sse_pass) {
-        const f4 xr = *(const f4*)(a.xref + off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = v[e] - xr[e];
-          sse += d * d;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (a.xref != nullptr) {
-    sse = wave_sum(sse);
-    const int ty8 = 2 * ty + (wave >> 1), tx8 = 2 * tx + (wave & 1);
-    const int tiles_x8 = (a.gw + 7) / 8;
-    if (lane == 0 && ty8 * 8 < a.gh && tx8 * 8 < a.gw)
-      a.partial[(long)b * a.partials_per_image + ty8 * tiles_x8 + tx8] = (double)sse;
-  }
 }
 
 // ------------------------------------------------------------------------------ conv1 kernel
@@ -1808,185 +150,6 @@ __global__ void __launch_bounds__(256) conv1_gdn_kernel(const EngineArgs a) {
   } else {
     static_assert(EPI == EPI_IGDN_BWD, "conv1 kernel epilogues: GDN fwd, IGDN bwd");
     gdn_bwd_epilogue<CO, MT, NT, true>(acc, smem, a, t, wm, ncol0, lane);
-  }
-}
-
-// ------------------------------------------------------------ deconv3 in the bf16 mode
-// synthesis_17.py:23-25 + model.py:59 on a bf16 NHWC input: the all-phase GEMM of
-// deconv3_x6_kernel (48 columns = 16 output phases × 3 channels, d3_col order, dy = −1 / dx = −1
-// taps on the tiles that hold their non-zero weights) with one bf16 product per MAC, but all 9
-// taps of a 32-channel chunk per barrier: the chunk's 18×18 patch and its 9 weight slices are
-// double-buffered by LDS-DMA (153 KB, one workgroup of 8 waves per CU), so a chunk costs one
-// barrier instead of nine. Wave w owns base rows 2w, 2w+1. The accumulation order (chunk, tap)
-// and the operands (weights rounded to bf16 in the loop, one bf16 product per MAC) are those of the
-// per-tap bf16 kernel this replaces, so the results are bit-identical to it.
-template <int CI>
-__global__ void __launch_bounds__(512) deconv3_bf16_kernel(const EngineArgs a) {
-  constexpr int KCH = 32, NCH = CI / KCH, MT = 2, NT = 3, NW = 8;
-  constexpr int NAI = (D3_PPX + 15) / 16;   // 21 patch wave-instructions per chunk (16 px each)
-  constexpr int SA = NAI * 256;             // patch buffer floats
-  constexpr int NBI = 19;                   // weight blocks per chunk: the 19 tile-taps
-  constexpr int PB = NBI * 256;             // weight floats per chunk: [block][k8 4][16][8] bf16
-  constexpr int KA = (NAI + NW - 1) / NW, KB = (NBI + NW - 1) / NW;
-  constexpr int LDS = 2 * SA + 2 * PB;
-  static_assert(3 * D3_EC + 16 <= LDS, "epilogue block fits");
-  __shared__ __attribute__((aligned(16))) float smem[LDS];
-  if (a.fold_partial != nullptr && blockIdx.x == 0) fold_bits<512>(a, (double*)smem);
-  float* const sA = smem;
-  float* const sB = smem + 2 * SA;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int bid = blockIdx.x;
-  const int tx = bid % a.tiles_x;
-  bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int b = bid / a.tiles_y;
-
-  // patch DMA: instruction i, slot q = 16i + lane/4 (patch pixel), physical piece lane & 3 ←
-  // logical piece (lane & 3) ^ swizzle(q); -1: zero line
-  int asrc[KA];
-#pragma unroll
-  for (int j = 0; j < KA; ++j) {
-    const int i = wave + NW * j;
-    const int p = i * 16 + (lane >> 2);
-    const int r = p / D3_PS, c = p - r * D3_PS;
-    const int iy = ty * D3_BS - 1 + r, ix = tx * D3_BS - 1 + c;
-    const bool ok = i < NAI && p < D3_PPX && (unsigned)iy < (unsigned)a.Hin &&
-                    (unsigned)ix < (unsigned)a.Win;
-    const int g = (lane & 3) ^ (((p >> 2) & 1) << 1);
-    asrc[j] = ok ? (iy * a.Win + ix) * CI + g * 8 : -1;
-  }
-  // weight DMA (iclr17_round_packed of the ICLR17_W_DECONV9 packing: [9][CI/8][48][8] bf16): only
-  // the column tiles a tap touches (d3_col; the others are exact zeros for it), one 1 KB block
-  // [k8 4][16][8] per tile-tap, taps in order (1, 1, 1, 2, 3, 3, 2, 3, 3 tiles): 19 KB per chunk
-  // instead of 27. Instruction i = block i, slot (k8, c) ← packed (cc·4 + k8, d3_col(16·tt + c)).
-  int bsrc[KB];
-#pragma unroll
-  for (int j = 0; j < KB; ++j) {
-    const int i = wave + NW * j;
-    int t = 0;
-    while (t < 8 && d3_boff(t + 1) <= i) ++t;
-    const int tt = i - d3_boff(t), k8 = lane >> 4, c = lane & 15;
-    bsrc[j] = ((t * (CI / 8) + k8) * 48 + d3_col(16 * tt + c)) * 8;
-  }
-  const unsigned short* __restrict__ wb = (const unsigned short*)a.w;
-  const unsigned short* __restrict__ inb = a.in_split + (long)b * a.Hin * a.Win * CI;
-  auto issue = [&](int cc, int buf) {
-#pragma unroll
-    for (int j = 0; j < KA; ++j) {
-      const int i = wave + NW * j;
-      if (i < NAI)
-        glds16(asrc[j] >= 0 ? (const float*)(inb + asrc[j] + cc * KCH) : g_zero16,
-               sA + buf * SA + i * 256);
-    }
-#pragma unroll
-    for (int j = 0; j < KB; ++j) {
-      const int i = wave + NW * j;
-      if (i < NBI) glds16((const float*)(wb + cc * 4 * 48 * 8 + bsrc[j]), sB + buf * PB + i * 256);
-    }
-  };
-
-  f4 acc[MT][NT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-  const int g = lane >> 4;
-  const int prow = (2 * wave + 1) * D3_PS + 1 + (lane & 15);   // window origin for mt = 0
-  auto compute = [&](int buf, int tap, auto ntt) {
-    constexpr int NTT = decltype(ntt)::value;   // tiles this tap touches
-    const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-    const u4* sb = (const u4*)(sB + buf * PB + d3_boff(tap) * 256) + g * 16 + (lane & 15);
-    bf8 Bb[NTT];
-#pragma unroll
-    for (int nt = 0; nt < NTT; ++nt) Bb[nt] = __builtin_bit_cast(bf8, sb[nt * 64]);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int p = prow + (mt + dy) * D3_PS + dx;
-      const unsigned short* sa =
-          (const unsigned short*)(sA + buf * SA + p * 16 + ((g ^ (((p >> 2) & 1) << 1)) * 4));
-      const bf8 Ab = __builtin_bit_cast(bf8, *(const u4*)(sa));
-#pragma unroll
-      for (int nt = 0; nt < NTT; ++nt)
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ab, Bb[nt], acc[mt][nt], 0, 0, 0);
-    }
-  };
-
-  issue(0, 0);
-  for (int cc = 0; cc < NCH; ++cc) {
-    dma_barrier();   // chunk cc landed; buffer (cc+1)&1 is free
-    if (cc + 1 < NCH) issue(cc + 1, (cc + 1) & 1);
-    const int buf = cc & 1;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      if (tap < 3)
-        compute(buf, tap, std::integral_constant<int, 1>{});
-      else if (tap == 3 || tap == 6)
-        compute(buf, tap, std::integral_constant<int, 2>{});
-      else
-        compute(buf, tap, std::integral_constant<int, 3>{});
-    }
-  }
-  __syncthreads();     // stage reads done before the epilogue reuses LDS
-
-  // epilogue: column n = co·16 + ry·4 + rx of row m = (by, bx) → output (4by + ry, 4bx + rx);
-  // the waves 2q, 2q+1 store output quadrant q's upper / lower 16 rows
-  constexpr int OS = 4 * D3_BS;
-  float* sO = smem;   // [3][64][64], strides D3_EC / D3_ES
-  float* red = smem + 3 * D3_EC;
-  const int H = a.Hout, W = a.Wout;
-  float sse = 0.f;
-  int pcol[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) pcol[nt] = d3_col(nt * 16 + (lane & 15));
-  const int q = wave >> 1, hf = wave & 1, qy = q >> 1, qx = q & 1;
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 1 && a.recon == nullptr) break;
-    float* dst = pass == 0 ? a.out : a.recon;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int by = 2 * wave + mt, bx = 4 * g + r;
-          const int co = pcol[nt] >> 4, ph = pcol[nt] & 15;
-          float v = acc[mt][nt][r] + a.bias[co];
-          if (pass == 0) v = fminf(fmaxf(v, 0.0f), 1.0f);
-          sO[co * D3_EC + (by * 4 + (ph >> 2)) * D3_ES + bx * 4 + (ph & 3)] = v;
-        }
-    __syncthreads();
-    const bool sse_pass = pass == (a.sse_unclipped ? 1 : 0) && a.xref != nullptr;
-    for (int k = lane; k < 3 * 16 * 8; k += 64) {
-      const int c4 = k & 7, row = (k >> 3) & 15, co = k >> 7;
-      const int oyl = qy * 32 + hf * 16 + row, oxl = qx * 32 + c4 * 4;
-      const int oy = ty * OS + oyl, ox = tx * OS + oxl;
-      if (oy >= H || ox >= W) continue;
-      const float* sp = sO + co * D3_EC + oyl * D3_ES + oxl;
-      const f4 v = f4{sp[0], sp[1], sp[2], sp[3]};
-      const long off = (((long)b * 3 + co) * H + oy) * W + ox;
-      *(f4*)(dst + off) = v;
-      if (sse_pass) {
-        const f4 xr = *(const f4*)(a.xref + off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = v[e] - xr[e];
-          sse += d * d;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (a.xref != nullptr) {
-    sse = wave_sum(sse);
-    if (lane == 0) red[wave] = sse;
-    __syncthreads();
-    const int ty8 = 2 * ty + qy, tx8 = 2 * tx + qx;
-    const int tiles_x8 = (a.gw + 7) / 8;
-    if (hf == 0 && lane == 0 && ty8 * 8 < a.gh && tx8 * 8 < a.gw)
-      a.partial[(long)b * a.partials_per_image + ty8 * tiles_x8 + tx8] =
-          (double)(red[wave] + red[wave + 1]);
   }
 }
 
@@ -2180,6 +343,29 @@ __global__ void __launch_bounds__(256, 2) conv1_x6_kernel(const EngineArgs a) {
   }
 }
 
+// x → three exact bf16 planes (x6 activation format), 8 values per thread
+__global__ void __launch_bounds__(256) split_planes_kernel(const float* __restrict__ x, long n8,
+                                                           unsigned short* __restrict__ planes,
+                                                           long plane) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
+    u4 hi, mi, lo;
+    split8(*(const f4*)(x + 8 * i), *(const f4*)(x + 8 * i + 4), hi, mi, lo);
+    *(u4*)(planes + 8 * i) = hi;
+    *(u4*)(planes + plane + 8 * i) = mi;
+    *(u4*)(planes + 2 * plane + 8 * i) = lo;
+  }
+}
+
+// packed fp32 operand [taps][K/4][N][4] → split planes [3][taps][K/8][N][8] bf16 (the
+// B-fragment layout of v_mfma_f32_16x16x32_bf16), exact
+__global__ void __launch_bounds__(256) split_packed_kernel(const float* __restrict__ w, int taps,
+                                                           int K, int N,
+                                                           unsigned short* __restrict__ planes) {
+  const long n = (long)taps * (K / 8) * N;   // 8-element groups
+  for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < n; g += (long)gridDim.x * 256)
+    split_packed_group(w, K, N, n * 8, planes, g);
+}
+
 // --------------------------------------------------------------------- stand-alone GDN / IGDN
 // GDN.forward (models/GDN.py:64-94) on a [B,C,H,W] tensor stored NCHW or NHWC: 64 pixels of one
 // image per workgroup (linear pixel order), all C channels, the same fused core as the layers.
@@ -2340,17 +526,9 @@ __global__ void __launch_bounds__(256) gdn_bwd_kernel(const float* __restrict__ 
 }
 
 // ====================================================================================== host
+// Launchers: the entry point has filled pointers, B, the input grid Hin × Win and the x6 planes;
+// the launcher adds everything derived from them and picks the instantiation.
 namespace {
-
-thread_local char g_err[512];
-
-int check_dims(int B, int H, int W, int N) {
-  ICLR17_REQUIRE(B > 0 && H > 0 && W > 0, ICLR17_EINVAL, "bad shape B=%d H=%d W=%d", B, H, W);
-  ICLR17_REQUIRE(H % 16 == 0 && W % 16 == 0, ICLR17_EINVAL,
-                 "image height/width must be multiples of 16 (got %dx%d)", H, W);
-  ICLR17_REQUIRE(N == 128 || N == 192, ICLR17_EUNSUPPORTED, "channel count N=%d unsupported (128, 192)", N);
-  return ICLR17_OK;
-}
 
 void fill_conv5_taps(TapTable& tt) {
   memset(&tt, 0, sizeof(tt));
@@ -2362,8 +540,7 @@ void fill_conv5_taps(TapTable& tt) {
     for (int kw = 0; kw < 5; ++kw) tt.dydx[kh * 5 + kw] = pack_tap(kh - 2, kw - 2);
 }
 
-// ConvTranspose2d(k, stride s, pad p): output o = s·q + r receives input q + d through kernel
-// tap k = r + p − s·d (0 ≤ k < K). Phase-major tap order; the packing kernel uses the same order.
+// Phase-major tap order; the packing kernel uses the same enumeration (for_each_deconv_tap).
 void fill_deconv_taps(TapTable& tt, int K, int s, int p) {
   memset(&tt, 0, sizeof(tt));
   tt.npx = s;
@@ -2372,16 +549,8 @@ void fill_deconv_taps(TapTable& tt, int K, int s, int p) {
   for (int ry = 0; ry < s; ++ry)
     for (int rx = 0; rx < s; ++rx) {
       tt.begin[ry * s + rx] = n;
-      for (int dy = 2; dy >= -2; --dy) {
-        const int kh = ry + p - s * dy;
-        if (kh < 0 || kh >= K) continue;
-        for (int dx = 2; dx >= -2; --dx) {
-          const int kw = rx + p - s * dx;
-          if (kw < 0 || kw >= K) continue;
-          tt.dydx[n] = pack_tap(dy, dx);
-          ++n;
-        }
-      }
+      for_each_deconv_tap(K, s, p, ry, rx,
+                          [&](int dy, int dx, int, int) { tt.dydx[n++] = pack_tap(dy, dx); });
     }
   tt.begin[s * s] = n;
 }
@@ -2394,287 +563,174 @@ void fill_neigh3_taps(TapTable& tt) {
   for (int i = 0; i < 9; ++i) tt.dydx[i] = pack_tap(i / 3 - 1, i % 3 - 1);
 }
 
-hipStream_t S(void* s) { return (hipStream_t)s; }
+// Output size, base grid gh × gw in 8×8 tiles, and the strides applied to base coordinates.
+void set_geometry(EngineArgs& a, int Hout, int Wout, int gh, int gw, int sin, int sout) {
+  a.Hout = Hout; a.Wout = Wout;
+  a.gh = gh; a.gw = gw; a.tiles_y = (gh + 7) / 8; a.tiles_x = (gw + 7) / 8;
+  a.sin = sin; a.sout = sout;
+}
+
+// conv1 (k9 s4) on the Hin × Win image. W_SPLIT: a.w holds the split ICLR17_W_CONV1_X6 planes and
+// the contraction itself runs in x6 (conv1_x6_kernel).
+enum Conv1Weights { W_PACKED, W_SPLIT };
+
+template <int EPI, Conv1Weights WF = W_PACKED>
+int launch_conv1(EngineArgs a, int N, hipStream_t st) {
+  set_geometry(a, a.Hin / 4, a.Win / 4, a.Hin / 4, a.Win / 4, 4, 1);
+  a.tt.npx = 1; a.tt.nph = 1;
+  const dim3 grid(a.tiles_x * a.tiles_y * a.B, 1);
+  return with_N(N, [&](auto n) {
+    constexpr int CN = decltype(n)::value;
+    if constexpr (WF == W_SPLIT) {
+      hipLaunchKernelGGL((conv1_x6_kernel<CN, EPI>), grid, dim3(256), 0, st, a);
+      return check_launch(EPI == EPI_GDN ? "conv1x6_gdn" : "bwd_deconv3_igdn_x6");
+    } else if constexpr (EPI == EPI_GDN) {
+      if (a.ggamma6 != nullptr)
+        hipLaunchKernelGGL((conv1_gdn_kernel<CN, EPI, true>), grid, dim3(256), 0, st, a);
+      else
+        hipLaunchKernelGGL((conv1_gdn_kernel<CN, EPI>), grid, dim3(256), 0, st, a);
+      return check_launch("conv1_gdn");
+    } else {
+      hipLaunchKernelGGL((conv1_gdn_kernel<CN, EPI>), grid, dim3(256), 0, st, a);
+      return check_launch("bwd_deconv3_igdn");
+    }
+  });
+}
+
+// k5 s2 convolution on the Hin × Win input grid (conv2, conv3, and the input gradients of the
+// deconvs, whose adjoint it is).
+template <int EPI>
+int launch_conv5(EngineArgs a, int N, hipStream_t st) {
+  set_geometry(a, a.Hin / 2, a.Win / 2, a.Hin / 2, a.Win / 2, 2, 1);
+  fill_conv5_taps(a.tt);
+  const bool X6in = a.in_split != nullptr;
+  const int tiles = a.tiles_x * a.tiles_y, B = a.B;
+  return with_N(N, [&](auto n) {
+    constexpr int CN = decltype(n)::value;
+    if constexpr (EPI == EPI_QUANT) {
+      // Column split of conv3: 96 columns (2×2 waves) at N = 192 — B=64 gives 512 workgroups, one
+      // round of slots, and 20 % fewer operand bytes per MAC than 64-column tiles.
+      constexpr int BN = conv3_bn(CN);
+      constexpr int WN = (BN / 16) % 4 == 0 ? 4 : 2, WM = 4 / WN;
+      a.partials_per_image = tiles * (CN / BN);
+      const dim3 grid(tiles * B, CN / BN);
+      if constexpr (CN == 192) {
+        if (X6in && conv3_narrow(CN, tiles, B, a.qmode)) {
+          a.partials_per_image = tiles * (CN / 48);
+          a.w6 = nullptr;   // the narrow instantiation splits its weights per k-step
+          hipLaunchKernelGGL((engine_kernel<CN, CN, 48, 4, 1, EPI_QUANT, true>),
+                             dim3(tiles * B, CN / 48), dim3(256), 0, st, a);
+          return check_launch("conv3_quant_rate (48-column tiles)");
+        }
+      }
+      if (X6in && a.w6 != nullptr)
+        hipLaunchKernelGGL((engine_kernel<CN, CN, BN, WM, WN, EPI_QUANT, true, true>), grid,
+                           dim3(256), 0, st, a);
+      else if (X6in)
+        hipLaunchKernelGGL((engine_kernel<CN, CN, BN, WM, WN, EPI_QUANT, true>), grid, dim3(256),
+                           0, st, a);
+      else
+        hipLaunchKernelGGL((engine_kernel<CN, CN, BN, WM, WN, EPI_QUANT>), grid, dim3(256), 0, st,
+                           a);
+      return check_launch("conv3_quant_rate");
+    } else if constexpr (EPI == EPI_PLAIN || EPI == EPI_RATE_BWD) {
+      constexpr int BN = 64;
+      const dim3 grid(tiles * B, CN / BN);
+      if (EPI == EPI_RATE_BWD && X6in)
+        hipLaunchKernelGGL((engine_kernel<CN, CN, BN, 1, 4, EPI, true>), grid, dim3(256), 0, st, a);
+      else
+        hipLaunchKernelGGL((engine_kernel<CN, CN, BN, 1, 4, EPI>), grid, dim3(256), 0, st, a);
+      return check_launch(EPI == EPI_PLAIN ? "conv3" : "bwd_deconv1_rate");
+    } else {
+      const dim3 grid(tiles * B, 1);
+      if constexpr (EPI == EPI_GDN) {
+        if (X6in) {
+          hipLaunchKernelGGL((engine_kernel<CN, CN, CN, 1, 4, EPI, true>), grid, dim3(256), 0, st, a);
+          return check_launch("conv2_gdn");
+        }
+      } else if constexpr (EPI == EPI_IGDN_BWD) {
+        if (X6in) {   // held to 256 VGPRs: two waves per SIMD
+          hipLaunchKernelGGL((engine_kernel_occ2<CN, CN, CN, 1, 4, EPI, true>), grid, dim3(256), 0,
+                             st, a);
+          return check_launch("bwd_deconv_igdn");
+        }
+      }
+      hipLaunchKernelGGL((engine_kernel<CN, CN, CN, 1, 4, EPI>), grid, dim3(256), 0, st, a);
+      return check_launch("conv2_gdn");
+    }
+  });
+}
+
+// k5 s2 transposed convolution on the Hin × Win input grid (deconv1, deconv2, and the input
+// gradient of conv2 / conv3): one workgroup per (base tile, stride phase), phase-major, the
+// 9-tap phase first.
+template <int EPI>
+int launch_deconv5(EngineArgs a, int N, hipStream_t st) {
+  set_geometry(a, 2 * a.Hin, 2 * a.Win, a.Hin, a.Win, 1, 2);
+  fill_deconv_taps(a.tt, 5, 2, 2);
+  const dim3 grid(a.tiles_x * a.tiles_y * a.B * 4);
+  return with_N(N, [&](auto n) {
+    constexpr int CN = decltype(n)::value;
+    if (a.in_split != nullptr) {
+      if constexpr (EPI == EPI_IGDN)
+        hipLaunchKernelGGL((engine_kernel<CN, CN, CN, 1, 4, EPI, true>), grid, dim3(256), 0, st, a);
+      else   // held to 256 VGPRs: two waves per SIMD
+        hipLaunchKernelGGL((engine_kernel_occ2<CN, CN, CN, 1, 4, EPI, true>), grid, dim3(256), 0,
+                           st, a);
+    } else {
+      hipLaunchKernelGGL((engine_kernel<CN, CN, CN, 1, 4, EPI>), grid, dim3(256), 0, st, a);
+    }
+    return check_launch(EPI == EPI_IGDN ? "deconv_igdn" : "bwd_conv_gdn");
+  });
+}
+
+// fp32 deconv3 (k9 s4, N → 3) as the engine's all-phase GEMM; a.Hin × a.Win is its input grid.
+int launch_deconv3(EngineArgs a, int N, hipStream_t st) {
+  set_geometry(a, 4 * a.Hin, 4 * a.Win, a.Hin, a.Win, 1, 4);
+  a.partials_per_image = a.tiles_x * a.tiles_y;
+  fill_neigh3_taps(a.tt);
+  const dim3 grid(a.tiles_x * a.tiles_y * a.B, 1);
+  return with_N(N, [&](auto n) {
+    constexpr int CN = decltype(n)::value;
+    hipLaunchKernelGGL((engine_kernel<CN, 48, 48, 4, 1, EPI_OUT3>), grid, dim3(256), 0, st, a);
+    return check_launch("deconv3");
+  });
+}
+
+// x6 activation planes [3][B][h][w][N]: the plane stride in elements
+long plane(int B, int h, int w, int N) { return (long)B * h * w * N; }
 
 }  // namespace
-
-void set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  int n = snprintf(g_err, sizeof(g_err), "iclr17 error %d: ", code);
-  if (n < 0) n = 0;
-  vsnprintf(g_err + n, sizeof(g_err) - n, fmt, ap);
-  va_end(ap);
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(ICLR17_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
-    return ICLR17_ELAUNCH;
-  }
-  return ICLR17_OK;
-}
-
-// exposed to aux.hip for its launches
-const char* last_error_buf() { return g_err; }
-
-// tap-table helpers shared with the packing code
-void deconv_phase_taps(int K, int s, int p, int ry, int rx, int* kh_out, int* kw_out, int* count) {
-  int n = 0;
-  for (int dy = 2; dy >= -2; --dy) {
-    const int kh = ry + p - s * dy;
-    if (kh < 0 || kh >= K) continue;
-    for (int dx = 2; dx >= -2; --dx) {
-      const int kw = rx + p - s * dx;
-      if (kw < 0 || kw >= K) continue;
-      kh_out[n] = kh;
-      kw_out[n] = kw;
-      ++n;
-    }
-  }
-  *count = n;
-}
-
-// x6 activation-format arguments of a launch (all null/0: fp32 in, fp32 out)
-struct SplitIO {
-  const unsigned short* in = nullptr;
-  long in_plane = 0;
-  unsigned short* out = nullptr;
-  long out_plane = 0;
-  int out_cm = 0;                           // out in the chunk-major split form
-  const unsigned short* gamma6 = nullptr;   // x6: split γ_eff for the GDN contraction
-  const unsigned short* gammaT6 = nullptr;  // x6 backward: split transposed γ_eff
-  const unsigned short* w6 = nullptr;       // x6 conv3: pre-split weights (engine W6)
-  long w6_plane = 0;
-};
-
-static void apply_split(EngineArgs& a, const SplitIO* x6) {
-  if (x6 == nullptr) return;
-  a.in_split = x6->in; a.in_plane = x6->in_plane;
-  a.out_split = x6->out; a.out_plane = x6->out_plane; a.out_cm = x6->out_cm;
-  a.ggamma6 = x6->gamma6;
-  a.ggammaT6 = x6->gammaT6;
-  a.w6 = x6->w6;
-  a.w6_plane = x6->w6_plane;
-}
-
-template <int N, int EPI = EPI_GDN>
-int launch_conv1(const float* x, int B, int H, int W, const float* wp, const float* bias,
-                 const float* beta, const float* gamma, float* out, float* pre, hipStream_t st,
-                 const EngineArgs* bwd = nullptr, const SplitIO* x6 = nullptr) {
-  EngineArgs a;
-  memset(&a, 0, sizeof(a));
-  if (bwd) a = *bwd;
-  apply_split(a, x6);
-  a.in = x; a.w = wp; a.bias = bias; a.gbeta = beta; a.ggamma = gamma; a.out = out; a.pre = pre;
-  a.B = B; a.Hin = H; a.Win = W; a.Hout = H / 4; a.Wout = W / 4;
-  a.gh = H / 4; a.gw = W / 4; a.tiles_y = (a.gh + 7) / 8; a.tiles_x = (a.gw + 7) / 8;
-  a.sin = 4; a.sout = 1;
-  a.tt.npx = 1; a.tt.nph = 1;
-  dim3 grid(a.tiles_x * a.tiles_y * B, 1);
-  if constexpr (EPI == EPI_GDN) {
-    if (a.ggamma6 != nullptr) {
-      hipLaunchKernelGGL((conv1_gdn_kernel<N, EPI, true>), grid, dim3(256), 0, st, a);
-      return check_launch("conv1_gdn");
-    }
-  } else {
-    if (a.in_split != nullptr) {   // bwd: a.w = the split ICLR17_W_CONV1_X6 planes (x6 contraction)
-      a.w = (const float*)a.in_split;
-      a.in_split = nullptr;
-      hipLaunchKernelGGL((conv1_x6_kernel<N, EPI>), grid, dim3(256), 0, st, a);
-      return check_launch("bwd_deconv3_igdn_x6");
-    }
-  }
-  hipLaunchKernelGGL((conv1_gdn_kernel<N, EPI>), grid, dim3(256), 0, st, a);
-  return check_launch(EPI == EPI_GDN ? "conv1_gdn" : "bwd_deconv3_igdn");
-}
-
-template <int N, int EPI>
-int launch_conv5(const float* in, int B, int Hin, int Win, const float* wp, const float* bias,
-                 const float* beta, const float* gamma, float* out, float* pre, int qmode,
-                 const float* noise, const float* rate, float* yhat, double* partial,
-                 hipStream_t st, const EngineArgs* bwd = nullptr, const SplitIO* x6 = nullptr,
-                 const float* rtab = nullptr) {
-  EngineArgs a;
-  memset(&a, 0, sizeof(a));
-  if (bwd) a = *bwd;
-  apply_split(a, x6);
-  const bool X6in = a.in_split != nullptr;
-  a.in = in; a.w = wp; a.bias = bias; a.gbeta = beta; a.ggamma = gamma; a.out = out; a.pre = pre;
-  a.B = B; a.Hin = Hin; a.Win = Win; a.Hout = Hin / 2; a.Wout = Win / 2;
-  a.gh = a.Hout; a.gw = a.Wout; a.tiles_y = (a.gh + 7) / 8; a.tiles_x = (a.gw + 7) / 8;
-  a.sin = 2; a.sout = 1;
-  fill_conv5_taps(a.tt);
-  a.qmode = qmode; a.noise = noise; a.rate = rate; a.rtab = rtab; a.yhat = yhat; a.partial = partial;
-  if constexpr (EPI == EPI_QUANT) {
-    // Column split of conv3: 96 columns (2×2 waves) at N = 192 — B=64 gives 512 workgroups, one
-    // round of slots, and 20 % fewer operand bytes per MAC than 64-column tiles.
-    constexpr int BN = conv3_bn(N);
-    constexpr int WN = (BN / 16) % 4 == 0 ? 4 : 2, WM = 4 / WN;
-    a.partials_per_image = a.tiles_x * a.tiles_y * (N / BN);
-    dim3 grid(a.tiles_x * a.tiles_y * B, N / BN);
-    if constexpr (N == 192) {
-      if (X6in && conv3_narrow(N, a.tiles_x * a.tiles_y, B, qmode)) {
-        a.partials_per_image = a.tiles_x * a.tiles_y * (N / 48);
-        a.w6 = nullptr;   // the narrow instantiation splits its weights per k-step
-        hipLaunchKernelGGL((engine_kernel<N, N, 48, 4, 1, EPI_QUANT, true>),
-                           dim3(a.tiles_x * a.tiles_y * B, N / 48), dim3(256), 0, st, a);
-        return check_launch("conv3_quant_rate (48-column tiles)");
-      }
-    }
-    if (X6in && a.w6 != nullptr)
-      hipLaunchKernelGGL((engine_kernel<N, N, BN, WM, WN, EPI_QUANT, true, true>), grid,
-                         dim3(256), 0, st, a);
-    else if (X6in)
-      hipLaunchKernelGGL((engine_kernel<N, N, BN, WM, WN, EPI_QUANT, true>), grid,
-                         dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((engine_kernel<N, N, BN, WM, WN, EPI_QUANT>), grid, dim3(256), 0, st, a);
-    return check_launch("conv3_quant_rate");
-  } else if constexpr (EPI == EPI_PLAIN || EPI == EPI_RATE_BWD) {
-    constexpr int BN = 64;
-    dim3 grid(a.tiles_x * a.tiles_y * B, N / BN);
-    if (EPI == EPI_RATE_BWD && X6in)
-      hipLaunchKernelGGL((engine_kernel<N, N, BN, 1, 4, EPI, true>), grid, dim3(256), 0,
-                         st, a);
-    else
-      hipLaunchKernelGGL((engine_kernel<N, N, BN, 1, 4, EPI>), grid, dim3(256), 0, st, a);
-    return check_launch(EPI == EPI_PLAIN ? "conv3" : "bwd_deconv1_rate");
-  } else {
-    dim3 grid(a.tiles_x * a.tiles_y * B, 1);
-    if constexpr (EPI == EPI_GDN) {
-      if (X6in) {
-        hipLaunchKernelGGL((engine_kernel<N, N, N, 1, 4, EPI, true>), grid, dim3(256), 0,
-                           st, a);
-        return check_launch("conv2_gdn");
-      }
-    } else if constexpr (EPI == EPI_IGDN_BWD) {
-      if (X6in) {   // held to 256 VGPRs: two waves per SIMD
-        hipLaunchKernelGGL((engine_kernel_occ2<N, N, N, 1, 4, EPI, true>), grid, dim3(256),
-                           0, st, a);
-        return check_launch("bwd_deconv_igdn");
-      }
-    }
-    hipLaunchKernelGGL((engine_kernel<N, N, N, 1, 4, EPI>), grid, dim3(256), 0, st, a);
-    return check_launch("conv2_gdn");
-  }
-}
-
-template <int N, int EPI = EPI_IGDN>
-int launch_deconv5(const float* in, int B, int h, int w, const float* wp, const float* bias,
-                   const float* beta, const float* gamma, float* out, float* pre, hipStream_t st,
-                   const EngineArgs* bwd = nullptr, const SplitIO* x6 = nullptr) {
-  EngineArgs a;
-  memset(&a, 0, sizeof(a));
-  if (bwd) a = *bwd;
-  apply_split(a, x6);
-  a.in = in; a.w = wp; a.bias = bias; a.gbeta = beta; a.ggamma = gamma; a.out = out; a.pre = pre;
-  a.B = B; a.Hin = h; a.Win = w; a.Hout = 2 * h; a.Wout = 2 * w;
-  a.gh = h; a.gw = w; a.tiles_y = (h + 7) / 8; a.tiles_x = (w + 7) / 8;
-  a.sin = 1; a.sout = 2;
-  fill_deconv_taps(a.tt, 5, 2, 2);
-  // one workgroup per (base tile, stride phase), phase-major: the 9-tap phase first
-  const int base_tiles = a.tiles_x * a.tiles_y * B;
-  if constexpr (EPI == EPI_IGDN) {
-    if (a.in_split != nullptr) {
-      hipLaunchKernelGGL((engine_kernel<N, N, N, 1, 4, EPI, true>), dim3(base_tiles * 4),
-                         dim3(256), 0, st, a);
-      return check_launch("deconv_igdn");
-    }
-  } else {
-    if (a.in_split != nullptr) {   // held to 256 VGPRs: two waves per SIMD
-      hipLaunchKernelGGL((engine_kernel_occ2<N, N, N, 1, 4, EPI, true>),
-                         dim3(base_tiles * 4), dim3(256), 0, st, a);
-      return check_launch("bwd_conv_gdn");
-    }
-  }
-    hipLaunchKernelGGL((engine_kernel<N, N, N, 1, 4, EPI>), dim3(base_tiles * 4), dim3(256), 0,
-                       st, a);
-  return check_launch(EPI == EPI_IGDN ? "deconv_igdn" : "bwd_conv_gdn");
-}
-
-template <int N>
-int launch_deconv3(const float* in, int B, int H, int W, const float* wp, const float* bias,
-                   const float* x, float* clipped, float* recon, double* partial, int sse_unclipped,
-                   hipStream_t st) {
-  EngineArgs a;
-  memset(&a, 0, sizeof(a));
-  a.sse_unclipped = sse_unclipped;
-  a.in = in; a.w = wp; a.bias = bias; a.out = clipped; a.recon = recon; a.xref = x;
-  a.partial = partial;
-  a.B = B; a.Hin = H / 4; a.Win = W / 4; a.Hout = H; a.Wout = W;
-  a.gh = H / 4; a.gw = W / 4; a.tiles_y = (a.gh + 7) / 8; a.tiles_x = (a.gw + 7) / 8;
-  a.partials_per_image = a.tiles_x * a.tiles_y;
-  a.sin = 1; a.sout = 4;
-  fill_neigh3_taps(a.tt);
-  dim3 grid(a.tiles_x * a.tiles_y * B, 1);
-  hipLaunchKernelGGL((engine_kernel<N, 48, 48, 4, 1, EPI_OUT3>), grid, dim3(256), 0, st, a);
-  return check_launch("deconv3");
-}
-
-// x → three exact bf16 planes (x6 activation format), 8 values per thread
-__global__ void __launch_bounds__(256) split_planes_kernel(const float* __restrict__ x, long n8,
-                                                           unsigned short* __restrict__ planes,
-                                                           long plane) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
-    u4 hi, mi, lo;
-    split8(*(const f4*)(x + 8 * i), *(const f4*)(x + 8 * i + 4), hi, mi, lo);
-    *(u4*)(planes + 8 * i) = hi;
-    *(u4*)(planes + plane + 8 * i) = mi;
-    *(u4*)(planes + 2 * plane + 8 * i) = lo;
-  }
-}
-
-// packed fp32 operand [taps][K/4][N][4] → split planes [3][taps][K/8][N][8] bf16 (the
-// B-fragment layout of v_mfma_f32_16x16x32_bf16), exact
-__global__ void __launch_bounds__(256) split_packed_kernel(const float* __restrict__ w, int taps,
-                                                           int K, int N,
-                                                           unsigned short* __restrict__ planes) {
-  const long n = (long)taps * (K / 8) * N;   // 8-element groups
-  for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < n; g += (long)gridDim.x * 256)
-    split_packed_group(w, K, N, n * 8, planes, g);
-}
-
 }  // namespace iclr17
 
 using namespace iclr17;
 
 extern "C" {
 
-int iclr17_version(void) { return 1; }
-
-int iclr17_last_error(char* buf, size_t len) {
-  const size_t n = strlen(g_err);
-  if (buf != nullptr && len > 0) {
-    const size_t c = n < len - 1 ? n : len - 1;
-    memcpy(buf, g_err, c);
-    buf[c] = 0;
-  }
-  return (int)n;
-}
-
 int iclr17_analysis_conv1_gdn(const float* x, int B, int H, int W, int N, const float* w_packed,
                               const float* bias, const float* beta_eff, const float* gamma_packed,
                               float* out, float* pre_out, void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(x && w_packed && bias && beta_eff && gamma_packed && out, ICLR17_EINVAL,
                  "conv1_gdn: null pointer");
-  return N == 192 ? launch_conv1<192>(x, B, H, W, w_packed, bias, beta_eff, gamma_packed, out, pre_out, S(stream))
-                  : launch_conv1<128>(x, B, H, W, w_packed, bias, beta_eff, gamma_packed, out, pre_out, S(stream));
+  EngineArgs a = zero_args();
+  a.in = x; a.w = w_packed; a.bias = bias; a.gbeta = beta_eff; a.ggamma = gamma_packed;
+  a.out = out; a.pre = pre_out;
+  a.B = B; a.Hin = H; a.Win = W;
+  return launch_conv1<EPI_GDN>(a, N, S(stream));
 }
 
 int iclr17_analysis_conv2_gdn(const float* in, int B, int H, int W, int N, const float* w_packed,
                               const float* bias, const float* beta_eff, const float* gamma_packed,
                               float* out, float* pre_out, void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(in && w_packed && bias && beta_eff && gamma_packed && out, ICLR17_EINVAL,
                  "conv2_gdn: null pointer");
-  const int h = H / 4, w = W / 4;
-  return N == 192 ? launch_conv5<192, EPI_GDN>(in, B, h, w, w_packed, bias, beta_eff, gamma_packed, out, pre_out, 0, nullptr, nullptr, nullptr, nullptr, S(stream))
-                  : launch_conv5<128, EPI_GDN>(in, B, h, w, w_packed, bias, beta_eff, gamma_packed, out, pre_out, 0, nullptr, nullptr, nullptr, nullptr, S(stream));
+  EngineArgs a = zero_args();
+  a.in = in; a.w = w_packed; a.bias = bias; a.gbeta = beta_eff; a.ggamma = gamma_packed;
+  a.out = out; a.pre = pre_out;
+  a.B = B; a.Hin = H / 4; a.Win = W / 4;
+  return launch_conv5<EPI_GDN>(a, N, S(stream));
 }
 
 int iclr17_conv3_x6_partials_per_image(int B, int H, int W, int N, int quant_mode) {
@@ -2692,158 +748,41 @@ int iclr17_analysis_conv3_quant_rate(const float* in, int B, int H, int W, int N
                                      const float* rate_packed, const float* rate_table,
                                      float* y_out, float* y_hat, double* bits_partial,
                                      void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(in && w_packed && rate_packed && y_hat && bits_partial, ICLR17_EINVAL,
                  "conv3_quant_rate: null pointer");
   ICLR17_REQUIRE(quant_mode == ICLR17_QUANT_ROUND || (quant_mode == ICLR17_QUANT_NOISE && noise),
                  ICLR17_EINVAL, "conv3_quant_rate: bad quant mode %d / missing noise", quant_mode);
-  const int h = H / 8, w = W / 8;
-  return N == 192 ? launch_conv5<192, EPI_QUANT>(in, B, h, w, w_packed, nullptr, nullptr, nullptr, y_out, nullptr, quant_mode, noise, rate_packed, y_hat, bits_partial, S(stream), nullptr, nullptr, rate_table)
-                  : launch_conv5<128, EPI_QUANT>(in, B, h, w, w_packed, nullptr, nullptr, nullptr, y_out, nullptr, quant_mode, noise, rate_packed, y_hat, bits_partial, S(stream), nullptr, nullptr, rate_table);
+  EngineArgs a = zero_args();
+  a.in = in; a.w = w_packed; a.out = y_out;
+  a.qmode = quant_mode; a.noise = noise; a.rate = rate_packed; a.rtab = rate_table;
+  a.yhat = y_hat; a.partial = bits_partial;
+  a.B = B; a.Hin = H / 8; a.Win = W / 8;
+  return launch_conv5<EPI_QUANT>(a, N, S(stream));
 }
 
 int iclr17_analysis_conv3(const float* in, int B, int H, int W, int N, const float* w_packed,
                           float* y_out, void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(in && w_packed && y_out, ICLR17_EINVAL, "conv3: null pointer");
-  const int h = H / 8, w = W / 8;
-  return N == 192 ? launch_conv5<192, EPI_PLAIN>(in, B, h, w, w_packed, nullptr, nullptr, nullptr, y_out, nullptr, 0, nullptr, nullptr, nullptr, nullptr, S(stream))
-                  : launch_conv5<128, EPI_PLAIN>(in, B, h, w, w_packed, nullptr, nullptr, nullptr, y_out, nullptr, 0, nullptr, nullptr, nullptr, nullptr, S(stream));
+  EngineArgs a = zero_args();
+  a.in = in; a.w = w_packed; a.out = y_out;
+  a.B = B; a.Hin = H / 8; a.Win = W / 8;
+  return launch_conv5<EPI_PLAIN>(a, N, S(stream));
 }
 
 int iclr17_synthesis_deconv_igdn(const float* in, int B, int h, int w, int N,
                                  const float* w_packed, const float* bias, const float* beta_eff,
                                  const float* gamma_packed, float* out, float* pre_out,
                                  void* stream) {
-  ICLR17_REQUIRE(B > 0 && h > 0 && w > 0, ICLR17_EINVAL, "deconv_igdn: bad shape");
-  ICLR17_REQUIRE(N == 128 || N == 192, ICLR17_EUNSUPPORTED, "channel count N=%d unsupported", N);
+  if (int rc = check_grid("deconv_igdn", B, h, w, N)) return rc;
   ICLR17_REQUIRE(in && w_packed && bias && beta_eff && gamma_packed && out, ICLR17_EINVAL,
                  "deconv_igdn: null pointer");
-  return N == 192 ? launch_deconv5<192>(in, B, h, w, w_packed, bias, beta_eff, gamma_packed, out, pre_out, S(stream))
-                  : launch_deconv5<128>(in, B, h, w, w_packed, bias, beta_eff, gamma_packed, out, pre_out, S(stream));
-}
-
-// w: iclr17_round_packed(9, N, 48) of the ICLR17_W_DECONV9 packing (bf16 mode) or its
-// iclr17_split_packed(9, N, 48) planes (x6)
-struct FoldBits {
-  const double* partial;
-  int T;
-  double* per_image;
-  float* total;
-  double scale;
-};
-
-static int launch_deconv3_halo(const uint16_t* in, int B, int H, int W, int N, const void* w,
-                               const float* bias, const float* x, float* clipped, float* recon,
-                               double* sse_partial, int sse_unclipped, void* stream, bool bf,
-                               int in_cm = 0, const FoldBits* fold = nullptr, bool h3 = false,
-                               const int* range_flag = nullptr) {
-  const char* what = bf ? "deconv3_bf16" : (h3 ? "deconv3_h3" : "deconv3_x6");
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
-  ICLR17_REQUIRE(in && w && bias && clipped, ICLR17_EINVAL, "%s: null pointer", what);
-  ICLR17_REQUIRE(x == nullptr || sse_partial != nullptr, ICLR17_EINVAL,
-                 "%s: sse_partial required with x", what);
-  ICLR17_REQUIRE(!sse_unclipped || recon != nullptr, ICLR17_EINVAL,
-                 "%s: the unclipped SSE needs the recon output", what);
-  EngineArgs a;
-  memset(&a, 0, sizeof(a));
-  a.sse_unclipped = sse_unclipped;
-  a.in_split = (const unsigned short*)in;
-  a.in_cm = in_cm;
-  a.w = (const float*)w; a.bias = bias; a.out = clipped; a.recon = recon; a.xref = x;
-  a.partial = sse_partial;
-  a.B = B; a.Hin = H / 4; a.Win = W / 4; a.Hout = H; a.Wout = W;
-  a.gh = H / 4; a.gw = W / 4;
-  a.in_plane = (long)B * a.Hin * a.Win * N;
-  a.tiles_y = (a.gh + D3_BS - 1) / D3_BS; a.tiles_x = (a.gw + D3_BS - 1) / D3_BS;
-  a.partials_per_image = ((a.gh + 7) / 8) * ((a.gw + 7) / 8);
-  if (fold != nullptr) {
-    ICLR17_REQUIRE(fold->partial && fold->T > 0 && fold->total, ICLR17_EINVAL,
-                   "%s: bits fold needs the partials, their count and a total", what);
-    a.fold_partial = fold->partial; a.fold_T = fold->T; a.fold_per_image = fold->per_image;
-    a.fold_total = fold->total; a.fold_scale = fold->scale;
-  }
-  dim3 grid(a.tiles_x * a.tiles_y * B);
-  if (bf) {
-    if (N == 192)
-      hipLaunchKernelGGL((deconv3_bf16_kernel<192>), grid, dim3(512), 0, S(stream), a);
-    else
-      hipLaunchKernelGGL((deconv3_bf16_kernel<128>), grid, dim3(512), 0, S(stream), a);
-  } else if (h3) {
-    a.wscale = (const float*)((const uint16_t*)w + 2L * 9 * N * 48);
-    a.range = const_cast<int*>(range_flag);   // read only (the poison check)
-    if (N == 192)
-      hipLaunchKernelGGL((deconv3_x6_kernel<192, true>), grid, dim3(256), 0, S(stream), a);
-    else
-      hipLaunchKernelGGL((deconv3_x6_kernel<128, true>), grid, dim3(256), 0, S(stream), a);
-  } else {
-    if (N == 192)
-      hipLaunchKernelGGL((deconv3_x6_kernel<192>), grid, dim3(256), 0, S(stream), a);
-    else
-      hipLaunchKernelGGL((deconv3_x6_kernel<128>), grid, dim3(256), 0, S(stream), a);
-  }
-  return check_launch(what);
-}
-
-int iclr17_synthesis_deconv3_h3(const uint16_t* in_h3_cm, int B, int H, int W, int N,
-                                const uint16_t* w_h3, const float* bias, const float* x,
-                                float* clipped, float* recon, double* sse_partial,
-                                int sse_unclipped, const double* bits_partial, int bits_T,
-                                double* bits_per_image, float* bpp_total, double bits_scale,
-                                const int* range_flag, void* stream) {
-  const FoldBits f = {bits_partial, bits_T, bits_per_image, bpp_total, bits_scale};
-  return launch_deconv3_halo(in_h3_cm, B, H, W, N, w_h3, bias, x, clipped, recon, sse_partial,
-                             sse_unclipped, stream, false, 1, bits_partial ? &f : nullptr, true,
-                             range_flag);
-}
-
-int iclr17_synthesis_deconv3_x6(const uint16_t* in_split, int B, int H, int W, int N,
-                                const uint16_t* w_split, const float* bias, const float* x,
-                                float* clipped, float* recon, double* sse_partial,
-                                int sse_unclipped, void* stream) {
-  return launch_deconv3_halo(in_split, B, H, W, N, w_split, bias, x, clipped, recon, sse_partial,
-                             sse_unclipped, stream, false);
-}
-
-int iclr17_synthesis_deconv3_x6_cm(const uint16_t* in_split_cm, int B, int H, int W, int N,
-                                   const uint16_t* w_split, const float* bias, const float* x,
-                                   float* clipped, float* recon, double* sse_partial,
-                                   int sse_unclipped, void* stream) {
-  return launch_deconv3_halo(in_split_cm, B, H, W, N, w_split, bias, x, clipped, recon, sse_partial,
-                             sse_unclipped, stream, false, 1);
-}
-
-int iclr17_synthesis_deconv3_x6_cm_bits(const uint16_t* in_split_cm, int B, int H, int W, int N,
-                                        const uint16_t* w_split, const float* bias, const float* x,
-                                        float* clipped, float* recon, double* sse_partial,
-                                        int sse_unclipped, const double* bits_partial, int bits_T,
-                                        double* bits_per_image, float* bpp_total, double bits_scale,
-                                        void* stream) {
-  const FoldBits f = {bits_partial, bits_T, bits_per_image, bpp_total, bits_scale};
-  return launch_deconv3_halo(in_split_cm, B, H, W, N, w_split, bias, x, clipped, recon, sse_partial,
-                             sse_unclipped, stream, false, 1, &f);
-}
-
-int iclr17_synthesis_deconv3_bf16_bits(const uint16_t* in, int B, int H, int W, int N,
-                                       const uint16_t* w_bf16, const float* bias, const float* x_ref,
-                                       float* clipped, float* recon, double* sse_partial,
-                                       int sse_unclipped, const double* bits_partial, int bits_T,
-                                       double* bits_per_image, float* bpp_total, double bits_scale,
-                                       void* stream) {
-  const FoldBits f = {bits_partial, bits_T, bits_per_image, bpp_total, bits_scale};
-  return launch_deconv3_halo(in, B, H, W, N, w_bf16, bias, x_ref, clipped, recon, sse_partial,
-                             sse_unclipped, stream, true, 0, &f);
-}
-
-int iclr17_synthesis_deconv3_bf16(const uint16_t* in, int B, int H, int W, int N,
-                                  const uint16_t* w_bf16, const float* bias, const float* x_ref,
-                                  float* clipped, float* recon, double* sse_partial,
-                                  int sse_unclipped, void* stream) {
-  return launch_deconv3_halo(in, B, H, W, N, w_bf16, bias, x_ref, clipped, recon, sse_partial,
-                             sse_unclipped, stream, true);
+  EngineArgs a = zero_args();
+  a.in = in; a.w = w_packed; a.bias = bias; a.gbeta = beta_eff; a.ggamma = gamma_packed;
+  a.out = out; a.pre = pre_out;
+  a.B = B; a.Hin = h; a.Win = w;
+  return launch_deconv5<EPI_IGDN>(a, N, S(stream));
 }
 
 int iclr17_output_partials_per_image(int H, int W) {
@@ -2853,15 +792,17 @@ int iclr17_output_partials_per_image(int H, int W) {
 int iclr17_synthesis_deconv3(const float* in, int B, int H, int W, int N, const float* w_packed,
                              const float* bias, const float* x, float* clipped, float* recon,
                              double* sse_partial, int sse_unclipped, void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(in && w_packed && bias && clipped, ICLR17_EINVAL, "deconv3: null pointer");
   ICLR17_REQUIRE(x == nullptr || sse_partial != nullptr, ICLR17_EINVAL,
                  "deconv3: sse_partial required with x");
   ICLR17_REQUIRE(!sse_unclipped || recon != nullptr, ICLR17_EINVAL,
                  "deconv3: the unclipped SSE needs the recon output");
-  return N == 192 ? launch_deconv3<192>(in, B, H, W, w_packed, bias, x, clipped, recon, sse_partial, sse_unclipped, S(stream))
-                  : launch_deconv3<128>(in, B, H, W, w_packed, bias, x, clipped, recon, sse_partial, sse_unclipped, S(stream));
+  EngineArgs a = zero_args();
+  a.in = in; a.w = w_packed; a.bias = bias; a.out = clipped; a.recon = recon;
+  a.xref = x; a.partial = sse_partial; a.sse_unclipped = sse_unclipped;
+  a.B = B; a.Hin = H / 4; a.Win = W / 4;
+  return launch_deconv3(a, N, S(stream));
 }
 
 // ------------------------------------------------------------------ x6 (bf16x6) precision mode
@@ -2890,63 +831,69 @@ int iclr17_analysis_conv1_gdn_x6(const float* x, int B, int H, int W, int N,
                                  const float* w_packed, const float* bias, const float* beta_eff,
                                  const float* gamma_packed, const uint16_t* gamma_split,
                                  float* out, uint16_t* out_split, float* pre_out, void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(x && w_packed && bias && beta_eff && gamma_packed && (out || out_split),
                  ICLR17_EINVAL, "conv1_gdn_x6: null pointer");
-  SplitIO io;
-  io.out = (unsigned short*)out_split;
-  io.out_plane = (long)B * (H / 4) * (W / 4) * N;
-  io.gamma6 = (const unsigned short*)gamma_split;
-  return N == 192 ? launch_conv1<192>(x, B, H, W, w_packed, bias, beta_eff, gamma_packed, out, pre_out, S(stream), nullptr, &io)
-                  : launch_conv1<128>(x, B, H, W, w_packed, bias, beta_eff, gamma_packed, out, pre_out, S(stream), nullptr, &io);
+  EngineArgs a = zero_args();
+  a.in = x; a.w = w_packed; a.bias = bias; a.gbeta = beta_eff; a.ggamma = gamma_packed;
+  a.ggamma6 = gamma_split;
+  a.out = out; a.pre = pre_out;
+  a.out_split = out_split; a.out_plane = plane(B, H / 4, W / 4, N);
+  a.B = B; a.Hin = H; a.Win = W;
+  return launch_conv1<EPI_GDN>(a, N, S(stream));
 }
 
 int iclr17_analysis_conv1x6_gdn(const float* x, int B, int H, int W, int N,
                                 const uint16_t* w_split, const float* bias, const float* beta_eff,
                                 const uint16_t* gamma_split, float* out, uint16_t* out_split,
                                 float* pre_out, void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(x && w_split && bias && beta_eff && gamma_split && (out || out_split),
                  ICLR17_EINVAL, "conv1x6_gdn: null pointer");
-  EngineArgs a;
-  memset(&a, 0, sizeof(a));
+  EngineArgs a = zero_args();
   a.in = x; a.w = (const float*)w_split; a.bias = bias; a.gbeta = beta_eff;
+  a.ggamma6 = gamma_split;
   a.out = out; a.pre = pre_out;
-  a.out_split = (unsigned short*)out_split;
-  a.out_plane = (long)B * (H / 4) * (W / 4) * N;
-  a.ggamma6 = (const unsigned short*)gamma_split;
-  a.B = B; a.Hin = H; a.Win = W; a.Hout = H / 4; a.Wout = W / 4;
-  a.gh = H / 4; a.gw = W / 4; a.tiles_y = (a.gh + 7) / 8; a.tiles_x = (a.gw + 7) / 8;
-  a.sin = 4; a.sout = 1;
-  a.tt.npx = 1; a.tt.nph = 1;
-  dim3 grid(a.tiles_x * a.tiles_y * B, 1);
-  if (N == 192)
-    hipLaunchKernelGGL((conv1_x6_kernel<192, EPI_GDN>), grid, dim3(256), 0, S(stream), a);
-  else
-    hipLaunchKernelGGL((conv1_x6_kernel<128, EPI_GDN>), grid, dim3(256), 0, S(stream), a);
-  return check_launch("conv1x6_gdn");
+  a.out_split = out_split; a.out_plane = plane(B, H / 4, W / 4, N);
+  a.B = B; a.Hin = H; a.Win = W;
+  return launch_conv1<EPI_GDN, W_SPLIT>(a, N, S(stream));
 }
 
 int iclr17_analysis_conv2_gdn_x6(const uint16_t* in_split, int B, int H, int W, int N,
                                  const float* w_packed, const float* bias, const float* beta_eff,
                                  const float* gamma_packed, const uint16_t* gamma_split,
                                  float* out, uint16_t* out_split, float* pre_out, void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(in_split && w_packed && bias && beta_eff && gamma_packed && gamma_split &&
                      (out || out_split),
                  ICLR17_EINVAL, "conv2_gdn_x6: null pointer");
-  const int h = H / 4, w = W / 4;
-  SplitIO io;
-  io.in = (const unsigned short*)in_split;
-  io.in_plane = (long)B * h * w * N;
-  io.out = (unsigned short*)out_split;
-  io.out_plane = (long)B * (h / 2) * (w / 2) * N;
-  io.gamma6 = (const unsigned short*)gamma_split;
-  return N == 192 ? launch_conv5<192, EPI_GDN>(nullptr, B, h, w, w_packed, bias, beta_eff, gamma_packed, out, pre_out, 0, nullptr, nullptr, nullptr, nullptr, S(stream), nullptr, &io)
-                  : launch_conv5<128, EPI_GDN>(nullptr, B, h, w, w_packed, bias, beta_eff, gamma_packed, out, pre_out, 0, nullptr, nullptr, nullptr, nullptr, S(stream), nullptr, &io);
+  EngineArgs a = zero_args();
+  a.w = w_packed; a.bias = bias; a.gbeta = beta_eff; a.ggamma = gamma_packed;
+  a.ggamma6 = gamma_split;
+  a.out = out; a.pre = pre_out;
+  a.in_split = in_split; a.in_plane = plane(B, H / 4, W / 4, N);
+  a.out_split = out_split; a.out_plane = plane(B, H / 8, W / 8, N);
+  a.B = B; a.Hin = H / 4; a.Win = W / 4;
+  return launch_conv5<EPI_GDN>(a, N, S(stream));
+}
+
+// w_split: nullable; the weights pre-split by iclr17_split_packed(w_packed, 25, N, N)
+static int conv3_quant_rate_x6(const char* what, const uint16_t* in_split, int B, int H, int W,
+                               int N, const float* w_packed, const uint16_t* w_split,
+                               int quant_mode, const float* noise, const float* rate_packed,
+                               const float* rate_table, float* y_out, float* y_hat,
+                               uint16_t* y_hat_split, double* bits_partial, void* stream) {
+  ICLR17_REQUIRE(quant_mode == ICLR17_QUANT_ROUND || (quant_mode == ICLR17_QUANT_NOISE && noise),
+                 ICLR17_EINVAL, "%s: bad quant mode %d / missing noise", what, quant_mode);
+  EngineArgs a = zero_args();
+  a.w = w_packed; a.out = y_out;
+  a.w6 = w_split; a.w6_plane = w_split ? 25L * N * N : 0;
+  a.qmode = quant_mode; a.noise = noise; a.rate = rate_packed; a.rtab = rate_table;
+  a.yhat = y_hat; a.partial = bits_partial;
+  a.in_split = in_split; a.in_plane = plane(B, H / 8, W / 8, N);
+  a.out_split = y_hat_split; a.out_plane = plane(B, H / 16, W / 16, N);
+  a.B = B; a.Hin = H / 8; a.Win = W / 8;
+  return launch_conv5<EPI_QUANT>(a, N, S(stream));
 }
 
 int iclr17_analysis_conv3_quant_rate_x6(const uint16_t* in_split, int B, int H, int W, int N,
@@ -2954,20 +901,12 @@ int iclr17_analysis_conv3_quant_rate_x6(const uint16_t* in_split, int B, int H, 
                                         const float* rate_packed, const float* rate_table,
                                         float* y_out, float* y_hat, uint16_t* y_hat_split,
                                         double* bits_partial, void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(in_split && w_packed && rate_packed && y_hat && bits_partial,
                  ICLR17_EINVAL, "conv3_quant_rate_x6: null pointer");
-  ICLR17_REQUIRE(quant_mode == ICLR17_QUANT_ROUND || (quant_mode == ICLR17_QUANT_NOISE && noise),
-                 ICLR17_EINVAL, "conv3_quant_rate_x6: bad quant mode %d / missing noise", quant_mode);
-  const int h = H / 8, w = W / 8;
-  SplitIO io;
-  io.in = (const unsigned short*)in_split;
-  io.in_plane = (long)B * h * w * N;
-  io.out = (unsigned short*)y_hat_split;
-  io.out_plane = (long)B * (h / 2) * (w / 2) * N;
-  return N == 192 ? launch_conv5<192, EPI_QUANT>(nullptr, B, h, w, w_packed, nullptr, nullptr, nullptr, y_out, nullptr, quant_mode, noise, rate_packed, y_hat, bits_partial, S(stream), nullptr, &io, rate_table)
-                  : launch_conv5<128, EPI_QUANT>(nullptr, B, h, w, w_packed, nullptr, nullptr, nullptr, y_out, nullptr, quant_mode, noise, rate_packed, y_hat, bits_partial, S(stream), nullptr, &io, rate_table);
+  return conv3_quant_rate_x6("conv3_quant_rate_x6", in_split, B, H, W, N, w_packed, nullptr,
+                             quant_mode, noise, rate_packed, rate_table, y_out, y_hat, y_hat_split,
+                             bits_partial, stream);
 }
 
 int iclr17_analysis_conv3_quant_rate_x6w(const uint16_t* in_split, int B, int H, int W, int N,
@@ -2976,42 +915,30 @@ int iclr17_analysis_conv3_quant_rate_x6w(const uint16_t* in_split, int B, int H,
                                          const float* rate_packed, const float* rate_table,
                                          float* y_out, float* y_hat, uint16_t* y_hat_split,
                                          double* bits_partial, void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(in_split && w_packed && w_split && rate_packed && y_hat && bits_partial,
                  ICLR17_EINVAL, "conv3_quant_rate_x6w: null pointer");
-  ICLR17_REQUIRE(quant_mode == ICLR17_QUANT_ROUND || (quant_mode == ICLR17_QUANT_NOISE && noise),
-                 ICLR17_EINVAL, "conv3_quant_rate_x6w: bad quant mode %d / missing noise", quant_mode);
-  const int h = H / 8, w = W / 8;
-  SplitIO io;
-  io.in = (const unsigned short*)in_split;
-  io.in_plane = (long)B * h * w * N;
-  io.out = (unsigned short*)y_hat_split;
-  io.out_plane = (long)B * (h / 2) * (w / 2) * N;
-  io.w6 = (const unsigned short*)w_split;
-  io.w6_plane = 25L * N * N;
-  return N == 192 ? launch_conv5<192, EPI_QUANT>(nullptr, B, h, w, w_packed, nullptr, nullptr, nullptr, y_out, nullptr, quant_mode, noise, rate_packed, y_hat, bits_partial, S(stream), nullptr, &io, rate_table)
-                  : launch_conv5<128, EPI_QUANT>(nullptr, B, h, w, w_packed, nullptr, nullptr, nullptr, y_out, nullptr, quant_mode, noise, rate_packed, y_hat, bits_partial, S(stream), nullptr, &io, rate_table);
+  return conv3_quant_rate_x6("conv3_quant_rate_x6w", in_split, B, H, W, N, w_packed, w_split,
+                             quant_mode, noise, rate_packed, rate_table, y_out, y_hat, y_hat_split,
+                             bits_partial, stream);
 }
 
 static int deconv_igdn_x6(const uint16_t* in_split, int B, int h, int w, int N,
                           const float* w_packed, const float* bias, const float* beta_eff,
                           const float* gamma_packed, const uint16_t* gamma_split, float* out,
                           uint16_t* out_split, float* pre_out, void* stream, int out_cm) {
-  ICLR17_REQUIRE(B > 0 && h > 0 && w > 0, ICLR17_EINVAL, "deconv_igdn_x6: bad shape");
-  ICLR17_REQUIRE(N == 128 || N == 192, ICLR17_EUNSUPPORTED, "channel count N=%d unsupported", N);
+  if (int rc = check_grid("deconv_igdn_x6", B, h, w, N)) return rc;
   ICLR17_REQUIRE(in_split && w_packed && bias && beta_eff && gamma_packed && gamma_split &&
                      (out || out_split),
                  ICLR17_EINVAL, "deconv_igdn_x6: null pointer");
-  SplitIO io;
-  io.in = (const unsigned short*)in_split;
-  io.in_plane = (long)B * h * w * N;
-  io.out = (unsigned short*)out_split;
-  io.out_plane = (long)B * (2 * h) * (2 * w) * N;
-  io.out_cm = out_cm;
-  io.gamma6 = (const unsigned short*)gamma_split;
-  return N == 192 ? launch_deconv5<192>(nullptr, B, h, w, w_packed, bias, beta_eff, gamma_packed, out, pre_out, S(stream), nullptr, &io)
-                  : launch_deconv5<128>(nullptr, B, h, w, w_packed, bias, beta_eff, gamma_packed, out, pre_out, S(stream), nullptr, &io);
+  EngineArgs a = zero_args();
+  a.w = w_packed; a.bias = bias; a.gbeta = beta_eff; a.ggamma = gamma_packed;
+  a.ggamma6 = gamma_split;
+  a.out = out; a.pre = pre_out;
+  a.in_split = in_split; a.in_plane = plane(B, h, w, N);
+  a.out_split = out_split; a.out_plane = plane(B, 2 * h, 2 * w, N); a.out_cm = out_cm;
+  a.B = B; a.Hin = h; a.Win = w;
+  return launch_deconv5<EPI_IGDN>(a, N, S(stream));
 }
 
 int iclr17_synthesis_deconv_igdn_x6(const uint16_t* in_split, int B, int h, int w, int N,
@@ -3032,36 +959,29 @@ int iclr17_synthesis_deconv_igdn_x6_cm(const uint16_t* in_split, int B, int h, i
                         out, out_split_cm, pre_out, stream, 1);
 }
 
-static EngineArgs bwd_args(const float* saved, const float* gammaT, float* tout) {
-  EngineArgs a;
-  memset(&a, 0, sizeof(a));
-  a.saved = saved;
-  a.ggammaT = gammaT;
-  a.tout = tout;
-  return a;
-}
-
+// ------------------------------------------------------------------ fused backward entry points
+// Each takes its upstream gradient and writes the input gradient in fp32, as x6 planes, or both.
 int iclr17_bwd_deconv3_igdn(const float* g_recon, int B, int H, int W, int N,
                             const float* w_packed, const uint16_t* w_split, const float* v_saved,
                             const float* beta_eff, const float* gamma_packed,
                             const float* gamma_packed_t,
                             const uint16_t* gamma_split, const uint16_t* gamma_t_split, float* g_v, uint16_t* g_v_split,
                             float* dn, float* colsum_gv, float* colsum_dn, void* stream) {
-  int rc = check_dims(B, H, W, N);
-  if (rc) return rc;
+  if (int rc = check_image(B, H, W, N)) return rc;
   ICLR17_REQUIRE(g_recon && (w_packed || w_split) && v_saved && beta_eff && gamma_packed &&
                      gamma_packed_t && (g_v || g_v_split) && dn, ICLR17_EINVAL, "bwd_deconv3_igdn: null pointer");
-  EngineArgs b = bwd_args(v_saved, gamma_packed_t, dn);
-  b.colsum_out = colsum_gv;
-  b.colsum_t = colsum_dn;
-  SplitIO io;
-  io.gamma6 = (const unsigned short*)gamma_split;
-  io.gammaT6 = (const unsigned short*)gamma_t_split;
-  io.in = (const unsigned short*)w_split;   // x6: the conv1_x6 kernel reads these weight planes
-  io.out = (unsigned short*)g_v_split;
-  io.out_plane = (long)B * (H / 4) * (W / 4) * N;
-  return N == 192 ? launch_conv1<192, EPI_IGDN_BWD>(g_recon, B, H, W, w_packed, nullptr, beta_eff, gamma_packed, g_v, nullptr, S(stream), &b, &io)
-                  : launch_conv1<128, EPI_IGDN_BWD>(g_recon, B, H, W, w_packed, nullptr, beta_eff, gamma_packed, g_v, nullptr, S(stream), &b, &io);
+  EngineArgs a = zero_args();
+  a.in = g_recon; a.gbeta = beta_eff; a.ggamma = gamma_packed; a.ggammaT = gamma_packed_t;
+  a.ggamma6 = gamma_split; a.ggammaT6 = gamma_t_split;
+  a.saved = v_saved; a.out = g_v; a.tout = dn; a.colsum_out = colsum_gv; a.colsum_t = colsum_dn;
+  a.out_split = g_v_split; a.out_plane = plane(B, H / 4, W / 4, N);
+  a.B = B; a.Hin = H; a.Win = W;
+  if (w_split != nullptr) {   // the contraction in x6, on the split ICLR17_W_CONV1_X6 planes
+    a.w = (const float*)w_split;
+    return launch_conv1<EPI_IGDN_BWD, W_SPLIT>(a, N, S(stream));
+  }
+  a.w = w_packed;
+  return launch_conv1<EPI_IGDN_BWD>(a, N, S(stream));
 }
 
 int iclr17_bwd_deconv_igdn(const float* g_v, const uint16_t* g_v_split, int B, int h, int w,
@@ -3070,23 +990,19 @@ int iclr17_bwd_deconv_igdn(const float* g_v, const uint16_t* g_v_split, int B, i
                            const float* gamma_packed_t,
                             const uint16_t* gamma_split, const uint16_t* gamma_t_split, float* g_v_prev, uint16_t* g_v_prev_split,
                            float* dn, float* colsum_gv, float* colsum_dn, void* stream) {
-  ICLR17_REQUIRE(B > 0 && h > 0 && w > 0, ICLR17_EINVAL, "bwd_deconv_igdn: bad shape");
-  ICLR17_REQUIRE(N == 128 || N == 192, ICLR17_EUNSUPPORTED, "channel count N=%d unsupported", N);
+  if (int rc = check_grid("bwd_deconv_igdn", B, h, w, N)) return rc;
   ICLR17_REQUIRE((g_v || g_v_split) && w_packed && v_prev && beta_eff && gamma_packed &&
                      gamma_packed_t && (g_v_prev || g_v_prev_split) && dn, ICLR17_EINVAL,
                  "bwd_deconv_igdn: null pointer");
-  EngineArgs b = bwd_args(v_prev, gamma_packed_t, dn);
-  b.colsum_out = colsum_gv;
-  b.colsum_t = colsum_dn;
-  SplitIO io;
-  io.gamma6 = (const unsigned short*)gamma_split;
-  io.gammaT6 = (const unsigned short*)gamma_t_split;
-  io.in = (const unsigned short*)g_v_split;
-  io.in_plane = (long)B * 2 * h * 2 * w * N;
-  io.out = (unsigned short*)g_v_prev_split;
-  io.out_plane = (long)B * h * w * N;
-  return N == 192 ? launch_conv5<192, EPI_IGDN_BWD>(g_v, B, 2 * h, 2 * w, w_packed, nullptr, beta_eff, gamma_packed, g_v_prev, nullptr, 0, nullptr, nullptr, nullptr, nullptr, S(stream), &b, &io)
-                  : launch_conv5<128, EPI_IGDN_BWD>(g_v, B, 2 * h, 2 * w, w_packed, nullptr, beta_eff, gamma_packed, g_v_prev, nullptr, 0, nullptr, nullptr, nullptr, nullptr, S(stream), &b, &io);
+  EngineArgs a = zero_args();
+  a.in = g_v; a.w = w_packed; a.gbeta = beta_eff; a.ggamma = gamma_packed;
+  a.ggammaT = gamma_packed_t; a.ggamma6 = gamma_split; a.ggammaT6 = gamma_t_split;
+  a.saved = v_prev; a.out = g_v_prev; a.tout = dn;
+  a.colsum_out = colsum_gv; a.colsum_t = colsum_dn;
+  a.in_split = g_v_split; a.in_plane = plane(B, 2 * h, 2 * w, N);
+  a.out_split = g_v_prev_split; a.out_plane = plane(B, h, w, N);
+  a.B = B; a.Hin = 2 * h; a.Win = 2 * w;
+  return launch_conv5<EPI_IGDN_BWD>(a, N, S(stream));
 }
 
 int iclr17_rate_bwd_partials(int h, int w) { return ((h + 7) / 8) * ((w + 7) / 8); }
@@ -3103,23 +1019,19 @@ int iclr17_bwd_deconv_rate(const float* g_v, const uint16_t* g_v_split, int B, i
                            int N, const float* w_packed, const float* y_tilde,
                            const float* rate_packed, const float* g_bpp, float count, float* g_y,
                            uint16_t* g_y_split, float* rate_partial, void* stream) {
-  ICLR17_REQUIRE(B > 0 && h > 0 && w > 0, ICLR17_EINVAL, "bwd_deconv_rate: bad shape");
-  ICLR17_REQUIRE(N == 128 || N == 192, ICLR17_EUNSUPPORTED, "channel count N=%d unsupported", N);
+  if (int rc = check_grid("bwd_deconv_rate", B, h, w, N)) return rc;
   ICLR17_REQUIRE((g_v || g_v_split) && w_packed && g_y, ICLR17_EINVAL,
                  "bwd_deconv_rate: null pointer");
   ICLR17_REQUIRE(g_bpp == nullptr || (y_tilde && rate_packed && rate_partial && count > 0),
                  ICLR17_EINVAL, "bwd_deconv_rate: rate term needs y_tilde, rate params, partials");
-  EngineArgs b = bwd_args(y_tilde, nullptr, nullptr);
-  b.gscale = g_bpp;
-  b.count = count;
-  b.rpart = rate_partial;
-  SplitIO io;
-  io.in = (const unsigned short*)g_v_split;
-  io.in_plane = (long)B * 2 * h * 2 * w * N;
-  io.out = (unsigned short*)g_y_split;
-  io.out_plane = (long)B * h * w * N;
-  return N == 192 ? launch_conv5<192, EPI_RATE_BWD>(g_v, B, 2 * h, 2 * w, w_packed, nullptr, nullptr, nullptr, g_y, nullptr, 0, nullptr, rate_packed, nullptr, nullptr, S(stream), &b, &io)
-                  : launch_conv5<128, EPI_RATE_BWD>(g_v, B, 2 * h, 2 * w, w_packed, nullptr, nullptr, nullptr, g_y, nullptr, 0, nullptr, rate_packed, nullptr, nullptr, S(stream), &b, &io);
+  EngineArgs a = zero_args();
+  a.in = g_v; a.w = w_packed; a.out = g_y;
+  a.saved = y_tilde; a.rate = rate_packed; a.gscale = g_bpp; a.count = count;
+  a.rpart = rate_partial;
+  a.in_split = g_v_split; a.in_plane = plane(B, 2 * h, 2 * w, N);
+  a.out_split = g_y_split; a.out_plane = plane(B, h, w, N);
+  a.B = B; a.Hin = 2 * h; a.Win = 2 * w;
+  return launch_conv5<EPI_RATE_BWD>(a, N, S(stream));
 }
 
 int iclr17_bwd_conv_gdn(const float* g_u, const uint16_t* g_u_split, int B, int h, int w, int N,
@@ -3128,24 +1040,21 @@ int iclr17_bwd_conv_gdn(const float* g_u, const uint16_t* g_u_split, int B, int 
                             const uint16_t* gamma_split, const uint16_t* gamma_t_split, float* g_u_prev,
                         uint16_t* g_u_prev_split, float* dn, float* colsum_gu, float* colsum_dn,
                         void* stream) {
-  ICLR17_REQUIRE(B > 0 && h > 0 && w > 0, ICLR17_EINVAL, "bwd_conv_gdn: bad shape");
-  ICLR17_REQUIRE(N == 128 || N == 192, ICLR17_EUNSUPPORTED, "channel count N=%d unsupported", N);
+  if (int rc = check_grid("bwd_conv_gdn", B, h, w, N)) return rc;
   ICLR17_REQUIRE((g_u || g_u_split) && w_packed && u_prev && beta_eff && gamma_packed &&
                      gamma_packed_t && (g_u_prev || g_u_prev_split) && dn, ICLR17_EINVAL, "bwd_conv_gdn: null pointer");
-  EngineArgs b = bwd_args(u_prev, gamma_packed_t, dn);
-  b.colsum_out = colsum_gu;
-  b.colsum_t = colsum_dn;
-  SplitIO io;
-  io.gamma6 = (const unsigned short*)gamma_split;
-  io.gammaT6 = (const unsigned short*)gamma_t_split;
-  io.in = (const unsigned short*)g_u_split;
-  io.in_plane = (long)B * h * w * N;
-  io.out = (unsigned short*)g_u_prev_split;
-  io.out_plane = (long)B * 2 * h * 2 * w * N;
-  return N == 192 ? launch_deconv5<192, EPI_GDN_BWD>(g_u, B, h, w, w_packed, nullptr, beta_eff, gamma_packed, g_u_prev, nullptr, S(stream), &b, &io)
-                  : launch_deconv5<128, EPI_GDN_BWD>(g_u, B, h, w, w_packed, nullptr, beta_eff, gamma_packed, g_u_prev, nullptr, S(stream), &b, &io);
+  EngineArgs a = zero_args();
+  a.in = g_u; a.w = w_packed; a.gbeta = beta_eff; a.ggamma = gamma_packed;
+  a.ggammaT = gamma_packed_t; a.ggamma6 = gamma_split; a.ggammaT6 = gamma_t_split;
+  a.saved = u_prev; a.out = g_u_prev; a.tout = dn;
+  a.colsum_out = colsum_gu; a.colsum_t = colsum_dn;
+  a.in_split = g_u_split; a.in_plane = plane(B, h, w, N);
+  a.out_split = g_u_prev_split; a.out_plane = plane(B, 2 * h, 2 * w, N);
+  a.B = B; a.Hin = h; a.Win = w;
+  return launch_deconv5<EPI_GDN_BWD>(a, N, S(stream));
 }
 
+// ------------------------------------------------------------------ stand-alone GDN / IGDN
 int iclr17_gdn_bwd(const float* x, const float* g, int B, int C, int H, int W, int layout,
                    int inverse, const float* beta_eff, const float* gamma_packed,
                    const float* gamma_packed_t, float* dx, float* dn, float* u_nhwc,
@@ -3157,19 +1066,14 @@ int iclr17_gdn_bwd(const float* x, const float* g, int B, int C, int H, int W, i
   ICLR17_REQUIRE(x && g && beta_eff && gamma_packed && gamma_packed_t && dx && dn, ICLR17_EINVAL,
                  "gdn_bwd: null pointer");
   const int HW = H * W;
-  dim3 grid(B * ((HW + BM - 1) / BM));
-  hipStream_t st = S(stream);
-#define ICLR17_GDNB_LAUNCH(CC, INV, LAY)                                                        \
-  hipLaunchKernelGGL((gdn_bwd_kernel<CC, INV, LAY>), grid, dim3(256), 0, st, x, g, HW, beta_eff, \
-                     gamma_packed, gamma_packed_t, dx, dn, u_nhwc)
-  if (C == 192) {
-    if (inverse) { if (layout == ICLR17_LAYOUT_NCHW) ICLR17_GDNB_LAUNCH(192, true, 0); else ICLR17_GDNB_LAUNCH(192, true, 1); }
-    else { if (layout == ICLR17_LAYOUT_NCHW) ICLR17_GDNB_LAUNCH(192, false, 0); else ICLR17_GDNB_LAUNCH(192, false, 1); }
-  } else {
-    if (inverse) { if (layout == ICLR17_LAYOUT_NCHW) ICLR17_GDNB_LAUNCH(128, true, 0); else ICLR17_GDNB_LAUNCH(128, true, 1); }
-    else { if (layout == ICLR17_LAYOUT_NCHW) ICLR17_GDNB_LAUNCH(128, false, 0); else ICLR17_GDNB_LAUNCH(128, false, 1); }
-  }
-#undef ICLR17_GDNB_LAUNCH
+  const dim3 grid(B * ((HW + BM - 1) / BM));
+  with_N(C, [&](auto c) { return with_bool(inverse, [&](auto inv) {
+    return with_bool(layout == ICLR17_LAYOUT_NHWC, [&](auto nhwc) {
+      hipLaunchKernelGGL((gdn_bwd_kernel<decltype(c)::value, decltype(inv)::value, decltype(nhwc)::value>),
+                         grid, dim3(256), 0, S(stream), x, g, HW, beta_eff, gamma_packed,
+                         gamma_packed_t, dx, dn, u_nhwc);
+      return 0;
+    }); }); });
   return check_launch("gdn_bwd");
 }
 
@@ -3181,18 +1085,13 @@ int iclr17_gdn(const float* x, int B, int C, int H, int W, int layout, int inver
                  "gdn: bad layout %d", layout);
   ICLR17_REQUIRE(x && beta_eff && gamma_packed && y, ICLR17_EINVAL, "gdn: null pointer");
   const int HW = H * W;
-  dim3 grid(B * ((HW + BM - 1) / BM));
-  hipStream_t st = S(stream);
-#define ICLR17_GDN_LAUNCH(CC, INV, LAY) \
-  hipLaunchKernelGGL((gdn_kernel<CC, INV, LAY>), grid, dim3(256), 0, st, x, HW, beta_eff, gamma_packed, y)
-  if (C == 192) {
-    if (inverse) { if (layout == ICLR17_LAYOUT_NCHW) ICLR17_GDN_LAUNCH(192, true, 0); else ICLR17_GDN_LAUNCH(192, true, 1); }
-    else { if (layout == ICLR17_LAYOUT_NCHW) ICLR17_GDN_LAUNCH(192, false, 0); else ICLR17_GDN_LAUNCH(192, false, 1); }
-  } else {
-    if (inverse) { if (layout == ICLR17_LAYOUT_NCHW) ICLR17_GDN_LAUNCH(128, true, 0); else ICLR17_GDN_LAUNCH(128, true, 1); }
-    else { if (layout == ICLR17_LAYOUT_NCHW) ICLR17_GDN_LAUNCH(128, false, 0); else ICLR17_GDN_LAUNCH(128, false, 1); }
-  }
-#undef ICLR17_GDN_LAUNCH
+  const dim3 grid(B * ((HW + BM - 1) / BM));
+  with_N(C, [&](auto c) { return with_bool(inverse, [&](auto inv) {
+    return with_bool(layout == ICLR17_LAYOUT_NHWC, [&](auto nhwc) {
+      hipLaunchKernelGGL((gdn_kernel<decltype(c)::value, decltype(inv)::value, decltype(nhwc)::value>),
+                         grid, dim3(256), 0, S(stream), x, HW, beta_eff, gamma_packed, y);
+      return 0;
+    }); }); });
   return check_launch("gdn");
 }
 

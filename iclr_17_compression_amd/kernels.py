@@ -212,7 +212,7 @@ def pack_rate(params: Sequence[Tensor]) -> Tensor:
     return out
 
 
-# ------------------------------------------------------------------------------ layers
+# ------------------------------------------------- layers, fp32 (csrc/engine_fp32.hip)
 def conv1_gdn(x: Tensor, wp: Tensor, bias: Tensor, beta_eff: Tensor, gp: Tensor, N: int,
               want_pre: bool = False):
     """analysis_17.py:14-17,33: x NCHW [B,3,H,W] → NHWC [B,H/4,W/4,N] (+ pre-GDN)."""
@@ -278,7 +278,7 @@ def deconv_igdn(h: Tensor, wp: Tensor, bias: Tensor, beta_eff: Tensor, gp: Tenso
     return (out, pre) if want_pre else out
 
 
-# ------------------------------------------------------------- x6 (bf16x6) precision mode
+# ----------------------------- x6 (bf16x6) precision mode (csrc/engine_fp32.hip)
 PRECISIONS = ("x6", "h3", "fp32", "bf16")
 _precision = os.environ.get("ICLR17_PRECISION", "h3")
 _scoped = threading.local()   # .mode: the thread's innermost precision_scope, if any
@@ -952,7 +952,7 @@ def deconv3_h3(hs: Tensor, w_h3: Tensor, bias: Tensor, x_ref: Optional[Tensor] =
 
 def _deconv3_halo(fn, hs, B, h4, w4, N, wp, bias, x_ref, want_recon, sse_unclipped, bits=None,
                   bits_per_image=False, flag=None):
-    """The halo-tiled deconv3 kernels. Without ``flag`` (x6, bf16) the entry ``fn`` has a
+    """The halo-tiled deconv3 kernels (csrc/deconv3_halo.hip). Without ``flag`` (x6, bf16) the entry ``fn`` has a
     ``_bits`` twin that also reduces the bit partials; the h3 entry is one function that always
     takes the bit arguments and, last, the chain's range flag."""
     B, h4, w4, N, H, W = _act_dims((B, h4, w4, N), 4)
@@ -1320,7 +1320,7 @@ def rate_bits(z: Tensor, rate_packed: Tensor) -> Tensor:
     return partial
 
 
-# ------------------------------------------------------------------------------ backward
+# ------------------------- backward (fused kernels: csrc/engine_fp32.hip, engine.h)
 def grad_recon(recon: Tensor, x: Tensor, g_mse: Optional[Tensor], g_clip: Optional[Tensor]) -> Tensor:
     """∂L/∂recon for L using mean((recon−x)²) (g_mse, 0-dim) and/or clamp(recon,0,1) (g_clip)."""
     _check(recon, "recon")
