@@ -86,6 +86,8 @@ SIGNATURES = {
                                                 _P]),
     "iclr17_reduce_partials": (_I, [_P, _I, _I, _P, _P, _D, _P]),
     "iclr17_resized_crop_batch": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "iclr17_image_ingest_u8": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "iclr17_image_egress_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "iclr17_adam_step": (_I, [_P, _I, ctypes.c_long, _D, _D, _D, _D, ctypes.c_long, _F, _P]),
     "iclr17_entropy_tables": (_I, [_P, _I, _I, _P, _P]),
     "iclr17_rans_capacity": (ctypes.c_long, [_I, _I, _I, _I]),

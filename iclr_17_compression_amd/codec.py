@@ -1,0 +1,287 @@
+"""Image-file codec: 8-bit RGB images of any size in, self-describing byte strings out, 8-bit
+images back (``ImageCompressor.compress_images`` / ``decompress_images`` / ``evaluate_images`` and
+the command line below). The reference has neither padding nor a bitstream, so the contract is
+this module's own.
+
+Padding. The transforms take multiples of 16, so an H×W image travels on the smallest *canvas*
+``canvas(H, W)`` that holds it, top left, with its bottom and right edges replicated
+(kernels.image_ingest); decoding crops the canvas back to H×W (kernels.image_egress). Images are
+batched by canvas, so none is padded by more than 15 rows or columns.
+
+Container. One blob per image: a 28-byte little-endian header, then the image's string exactly as
+``ImageCompressor.compress`` emits it (P uint32 stream word counts, then the rANS words).
+
+    struct "<4sBBHHxxIIQ":  magic b"I17C" | version u8 = 1 | P u8 (streams per image) |
+                            N u16 (channels) | K u16 (entropy alphabet half-width) | 2 pad bytes |
+                            H u32 | W u32 (the true size) | fingerprint u64
+
+The fingerprint is the first 8 bytes (little-endian) of the SHA-256 over the model's state_dict
+tensors, in sorted key order, as fp32 little-endian bytes: a stream decoded with other weights
+fails loudly instead of returning noise.
+
+Precision. The stream does not record the precision mode (kernels.precision()). The latents decode
+bit-exactly in every mode; the synthesis transform then runs in the decoder's mode, so decoded
+pixels may differ by one 8-bit step between modes. Within one mode the decoded bytes are
+reproducible and do not depend on the batch an image travelled in.
+
+    python -m iclr_17_compression_amd.codec encode IN.png OUT.i17c --weights CKPT [--N 192]
+    python -m iclr_17_compression_amd.codec decode IN.i17c OUT.png --weights CKPT
+    python -m iclr_17_compression_amd.codec eval IMG... --weights CKPT [--ms-ssim]
+"""
+from __future__ import annotations
+
+import argparse
+import hashlib
+import json
+import math
+import struct
+import sys
+from collections import namedtuple
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import kernels
+from ._lib import Iclr17Error
+from .packcache import PackCache
+
+MAGIC = b"I17C"
+VERSION = 1
+HEADER = struct.Struct("<4sBBHHxxIIQ")
+assert HEADER.size == 28
+
+Header = namedtuple("Header", "P N K H W fingerprint")
+
+
+# ------------------------------------------------------------------------------ canvas
+def canvas(H: int, W: int) -> Tuple[int, int]:
+    """The smallest multiples of 16 ≥ H and W."""
+    if H < 1 or W < 1:
+        raise Iclr17Error(f"iclr17: codec: image size {H}x{W} must be at least 1x1")
+    return -(-H // 16) * 16, -(-W // 16) * 16
+
+
+def _group(keys: Sequence, max_batch: int) -> List[List[int]]:
+    """Indices grouped by equal key, at most ``max_batch`` per group; groups in the order their
+    first member appears, indices ascending inside a group."""
+    if max_batch < 1:
+        raise Iclr17Error(f"iclr17: codec: max_batch must be at least 1 (got {max_batch})")
+    by_key: Dict[object, List[int]] = {}
+    for i, k in enumerate(keys):
+        by_key.setdefault(k, []).append(i)
+    return [idx[s:s + max_batch] for idx in by_key.values() for s in range(0, len(idx), max_batch)]
+
+
+def group_by_canvas(shapes: Sequence[Tuple[int, int]], max_batch: int = 64) -> List[List[int]]:
+    """Index groups of ``shapes`` [(H, W)]: every group holds images of one canvas, at most
+    ``max_batch`` of them (Kodak's landscape and portrait images: two groups)."""
+    return _group([canvas(H, W) for H, W in shapes], max_batch)
+
+
+# ------------------------------------------------------------------------------ container
+def fingerprint(model) -> int:
+    """u64 of the model's weights (module docstring); cached on the model until a parameter
+    changes (the parameters' version counters, as packcache does for the packed layouts)."""
+    sd = model.state_dict()
+    keys = sorted(sd)
+    cache = model.__dict__.setdefault("_codec_cache", PackCache())
+
+    def build() -> int:
+        h = hashlib.sha256()
+        for k in keys:
+            h.update(sd[k].detach().to(torch.float32).cpu().contiguous().numpy().astype("<f4").tobytes())
+        return int.from_bytes(h.digest()[:8], "little")
+
+    return cache.get("fingerprint", [sd[k] for k in keys], build)
+
+
+def pack_header(P: int, N: int, K: int, H: int, W: int, fingerprint: int) -> bytes:
+    if H < 1 or W < 1:
+        raise Iclr17Error(f"iclr17: codec: image size {H}x{W} must be at least 1x1")
+    if not (1 <= P <= 255 and 1 <= N <= 65535 and 1 <= K <= 65535 and H < 2 ** 32 and W < 2 ** 32):
+        raise Iclr17Error(f"iclr17: codec: header field out of range (P={P} N={N} K={K} {H}x{W})")
+    return HEADER.pack(MAGIC, VERSION, P, N, K, H, W, fingerprint & (2 ** 64 - 1))
+
+
+def parse_header(blob: bytes, N: Optional[int] = None, fingerprint: Optional[int] = None) -> Header:
+    """The header of a blob; with ``N`` / ``fingerprint`` (the decoding model's) also checked
+    against them. The payload (blob[HEADER.size:]) is checked by ``decompress``."""
+    if len(blob) < HEADER.size:
+        raise Iclr17Error(f"iclr17: codec: truncated header ({len(blob)} of {HEADER.size} bytes)")
+    magic, version, P, n, K, H, W, fp = HEADER.unpack_from(blob)
+    if magic != MAGIC:
+        raise Iclr17Error(f"iclr17: codec: bad magic {magic!r} (not an I17C stream)")
+    if version != VERSION:
+        raise Iclr17Error(f"iclr17: codec: unknown version {version} (this build reads {VERSION})")
+    if H == 0 or W == 0:
+        raise Iclr17Error(f"iclr17: codec: image size {H}x{W} must be at least 1x1")
+    if N is not None and n != N:
+        raise Iclr17Error(f"iclr17: codec: the stream is for N={n}, the model has N={N}")
+    if fingerprint is not None and fp != fingerprint:
+        raise Iclr17Error(f"iclr17: codec: weights fingerprint mismatch (stream {fp:016x}, model "
+                          f"{fingerprint:016x}): the stream was coded with other weights")
+    return Header(P, n, K, H, W, fp)
+
+
+# ------------------------------------------------------------------------------ batches
+def as_u8_hwc(image) -> np.ndarray:
+    """A uint8 HWC RGB array (numpy or torch) as a contiguous numpy array."""
+    a = image.detach().cpu().numpy() if isinstance(image, torch.Tensor) else np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise Iclr17Error(f"iclr17: codec: images are uint8 HWC RGB arrays of at least 1x1 (got "
+                          f"{a.dtype} {a.shape})")
+    a = np.ascontiguousarray(a)
+    return a if a.flags.writeable else a.copy()   # torch.from_numpy wants a writable array
+
+
+def upload_packed(images: Sequence[np.ndarray], device):
+    """The images back to back in one pinned buffer and one upload → (device uint8 tensor, byte
+    offsets, [(H, W)])."""
+    sizes = [im.size for im in images]
+    offsets = [0] + list(np.cumsum(sizes)[:-1])
+    host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
+    flat = host.numpy()
+    for im, o in zip(images, offsets):
+        flat[o:o + im.size] = im.reshape(-1)
+    return host.to(device, non_blocking=True), [int(o) for o in offsets], [im.shape[:2] for im in images]
+
+
+def compress_images(net, images, max_batch: int = 64,
+                    streams_per_image: int = kernels.STREAMS_PER_IMAGE,
+                    K: int = kernels.ENTROPY_K) -> List[bytes]:
+    imgs = [as_u8_hwc(im) for im in images]
+    device = next(net.parameters()).device
+    fp, N = fingerprint(net), net.out_channel_N
+    blobs: List[Optional[bytes]] = [None] * len(imgs)
+    for idx in group_by_canvas([im.shape[:2] for im in imgs], max_batch):
+        group = [imgs[i] for i in idx]
+        packed, offsets, shapes = upload_packed(group, device)
+        x = kernels.image_ingest(packed, offsets, shapes, canvas(*shapes[0]))
+        enc = net.compress(x, streams_per_image=streams_per_image, K=K)
+        for i, (H, W), s in zip(idx, shapes, enc["strings"]):
+            blobs[i] = pack_header(streams_per_image, N, K, H, W, fp) + s
+    return blobs
+
+
+def decode_groups(net, blobs, max_batch: int, refs=None):
+    """``decompress_images``; with ``refs`` (the original uint8 images, one per blob) also each
+    image's Σ (decoded − original)² → ([uint8 HWC arrays], [int] | None)."""
+    device = next(net.parameters()).device
+    fp, N = fingerprint(net), net.out_channel_N
+    heads = [parse_header(b, N, fp) for b in blobs]
+    for b, h in zip(blobs, heads):
+        # decompress reads the payload as 16-bit words and checks the counts; an odd rest cannot
+        # even be read that way
+        if len(b) < HEADER.size + 4 * h.P or (len(b) - HEADER.size) % 2:
+            raise Iclr17Error(f"iclr17: codec: truncated stream ({len(b)} bytes)")
+    out: List[Optional[np.ndarray]] = [None] * len(blobs)
+    sses: Optional[List[Optional[int]]] = [None] * len(blobs) if refs is not None else None
+    for idx in _group([canvas(h.H, h.W) + (h.P, h.K) for h in heads], max_batch):
+        h0 = heads[idx[0]]
+        Hc, Wc = canvas(h0.H, h0.W)
+        dec = net.decompress([blobs[i][HEADER.size:] for i in idx], (Hc // 16, Wc // 16),
+                             streams_per_image=h0.P, K=h0.K, device=device)
+        shapes = [(heads[i].H, heads[i].W) for i in idx]
+        ref = None
+        if refs is not None:
+            group = [refs[i] for i in idx]
+            if [g.shape[:2] for g in group] != shapes:
+                raise Iclr17Error("iclr17: codec: a reference image's size differs from its stream's")
+            ref, offsets, _ = upload_packed(group, device)
+        else:
+            offsets = [int(o) for o in np.cumsum([0] + [3 * H * W for H, W in shapes[:-1]])]
+        dst, sse = kernels.image_egress(dec["x_hat"], offsets, shapes, ref)
+        flat = dst.numpy()
+        for k, (i, o, (H, W)) in enumerate(zip(idx, offsets, shapes)):
+            out[i] = flat[o:o + 3 * H * W].reshape(H, W, 3).copy()
+            if sses is not None:
+                sses[i] = int(sse[k])
+    return out, sses
+
+
+def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64) -> List[dict]:
+    imgs = [as_u8_hwc(im) for im in images]
+    blobs = compress_images(net, imgs, max_batch=max_batch)
+    recons, sses = decode_groups(net, blobs, max_batch, refs=imgs)
+    device = next(net.parameters()).device
+    res = []
+    for im, blob, rec, sse in zip(imgs, blobs, recons, sses):
+        H, W = im.shape[:2]
+        r = {"bytes": len(blob), "bpp": 8 * len(blob) / (H * W), "sse_u8": sse,
+             "psnr_u8": 10.0 * math.log10(255.0 ** 2 * 3 * H * W / sse) if sse else math.inf,
+             "recon": rec}
+        if want_msssim:
+            r["ms_ssim"] = r["ms_ssim_db"] = None
+            if kernels.query("iclr17_ms_ssim_workspace_size", 1, H, W):   # 0: too small for 5 levels
+                def unit(a):
+                    return (torch.from_numpy(a).to(device).permute(2, 0, 1).float() / 255)[None].contiguous()
+                ms = float(kernels.ms_ssim(unit(rec), unit(im), data_range=1.0)[0])
+                r["ms_ssim"] = ms
+                r["ms_ssim_db"] = -10.0 * math.log10(1.0 - ms) if ms < 1.0 else math.inf
+        res.append(r)
+    return res
+
+
+# ------------------------------------------------------------------------------ command line
+def _load_image(path: str) -> np.ndarray:
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"))   # datasets.py:21
+
+
+def _model(args):
+    from .model import ImageCompressor, load_model
+    if not torch.cuda.is_available():
+        raise Iclr17Error("iclr17: codec: no ROCm GPU (MI355X / gfx950) — there is no CPU implementation")
+    net = ImageCompressor(out_channel_N=args.N)
+    load_model(net, args.weights)
+    return net.to(torch.device("cuda:0")).eval()
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    common = argparse.ArgumentParser(add_help=False)
+    common.add_argument("--weights", required=True, help="checkpoint (model.load_model)")
+    common.add_argument("--N", type=int, default=192, help="channel count of the checkpoint")
+    common.add_argument("--precision", choices=kernels.PRECISIONS, default=None)
+    ap = argparse.ArgumentParser(prog="python -m iclr_17_compression_amd.codec",
+                                 description="Code 8-bit RGB image files with the Ballé-2017 codec.")
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    enc = sub.add_parser("encode", parents=[common], help="IN.png OUT.i17c")
+    enc.add_argument("input")
+    enc.add_argument("output")
+    dec = sub.add_parser("decode", parents=[common], help="IN.i17c OUT.png")
+    dec.add_argument("input")
+    dec.add_argument("output")
+    ev = sub.add_parser("eval", parents=[common], help="IMG...: one JSON line per image and a mean")
+    ev.add_argument("images", nargs="+")
+    ev.add_argument("--ms-ssim", action="store_true")
+    args = ap.parse_args(argv)
+    net = _model(args)
+    with kernels.precision_scope(args.precision or kernels.precision()):
+        if args.cmd == "encode":
+            blob = net.compress_images([_load_image(args.input)])[0]
+            with open(args.output, "wb") as f:
+                f.write(blob)
+        elif args.cmd == "decode":
+            from PIL import Image
+            with open(args.input, "rb") as f:
+                blob = f.read()
+            Image.fromarray(net.decompress_images([blob])[0]).save(args.output, format="PNG")
+        else:
+            imgs = [_load_image(p) for p in args.images]
+            rows = net.evaluate_images(imgs, want_msssim=args.ms_ssim)
+            for p, im, r in zip(args.images, imgs, rows):
+                print(json.dumps({"name": p, "H": im.shape[0], "W": im.shape[1], "bytes": r["bytes"],
+                                  "bpp": r["bpp"], "psnr_u8": r["psnr_u8"],
+                                  "ms_ssim": r.get("ms_ssim")}))
+            ms = [r["ms_ssim"] for r in rows if r.get("ms_ssim") is not None]
+            print(json.dumps({"name": "mean", "images": len(rows),
+                              "bpp": float(np.mean([r["bpp"] for r in rows])),
+                              "psnr_u8": float(np.mean([r["psnr_u8"] for r in rows])),
+                              "ms_ssim": float(np.mean(ms)) if ms else None}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

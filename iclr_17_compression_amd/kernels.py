@@ -1192,6 +1192,100 @@ def _check_f64(t: Tensor) -> None:
         raise Iclr17Error("iclr17: partial sums must be a 2-D float64 GPU tensor")
 
 
+# ---------------------------------------------------------------- image files (§1 f5)
+def _image_desc(what: str, nbytes: int, offsets, shapes, canvas) -> Tensor:
+    """The int64 [B][4] descriptors {byte offset, H, W, 0} of uint8 HWC images packed in a buffer
+    of ``nbytes``, checked on the host (the library cannot: it sees device memory): every image
+    fits the canvas and lies inside the buffer. A CPU tensor."""
+    Hc, Wc = int(canvas[0]), int(canvas[1])
+    _check_image_dims(Hc, Wc)
+    if len(offsets) != len(shapes) or not len(shapes):
+        raise Iclr17Error(f"iclr17: {what}: {len(offsets)} offsets for {len(shapes)} images")
+    rows = []
+    for b, (off, (H, W)) in enumerate(zip(offsets, shapes)):
+        off, H, W = int(off), int(H), int(W)
+        if not (1 <= H <= Hc and 1 <= W <= Wc):
+            raise Iclr17Error(f"iclr17: {what}: image {b} is {H}x{W}, outside the canvas {Hc}x{Wc}")
+        if off < 0 or off + 3 * H * W > nbytes:
+            raise Iclr17Error(f"iclr17: {what}: image {b} (bytes {off}..{off + 3 * H * W}) lies "
+                              f"outside the buffer of {nbytes} bytes")
+        rows.append((off, H, W, 0))
+    return torch.tensor(rows, dtype=torch.int64)
+
+
+def _check_u8(t: Tensor, name: str) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1:
+        raise Iclr17Error(f"iclr17: {name} must be a 1-D uint8 tensor")
+
+
+def _check_u8_gpu(t: Tensor, name: str) -> Tensor:
+    if t.device.type != "cuda":
+        raise Iclr17Error(f"iclr17: {name} is on {t.device}; this framework runs only on a ROCm GPU "
+                          "(MI355X / gfx950) — there is no CPU implementation")
+    return t.contiguous()
+
+
+def image_ingest(src_u8: Tensor, offsets, shapes, canvas) -> Tensor:
+    """uint8 HWC RGB images of any sizes, packed in ``src_u8`` at byte ``offsets`` (any alignment)
+    with ``shapes`` [(H, W)], → the fp32 batch [B,3,Hc,Wc] the analysis transform reads: /255 as
+    ToTensor, each image at the top left of the ``canvas`` (Hc, Wc), its bottom and right edges
+    replicated into the padding."""
+    _check_u8(src_u8, "image bytes")
+    desc = _image_desc("image_ingest", src_u8.numel(), offsets, shapes, canvas)
+    src_u8 = _check_u8_gpu(src_u8, "image bytes")
+    Hc, Wc = int(canvas[0]), int(canvas[1])
+    B = desc.shape[0]
+    out = torch.empty(B, 3, Hc, Wc, device=src_u8.device, dtype=torch.float32)
+    call("iclr17_image_ingest_u8", _p(src_u8), _p(desc.to(src_u8.device)), B, Hc, Wc, _p(out),
+         _stream(src_u8))
+    return out
+
+
+def image_egress_device(recon: Tensor, offsets, shapes, ref: Optional[Tensor] = None):
+    """``image_egress`` without the transfer: → (buffer, dst, sse | None, status), all on the
+    device; dst, sse and status are views of the one uint8 ``buffer`` ({sse int64 [B], status
+    int32, 4 spare bytes, the packed pixels}), so one copy brings all three to the host. Nothing
+    is checked here: the caller reads ``status``."""
+    _check(recon, "reconstruction", 4)
+    B, C, Hc, Wc = recon.shape
+    if C != 3:
+        raise Iclr17Error(f"iclr17: image_egress takes a [B,3,Hc,Wc] reconstruction (got {C} channels)")
+    total = max(int(o) + 3 * int(h) * int(w) for o, (h, w) in zip(offsets, shapes)) if len(shapes) else 0
+    if ref is not None:
+        _check_u8(ref, "reference bytes")
+        total = ref.numel()
+    desc = _image_desc("image_egress", total, offsets, shapes, (Hc, Wc))
+    if desc.shape[0] != B:
+        raise Iclr17Error(f"iclr17: image_egress: {desc.shape[0]} images for a batch of {B}")
+    if ref is not None:
+        ref = _check_u8_gpu(ref, "reference bytes")
+    buf = torch.empty(8 * B + 8 + total, device=recon.device, dtype=torch.uint8)
+    sse = buf[:8 * B].view(torch.int64)
+    status = buf[8 * B:8 * B + 4].view(torch.int32)
+    dst = buf[8 * B + 8:]
+    call("iclr17_image_egress_u8", _p(recon.contiguous()), _p(desc.to(recon.device)), B, Hc, Wc,
+         _p(dst), _p(ref), _p(sse) if ref is not None else None, _p(status), _stream(recon))
+    return buf, dst, (sse if ref is not None else None), status
+
+
+def image_egress(recon: Tensor, offsets, shapes, ref: Optional[Tensor] = None):
+    """The reconstruction [B,3,Hc,Wc] (fp32, on the GPU) → the 8-bit images a user saves:
+    round-half-even of clamp(recon, 0, 1)·255 over each image's own H×W (``shapes``), uint8 HWC at
+    byte ``offsets`` of the returned packed buffer. With ``ref`` (the original images in that
+    layout, on the GPU) also the per-image Σ (dst − ref)² (int64 [B], exact and order-independent).
+    Returns (dst_u8, sse | None) on the HOST: pixels, sums and the kernel's status word come over
+    in one transfer, and a non-finite value inside an image (in the h3 mode: the poison of an
+    activation that did not fit the form) raises Iclr17Error. The padding is never looked at."""
+    buf, _, sse, _ = image_egress_device(recon, offsets, shapes, ref)
+    host = buf.cpu()
+    B = recon.shape[0]
+    if int(host[8 * B:8 * B + 4].view(torch.int32).item()):
+        if precision() == "h3":
+            raise Iclr17Error(H3_RANGE_MESSAGE)
+        raise Iclr17Error("iclr17: image_egress: non-finite reconstruction")
+    return host[8 * B + 8:], (host[:8 * B].view(torch.int64) if sse is not None else None)
+
+
 # ------------------------------------------------------------------------------ modules
 def gdn(x: Tensor, beta_eff: Tensor, gp: Tensor, inverse: bool) -> Tensor:
     """GDN.forward (models/GDN.py:64-94) on a 4-D tensor; keeps the input's memory format."""

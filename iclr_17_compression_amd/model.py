@@ -225,6 +225,44 @@ class ImageCompressor(nn.Module):
                                     None, False)
         return {"y_hat": y_hat.permute(0, 3, 1, 2).contiguous(), "x_hat": clipped}
 
+    # ------------------------------------------------------------- image files (§1 f5, codec.py)
+    @torch.no_grad()
+    def compress_images(self, images, max_batch: int = 64,
+                        streams_per_image: int = kernels.STREAMS_PER_IMAGE,
+                        K: int = kernels.ENTROPY_K):
+        """8-bit images of any sizes ≥ 1×1 (a sequence of uint8 HWC RGB arrays, numpy or torch) →
+        one self-describing blob per image, in input order: codec.py's 28-byte header (true size,
+        N, P, K, weights fingerprint) + the image's ``compress`` string. Images are batched by
+        canvas (the size rounded up to multiples of 16, edges replicated), at most ``max_batch``
+        per batch; each batch is one pinned upload, kernels.image_ingest and ``compress`` as it
+        stands (its x6 fall-back on an h3 overflow included). The precision mode is not recorded:
+        the latents decode bit-exactly in every mode, decoded pixels may differ by one 8-bit step
+        between modes, and within one mode a blob does not depend on its batch."""
+        from . import codec
+        return codec.compress_images(self, images, max_batch, streams_per_image, K)
+
+    @torch.no_grad()
+    def decompress_images(self, blobs, max_batch: int = 64):
+        """Inverse of ``compress_images``: blobs → uint8 HWC numpy arrays of the true sizes, in
+        input order (``decompress`` per canvas batch, then kernels.image_egress: round-half-even of
+        the clipped reconstruction·255, cropped). Raises Iclr17Error on a foreign or truncated
+        blob, another N or other weights (the header's fingerprint). Within one precision mode
+        the bytes are reproducible and independent of the batch; between modes a pixel may differ
+        by one 8-bit step."""
+        from . import codec
+        return codec.decode_groups(self, list(blobs), max_batch)[0]
+
+    @torch.no_grad()
+    def evaluate_images(self, images, want_msssim: bool = False, max_batch: int = 64):
+        """The real codec path per image, compress_images then decompress_images, measured on
+        the 8-bit decoded image as codecs are reported: a dict per image with ``bytes``, ``bpp`` =
+        8·len(blob)/(H·W) (header included, true pixel count), ``sse_u8`` (int), ``psnr_u8`` =
+        10·log10(255²·3HW / sse_u8) (float64; inf at 0), ``recon`` (uint8 HWC) and, with
+        ``want_msssim``, ``ms_ssim`` / ``ms_ssim_db`` of the cropped pair (None for an image too
+        small for 5 levels). Precision as ``decompress_images``."""
+        from . import codec
+        return codec.evaluate_images(self, images, want_msssim, max_batch)
+
     @torch.no_grad()
     def evaluate(self, x: torch.Tensor, want_y: bool = False,
                  want_msssim: bool = False, h3_overflow: str = "nan") -> Dict[str, torch.Tensor]:

@@ -327,6 +327,28 @@ int iclr17_ssim_bwd(const float* x, const float* y, int B, int H, int W, int sav
 int iclr17_resized_crop_batch(const uint8_t* src, const int64_t* desc, int B, int S, int max_ch,
                               const int32_t* taps, uint8_t* tmp, float* out, void* stream);
 
+/* ---------------------------------------------------------------- image files (§1 f5)
+ * 8-bit images of any size in and out of the codec (csrc/imageio.hip; the reference feeds fp32
+ * crops and has no such step). src / dst / ref: uint8 HWC RGB images in one packed buffer; desc:
+ * int64 [B][4] = {byte offset of image b (any alignment), H_b, W_b, 0}. All images of a call share
+ * the canvas Hc×Wc (multiples of 16, ≥ every H_b, W_b); the caller guarantees 1 ≤ H_b ≤ Hc,
+ * 1 ≤ W_b ≤ Wc and that every image lies inside its buffer (the descriptors are device memory:
+ * the library cannot check them). No byte outside an image's own H_b·W_b·3 is read or written. */
+/* out NCHW fp32 [B,3,Hc,Wc]: out[b,c,i,j] = float(src_b[min(i,H_b−1)][min(j,W_b−1)][c]) / 255.0f
+ * (a true fp32 division, torchvision's ToTensor): the image at the top left, its bottom and right
+ * edges replicated into the padding. */
+int iclr17_image_ingest_u8(const uint8_t* src, const int64_t* desc, int B, int Hc, int Wc,
+                           float* out, void* stream);
+/* dst_b[i][j][c] = (uint8) rintf(fminf(fmaxf(recon[b,c,i,j], 0), 1) · 255.0f) for i < H_b, j < W_b
+ * (half to even, no FMA), recon NCHW fp32 [B,3,Hc,Wc]; recon's padding never influences a result.
+ * ref (nullable; the original images, laid out as dst): sse[b] = Σ (dst − ref)² over image b's
+ * H_b·W_b·3 values (int64 [B]; integer atomics, so bitwise reproducible). status (int32):
+ * |= 1 when a recon value inside an image's own region is not finite (its pixel is then 0). The
+ * call clears sse and status on the stream first. */
+int iclr17_image_egress_u8(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
+                           uint8_t* dst, const uint8_t* ref, int64_t* sse, int32_t* status,
+                           void* stream);
+
 /* train.py:106-112: element-wise gradient clamp to ±grad_clip (≤ 0: none; written back to the
  * gradient) fused with one torch.optim.Adam step (no weight decay, no amsgrad) over n_tensors
  * parameter tensors in one launch. desc: device int64 [n_tensors][5] = {param, grad, exp_avg,
