@@ -26,8 +26,8 @@
 //
 // Epilogue: x = acc·2⁻¹¹/(σ_a·σ_w) + bias (a power-of-two scale: exact), then the GDN / IGDN
 // contraction n = Σ_j γ[i][j]·x_j² in the h3 form (γ split into two fp16 planes, staged in LDS
-// half the output channels at a time; x² scaled per pixel by a power of two and split in
-// registers), y = x·√(β + n) | x / √(β + n), and y stored
+// a quarter of the input channels at a time; x² scaled per pixel by a power of two and split in
+// registers, each 16-channel block once), y = x·√(β + n) | x / √(β + n), and y stored
 // as fp32 and/or in the h3 form (NHWC, or chunk-major [2][B][N/32][h][w][32]) and/or the x6
 // split form.
 #include <stdio.h>
@@ -176,10 +176,16 @@ struct HK {
   static constexpr int NBI = SB / 1024;
   static constexpr int NST = NS;
   static constexpr int MAIN = NPB * PBUF + NST * SB + 1024;
-  static constexpr int NTH = NT / 2;           // epilogue: output tiles per pass
   static constexpr int KB = CO / 16;           // epilogue: 16-channel k-blocks
-  static constexpr int GBL = 2 * NTH * KB;     // epilogue: γ fragment blocks per pass (1 KB)
-  static constexpr int LDS0 = MAIN > GBL * 1024 ? MAIN : GBL * 1024;
+  static constexpr int KQ = KB / 4;            // epilogue: k-blocks per γ stage (a k-quarter)
+  static constexpr int GBL = 2 * NT * KQ;      // epilogue: γ fragment blocks per stage (1 KB each)
+  // epilogue, the 16-row N = 192 kernels (two waves per SIMD: 256 registers a lane, of which the
+  // conv accumulators and the contraction's sums would take 96 each): NPK accumulator tiles wait
+  // in lane-private LDS rows behind the two γ stages, 4 KB per tile and wave
+  static constexpr int NPK = TH == 16 && NT == 6 ? 2 : 0;
+  static constexpr int PKOFF = 2 * GBL * 1024;
+  static constexpr int EPIB = PKOFF + NPK * NW * 4096;
+  static constexpr int LDS0 = MAIN > EPIB ? MAIN : EPIB;
   static constexpr int BBOFF = (LDS0 + 1023) / 1024 * 1024;
   static constexpr int LDS = BBOFF + 2048 + 256;   // + bias, β_eff, the epilogue's sink
   static_assert(SB % 1024 == 0, "weight stage");
@@ -659,6 +665,30 @@ __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, in
   const float dsc = a.wscale[1];   // 2⁻¹¹/(σ_a·σ_w): exact
   const long hb0 = h3_out_off(a, b, oy, ox, CO, 16 * eh), hb1 = h3_out_off(a, b, oy, ox, CO, 16 * eh + 8);
   const long hstep = h3_out_step32(a);
+  // γ staged in four k-quarter stages q into two alternating buffers (36 KB each at N = 192):
+  // every output row of both planes for k-blocks q·KQ .. q·KQ + KQ − 1; block (plane, i, kk) ←
+  // elane (er32, eh) γ_p[32i + er32][16kb + 8eh .. +7] (the [CO/8][CO][8] packing). Each wave
+  // issues GK pieces per stage (sink loads as padding), so vmcnt(GK) leaves exactly the newer
+  // stage in flight. Stage q+1 lands while stage q is contracted; stages 0 and 1 go out here,
+  // under the bias and scale arithmetic below.
+  constexpr int KB = KK::KB, KQ = KK::KQ, QBL = KK::GBL, GK = (QBL + NW - 1) / NW, NPK = KK::NPK;
+  static_assert(KB % 4 == 0 && NT % 2 == 0, "GDN epilogue: k-quarters, pairs of k-blocks per tile");
+  auto stage_g = [&](int q) {
+#pragma unroll
+    for (int k = 0; k < GK; ++k) {
+      const int blk = k * NW + ewave;
+      if (blk >= QBL) {   // the epilogue's own sink: the main loop's may lie under a γ buffer
+        sink4((unsigned char*)sbb + 2048);
+        continue;
+      }
+      const int p = blk / (NT * KQ), rem = blk - p * NT * KQ;
+      const int i = rem / KQ, kb = q * KQ + rem - i * KQ;
+      glds16(a.gamma_h3 + (long)p * CO * CO + ((2 * kb + eh) * CO + 32 * i + er32) * 8,
+             smem + (q & 1) * QBL * 1024 + blk * 1024);
+    }
+  };
+  stage_g(0);
+  stage_g(1);
 #pragma unroll
   for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -667,8 +697,6 @@ __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, in
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][4 * m + j] = acc[i][4 * m + j] * dsc + bv[j];   // x = conv + bias
     }
-  constexpr int NTH = KK::NTH, KB = KK::KB;
-  static_assert(NT % 2 == 0, "GDN epilogue: pairs of 32-channel tiles");
   bool ovf = false, wid = false;
   // The channel contraction n_i = Σ_j γ_ij·x_j² in the h3 form. x² of a pixel (rounded to fp32,
   // as conv2d(x², γ) sees it) is scaled by a power of two s_p that puts the pixel's largest x²
@@ -696,98 +724,107 @@ __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, in
   const float sp = ldexpf(1.0f, ep);
   // n = acc_n · 2⁻¹¹ / (σ_γ · s_p) = acc_n · gamma_scale[1] · σ_a / s_p (powers of two: exact)
   const float nsc = ldexpf(a.gamma_scale[1] * kH3Sa, -ep);
-  // γ staged in four half-passes q = (pass hf, k-half kh) into two alternating 36-KB buffers: the
-  // rows 32·(hf·NTH + il) .. of both planes for k-blocks kh·KH .. kh·KH + KH − 1; block (plane, il,
-  // kk) ← elane (er32, eh) γ_p[32(hf·NTH + il) + er32][16kb + 8eh .. +7] (the [CO/8][CO][8]
-  // packing). Each wave issues GK pieces per stage (sink loads as padding), so vmcnt(GK) leaves
-  // exactly the newer stage in flight. Stage q+1 lands while stage q is contracted.
-  constexpr int KH = KB / 2, HBL = 2 * NTH * KH, GK = (HBL + NW - 1) / NW;
-  static_assert(KB % 2 == 0 && 2 * HBL * 1024 <= KK::LDS0, "γ half-stages");
-  auto stage_g = [&](int q) {
-    const int hf = q >> 1, kh = q & 1;
+  // One pass over the k-blocks: every k-block's x² is split once and contracted into all NT
+  // output tiles' sums n, which stay in registers beside the accumulators until the output phase.
+  // Where that is more than the lane's registers (NPK > 0), the last NPK accumulator tiles wait in
+  // LDS — 16 bytes per lane and store, rows of 1 KB per wave, lane-private, so no barrier — until
+  // their own k-blocks come up; by then the first tiles' k-blocks are done, and tile s takes the
+  // place of tile NT − NPK + s until its output. (Tile i is k-blocks 2i and 2i + 1.)
+  typedef __attribute__((address_space(3))) f4* lf4p;
+  unsigned char* const pk = smem + KK::PKOFF + ewave * 4096 + elane * 16;
+  static_assert(NPK <= NT - NPK, "parked tiles change places with the first ones");
+  if constexpr (NPK > 0) {
+    static_assert(KK::EPIB <= KK::BBOFF, "parked tiles below the bias / β stage");
 #pragma unroll
-    for (int k = 0; k < GK; ++k) {
-      const int blk = k * NW + ewave;
-      if (blk >= HBL) {   // the epilogue's own sink: the main loop's may lie under a γ buffer
-        sink4((unsigned char*)sbb + 2048);
-        continue;
+    for (int s = 0; s < NPK; ++s)
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const f16v& t = acc[NT - NPK + s];
+        *(lf4p)(pk + (s * NW * 4 + m) * 1024) = f4{t[4 * m], t[4 * m + 1], t[4 * m + 2], t[4 * m + 3]};
       }
-      const int p = blk / (NTH * KH), rem = blk - p * NTH * KH;
-      const int il = rem / KH, kb = kh * KH + rem - il * KH;
-      glds16(a.gamma_h3 + (long)p * CO * CO + ((2 * kb + eh) * CO + 32 * (hf * NTH + il) + er32) * 8,
-             smem + (q & 1) * HBL * 1024 + blk * 1024);
+  }
+  f16v n[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) n[i][j] = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (q == 0) {
+      wait_vm_barrier<GK>();   // stage 0 landed (stage 1 in flight)
+    } else {
+      vm_barrier();            // stage q landed, every wave done with the buffer stage q+1 refills
+      if (q + 1 < 4) stage_g(q + 1);
     }
-  };
-  stage_g(0);
-  stage_g(1);
+    const unsigned char* sg = smem + (q & 1) * QBL * 1024 + elane * 16;
 #pragma unroll
-  for (int hf = 0; hf < 2; ++hf) {
-    // opaque to the optimiser: pass 1 recomputes the x² planes instead of keeping pass 0's
-    // (12 k-blocks × 2 planes × 4 registers) alive across the passes
+    for (int kk = 0; kk < KQ; ++kk) {
+      const int kb = q * KQ + kk;
+      // x²·s_p of channels 16kb .. 16kb + 15 as the hi / lo B planes: the accumulator rows a
+      // lane holds are 4h + 0..3 and 8 + 4h + 0..3 of the 16-channel block; one permlane32 swap
+      // per register pair and plane hands lane half eh the 8 consecutive channels 8eh .. 8eh + 7
+      const int i = kb >> 1, r0 = 8 * (kb & 1);
+      if constexpr (NPK > 0) {
+        if (r0 == 0 && i >= NT - NPK) {   // tile i comes back, tile s takes its rows
+          const int s = i - (NT - NPK);
 #pragma unroll
-    for (int i = 0; i < NT; ++i)
+          for (int m = 0; m < 4; ++m) {
+            const lf4p row = (lf4p)(pk + (s * NW * 4 + m) * 1024);
+            const f4 t = *row;
+            *row = f4{acc[s][4 * m], acc[s][4 * m + 1], acc[s][4 * m + 2], acc[s][4 * m + 3]};
 #pragma unroll
-      for (int j = 0; j < 16; ++j) asm volatile("" : "+v"(acc[i][j]));
-    f16v n[NTH];
-#pragma unroll
-    for (int il = 0; il < NTH; ++il)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) n[il][j] = 0.f;
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) {
-      const int q = 2 * hf + kh;
-      if (q == 0) {
-        wait_vm_barrier<GK>();   // stage 0 landed (stage 1 in flight)
-      } else {
-        vm_barrier();            // stage q landed (and pass 0's stores), every wave done with
-                                 // the buffer stage q+1 refills
-        if (q + 1 < 4 && q >= 1) stage_g(q + 1);
+            for (int j = 0; j < 4; ++j) acc[i][4 * m + j] = t[j];
+          }
+        }
       }
-      const unsigned char* sg = smem + (q & 1) * HBL * 1024 + elane * 16;
+      unsigned hv[4], lv[4];   // channel pairs (2q, 2q + 1) of the lane's 8, packed fp16
 #pragma unroll
-      for (int kk = 0; kk < KH; ++kk) {
-        const int kb = kh * KH + kk;
-        // x²·s_p of channels 16kb .. 16kb + 15 as the hi / lo B planes: the accumulator rows a
-        // lane holds are 4h + 0..3 and 8 + 4h + 0..3 of the 16-channel block; one permlane32 swap
-        // per register pair and plane hands lane half eh the 8 consecutive channels 8eh .. 8eh + 7
-        const int i = kb >> 1, r0 = 8 * (kb & 1);
-        unsigned hv[4], lv[4];   // channel pairs (2q, 2q + 1) of the lane's 8, packed fp16
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          typedef float f2 __attribute__((ext_vector_type(2)));
-          const f2 v = f2{acc[i][r0 + 2 * qq] * acc[i][r0 + 2 * qq], acc[i][r0 + 2 * qq + 1] * acc[i][r0 + 2 * qq + 1]} * sp;
-          const h2v hh = __builtin_convertvector(v, h2v);
-          const h2v ll = __builtin_convertvector((v - __builtin_convertvector(hh, f2)) * 2048.0f, h2v);
-          hv[qq] = __builtin_bit_cast(unsigned, hh);
-          lv[qq] = __builtin_bit_cast(unsigned, ll);
-        }
-        u4 xp[2];
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-          const unsigned* v = pl == 0 ? hv : lv;
-          const auto s0 = __builtin_amdgcn_permlane32_swap(v[0], v[2], false, false);
-          const auto s1 = __builtin_amdgcn_permlane32_swap(v[1], v[3], false, false);
-          xp[pl] = u4{s0[0], s1[0], s0[1], s1[1]};
-        }
-#pragma unroll
-        for (int il = 0; il < NTH; ++il) {
-          const u4 gh = *(lu4p)(sg + ((0 * NTH + il) * KH + kk) * 1024);
-          const u4 gl = *(lu4p)(sg + ((1 * NTH + il) * KH + kk) * 1024);
-          f16v t = mfma32h(gh, xp[1], n[il]);
-          t = mfma32h(gl, xp[0], t);
-          n[il] = mfma32h(h3_x2048(gh), xp[0], t);
-        }
-        __builtin_amdgcn_sched_barrier(0);   // one k-block's operands live at a time
+      for (int qq = 0; qq < 4; ++qq) {
+        typedef float f2 __attribute__((ext_vector_type(2)));
+        const f2 v = f2{acc[i][r0 + 2 * qq] * acc[i][r0 + 2 * qq], acc[i][r0 + 2 * qq + 1] * acc[i][r0 + 2 * qq + 1]} * sp;
+        const h2v hh = __builtin_convertvector(v, h2v);
+        const h2v ll = __builtin_convertvector((v - __builtin_convertvector(hh, f2)) * 2048.0f, h2v);
+        hv[qq] = __builtin_bit_cast(unsigned, hh);
+        lv[qq] = __builtin_bit_cast(unsigned, ll);
       }
+      u4 xp[2];
+#pragma unroll
+      for (int pl = 0; pl < 2; ++pl) {
+        const unsigned* v = pl == 0 ? hv : lv;
+        const auto s0 = __builtin_amdgcn_permlane32_swap(v[0], v[2], false, false);
+        const auto s1 = __builtin_amdgcn_permlane32_swap(v[1], v[3], false, false);
+        xp[pl] = u4{s0[0], s1[0], s0[1], s1[1]};
+      }
+#pragma unroll
+      for (int il = 0; il < NT; ++il) {
+        const u4 gh = *(lu4p)(sg + ((0 * NT + il) * KQ + kk) * 1024);
+        const u4 gl = *(lu4p)(sg + ((1 * NT + il) * KQ + kk) * 1024);
+        f16v t = mfma32h(gh, xp[1], n[il]);
+        t = mfma32h(gl, xp[0], t);
+        n[il] = mfma32h(h3_x2048(gh), xp[0], t);
+      }
+      __builtin_amdgcn_sched_barrier(0);   // one k-block's operands live at a time
     }
+  }
+  // (the parked rows are read below what wrote them with no barrier between: keep the compiler
+  // from handing the stored registers on instead)
+  asm volatile("" ::: "memory");
+  {
+    // y = x·√(β + n) (IGDN) | x / √(β + n) (GDN); stores. The tiles in registers first, then the
+    // parked ones (tile s < NPK lies in the rows of slot s).
 #pragma unroll
-    for (int il = 0; il < NTH; ++il)
+    for (int io = 0; io < NT; ++io) {
+      const int i = io + NPK < NT ? io + NPK : io + NPK - NT, il = i;
+      if constexpr (NPK > 0) {
+        if (i < NPK) {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) n[il][j] = n[il][j] * nsc;
-    // y = x·√(β + n) (IGDN) | x / √(β + n) (GDN); stores
+          for (int m = 0; m < 4; ++m) {
+            const f4 t = *(lf4p)(pk + (i * NW * 4 + m) * 1024);
 #pragma unroll
-    for (int il = 0; il < NTH; ++il) {
-      const int i = hf * NTH + il;
+            for (int j = 0; j < 4; ++j) acc[i][4 * m + j] = t[j];
+          }
+        }
+      }
       f4 y[4], bes[4];
 #pragma unroll
       for (int m = 0; m < 4; ++m) bes[m] = *(const f4*)(sbb + 256 + 32 * i + 8 * m + 4 * eh);   // one wait
@@ -799,10 +836,15 @@ __device__ __forceinline__ void h3k_body(const HArgs& a, unsigned char* smem, in
         const f4 be = bes[m];
         // the hardware square root / reciprocal square root (v_sqrt_f32, v_rsq_f32: within an ulp
         // or two, far inside the h3 form's own 2⁻²² — and a sixth of the IEEE sequences' VALU
-        // work, which set the epilogue's length); n ≥ β_min > 0
+        // work, which set the epilogue's length); n ≥ β_min > 0.
+        // β + n·nsc as one fused multiply-add rounds as the product and the sum did apart: nsc is a
+        // power of two, so the product is exact unless it falls below 2⁻¹²⁶, and then both forms
+        // return β_eff itself — β_eff is at least the GDN's lower bound (≈ 10⁻⁶), whose half ulp
+        // (> 2⁻⁴⁵) is far above anything that small; an overflowing product is inf either way.
+        // (Not so for acc·dsc + bias above: a bias may be arbitrarily small.)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float nn = n[il][4 * m + j] + be[j];
+          const float nn = __builtin_fmaf(n[il][4 * m + j], nsc, be[j]);
           const float x = acc[i][4 * m + j];
           y[m][j] = EPI == HE_IGDN ? x * __builtin_amdgcn_sqrtf(nn) : x * __builtin_amdgcn_rsqf(nn);
         }

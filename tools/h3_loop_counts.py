@@ -11,7 +11,11 @@ The narrow-activation form (csrc/engine_h3.hip, NARROW) scales the one activatio
 step by 2^11 — 4 v_pk_mul_f16 — where the general form scales the weight fragments — 4 per
 32-channel tile; this tool is how DESIGN §0b's counts were taken.
 
-  python tools/h3_loop_counts.py [libiclr17.so] [name filter]
+  python tools/h3_loop_counts.py [libiclr17.so] [name filter] [--all]
+
+--all lists every segment group, not the eight most frequent: the GDN / IGDN epilogue's channel
+contraction is four segments per body (one per γ stage: 54 MFMAs at N = 192, 24 at N = 128; the
+last one runs on into the output phase), which the main loop's steps outnumber.
 """
 from __future__ import annotations
 
@@ -82,6 +86,8 @@ def segments(body):
 
 
 def main(argv):
+    every = "--all" in argv
+    argv = [a for a in argv if a != "--all"]
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = argv[1] if len(argv) > 1 else os.path.join(here, "iclr_17_compression_amd", "libiclr17.so")
     flt = argv[2] if len(argv) > 2 else "h3k_kernel"
@@ -94,11 +100,13 @@ def main(argv):
             if flt not in nm:
                 continue
             m = md.get(k, {})
+            scratch = sum(op.startswith("scratch_") for _, op, _ in body)
             print(f"{nm}\n  vgpr {m.get('vgpr_count')} agpr {m.get('agpr_count')} "
                   f"vgpr_spill {m.get('vgpr_spill_count')} sgpr_spill {m.get('sgpr_spill_count')} "
-                  f"lds {m.get('group_segment_fixed_size')}  instructions {len(body)}")
+                  f"scratch_instructions {scratch} lds {m.get('group_segment_fixed_size')}  "
+                  f"instructions {len(body)}")
             hist = collections.Counter(segments(body))
-            for (mf, va, pk, ds), n in sorted(hist.items(), key=lambda kv: -kv[1])[:8]:
+            for (mf, va, pk, ds), n in sorted(hist.items(), key=lambda kv: -kv[1])[:None if every else 8]:
                 print(f"  {n:4d} segments: {mf:3d} MFMA {va:4d} VALU ({pk:3d} v_pk_mul_f16) {ds:3d} ds_read"
                       f"   VALU/MFMA {va / mf:.2f}")
 

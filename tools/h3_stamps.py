@@ -1,5 +1,6 @@
 """Per-phase cycle counts of the h3 engine's kernels from a stamped diagnostic build (s_memtime
-at kernel entry, end of prologue, end of main loop, end of epilogue pass 0, end; wave 0 of each
+at kernel entry, end of prologue, end of main loop, γ stage 0 landed, end of each of the epilogue's
+four γ stages, end; wave 0 of each
 workgroup; tools/stamp_build.py builds it). Diagnostic tool:
 ICLR17_LIB=build/diag/lib_st.so ONLY=<h3_time runs> python tools/h3_stamps.py"""
 import ctypes
@@ -29,7 +30,7 @@ for k in os.environ["ONLY"].split(","):
     used = st[:, 8] > 0
     st = st[used]
     d = np.diff(st[:, :9], axis=1)
-    names = ["prologue", "main", "γ wait", "contract0", "out0", "γ2 wait", "contract1", "out1"]
+    names = ["prologue", "main", "γ wait", "stage0", "stage1", "stage2", "stage3", "out"]
     wall_ns = (st[:, 10] - st[:, 9]) * 10.0   # s_memrealtime: 100 MHz
     clk = (st[:, 8] - st[:, 0]) / wall_ns
     t0 = st[:, 9].min()

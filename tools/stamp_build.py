@@ -1,6 +1,6 @@
 """Builds build/diag/lib_st.so: the library with a stamped copy of csrc/engine_h3.hip (s_memtime at
-kernel entry, end of prologue, end of main loop, γ stage 0 landed, pass-0 contraction done, pass-0
-outputs done, γ stage 2 landed, pass-1 contraction done, end; wave 0 of each workgroup into a
+kernel entry, end of prologue, end of main loop, γ stage 0 landed, the contraction of each of the
+four γ stages done (a stage's own wait included from stage 1 on), end; wave 0 of each workgroup into a
 device array read back by diag_stamps) for tools/h3_stamps.py. Diagnostic build only: the product
 library carries no stamps."""
 import os
@@ -31,22 +31,21 @@ rep('''  Frag cur;
 rep('''  vm_barrier();   // trailing sink loads landed; every wave is done with the stages''',
     '''  vm_barrier();   // trailing sink loads landed; every wave is done with the stages
   STAMP(2);''')
-rep('''  for (int hf = 0; hf < 2; ++hf) {
-    // opaque to the optimiser''', '''  for (int hf = 0; hf < 2; ++hf) {
-    if (hf) STAMP(5);
-    // opaque to the optimiser''')
-rep('''        wait_vm_barrier<GK>();   // stage 0 landed (stage 1 in flight)''',
-    '''        wait_vm_barrier<GK>();   // stage 0 landed (stage 1 in flight)
-        STAMP(3);''')
-rep('''        if (q + 1 < 4 && q >= 1) stage_g(q + 1);''', '''        if (q + 1 < 4 && q >= 1) stage_g(q + 1);
-        if (q == 2) STAMP(6);''')
-rep('''      for (int j = 0; j < 16; ++j) n[il][j] = n[il][j] * nsc;''',
-    '''      for (int j = 0; j < 16; ++j) n[il][j] = n[il][j] * nsc;
-    STAMP(4 + 3 * hf);''')
-rep('''  if (ovf && a.range) atomicOr(a.range, 1);   // vector atomic, per offending lane (rare)
-}''', '''  if (ovf && a.range) atomicOr(a.range, 1);   // vector atomic, per offending lane (rare)
+rep('''      wait_vm_barrier<GK>();   // stage 0 landed (stage 1 in flight)''',
+    '''      wait_vm_barrier<GK>();   // stage 0 landed (stage 1 in flight)
+      STAMP(3);''')
+rep('''      __builtin_amdgcn_sched_barrier(0);   // one k-block's operands live at a time
+    }
+  }''', '''      __builtin_amdgcn_sched_barrier(0);   // one k-block's operands live at a time
+    }
+    STAMP(4 + q);
+  }''')
+rep('''  if (wid && a.wide) atomicOr(a.wide, 1);
+  }
+}''', '''  if (wid && a.wide) atomicOr(a.wide, 1);
   STAMP(8);
   if (threadIdx.x == 0) g_st[blockIdx.x & 4095][10] = __builtin_amdgcn_s_memrealtime();
+  }
 }''')
 rep('''  int bid = blockIdx.x;
   const int per_ph''', '''  STAMP(0);
