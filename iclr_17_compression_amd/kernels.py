@@ -1601,13 +1601,10 @@ def wgrad_k9(G: Tensor, X: Tensor) -> Tensor:
     return dW
 
 
-def gdn_wgrad(dn: Tensor, u: Tensor, x6: Optional[bool] = None) -> Tensor:
-    """dγ_eff [C, C] = Σ_p dn[p] ⊗ u[p]² (GDN.py:83); x6 (default: the build's precision) or
-    exact f32."""
+def gdn_wgrad(dn: Tensor, u: Tensor, x6: bool) -> Tensor:
+    """dγ_eff [C, C] = Σ_p dn[p] ⊗ u[p]² (GDN.py:83); x6 or exact f32."""
     C = dn.shape[-1]
     P = dn.numel() // C
-    if x6 is None:
-        x6 = precision() != "fp32"
     name = "iclr17_gdn_wgrad_x6" if x6 else "iclr17_gdn_wgrad"
     ws = torch.empty(query(name + "_workspace_size", P, C), device=dn.device, dtype=torch.float32)
     dge = torch.empty(C, C, device=dn.device, dtype=torch.float32)
@@ -1617,7 +1614,7 @@ def gdn_wgrad(dn: Tensor, u: Tensor, x6: Optional[bool] = None) -> Tensor:
 
 def gdn_param_grads(dn: Tensor, u: Tensor, dbe: Tensor, beta: Tensor, gamma: Tensor,
                     beta_bound: float = DEFAULT_BETA_BOUND, gamma_bound: float = DEFAULT_GAMMA_BOUND,
-                    x6: Optional[bool] = None):
+                    *, x6: bool):
     """GDN parameter gradients (dβ, dγ) in the raw-parameter space (through GDN.py:73-79);
     dbe = ∂β_eff (Σ dn, from the backward kernel's column sums). x6 as ``gdn_wgrad``: a backward
     passes what its forward's mode asks for."""

@@ -132,10 +132,11 @@ class Analysis_net_17(nn.Module):
 
     def y_nhwc(self, x, mode, feats=None):
         """y (NHWC) through the analysis kernels of the codec's chain in ``mode`` (chain.MODES).
-        ``feats``: the training forward's features of x (autograd.analysis_features_train in the
-        same mode), whose conv2+GDN2 output is reused for conv3 where it is the codec's own
-        operand (x6: its split form; fp32: the fp32 activation; h3: its h3 form — the training
-        forward runs the codec's h3 kernels). In the bf16 mode the codec's own chain runs again
+        ``feats``: the training forward's record of x (chain.train_mode(mode).train_analysis, a
+        chain.AnalysisFeats), whose conv2+GDN2 output is reused for conv3 where it is the codec's
+        own operand; the mode's ``conv3_operand`` picks it (x6: its split form; fp32: the fp32
+        activation; h3: its h3 form — the training forward runs the codec's h3 kernels and began
+        the chain). In the bf16 mode the codec's own chain runs again
         (its y is what the codec rounds) while the gradient is the training kernels' x6 one, a
         different function at bf16 precision (≈0.3 % of the rounded latents, §3 of DESIGN.md)."""
         N = self.out_channel_N

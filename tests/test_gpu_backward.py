@@ -314,34 +314,29 @@ def test_h3_training_forward_saved_tensors(device):
     """The h3 training forward (the codec's h3 kernels with their pre-activation and x6 split
     outputs) hands the backward the x6 forward's tensors to the h3 form's accuracy, at a size with
     partial tiles (B=2, 48×80: conv2's 12×20 output, deconv1's 3×5 input)."""
-    from iclr_17_compression_amd import autograd, kernels
+    from iclr_17_compression_amd import chain, kernels
     N = 192
     net, _ = make(N, 3, device)
     x = torch.from_numpy(synth.to_unit_float(synth.image_u8(7, 2, 48, 80))).to(device)
     enc, dec = net.Encoder, net.Decoder
-    old = kernels.precision()
-    try:
-        with torch.no_grad():
-            kernels.set_precision("x6")
-            _, sx = autograd.analysis_features_train(enc, x)
-            y = kernels.conv3_quant_rate_x6(sx["a2s"], enc.packed()[2], net.bitEstimator.packed())[0]
-            _, rx, ssex, tx = autograd.synthesis_forward_train(dec, y, x_ref=x)
-            kernels.set_precision("h3")
-            _, sh = autograd.analysis_features_train(enc, x)
-            _, rh, sseh, th = autograd.synthesis_forward_train(dec, y, x_ref=x)
-    finally:
-        kernels.set_precision(old)
+    x6, h3 = chain.train_mode("x6"), chain.train_mode("h3")
+    with torch.no_grad():
+        sx = x6.train_analysis(enc, x)
+        y = kernels.conv3_quant_rate_x6(sx.a2s, enc.packed()[2], net.bitEstimator.packed())[0]
+        _, rx, ssex, tx = x6.train_synthesis(dec, y, None, x)
+        sh = h3.train_analysis(enc, x)
+        _, rh, sseh, th = h3.train_synthesis(dec, y, None, x)
     rel = lambda a, b: ((a - b).abs().max() / b.abs().max()).item()  # noqa: E731
     for k in ("u1", "u2"):
-        assert rel(sh[k], sx[k]) < 5e-6, k
+        assert rel(getattr(sh, k), getattr(sx, k)) < 5e-6, k
     for k in ("a1s", "a2s"):
-        assert rel(kernels.merge_planes(sh[k]), kernels.merge_planes(sx[k])) < 5e-6, k
-    assert torch.equal(kernels.merge_h3(sh["a2h"]), kernels.merge_h3(kernels.h3_planes(
-        kernels.merge_planes(sh["a2s"]))))
+        assert rel(kernels.merge_planes(getattr(sh, k)), kernels.merge_planes(getattr(sx, k))) < 5e-6, k
+    assert torch.equal(kernels.merge_h3(sh.a2h), kernels.merge_h3(kernels.h3_planes(
+        kernels.merge_planes(sh.a2s))))
     for k in ("v1", "v2"):
-        assert rel(th[k], tx[k]) < 5e-6, k
+        assert rel(getattr(th, k), getattr(tx, k)) < 5e-6, k
     for k in ("s1s", "s2s"):
-        assert rel(kernels.merge_planes(th[k]), kernels.merge_planes(tx[k])) < 5e-6, k
+        assert rel(kernels.merge_planes(getattr(th, k)), kernels.merge_planes(getattr(tx, k))) < 5e-6, k
     assert rel(rh, rx) < 5e-6
     assert abs(sseh.double().sum().item() - ssex.double().sum().item()) <= 1e-5 * ssex.double().sum().item()
 

@@ -70,6 +70,57 @@ def test_x6_fallback_never_sets_the_default(device, default_mode, monkeypatch, e
     assert kernels.precision() == "h3"
 
 
+# ------------------------------------------------------------ each h3 training entry begins a chain
+def test_h3_training_entries_begin_their_own_chain(device, default_mode):
+    """A training step, Encoder(x) with grad and Decoder(ŷ) with grad in h3 each begin their own
+    chain: run right after an h3 eval chain that overflowed the range on the same stream (its flag
+    still set), every output and gradient of the three is finite."""
+    default_mode("h3")
+    bad = _net(192, device)
+    with torch.no_grad():   # the overflow model of test_gpu_h3_range._encoder_overflow
+        bad.Encoder.conv1.bias[0] = 1e4
+        bad.Encoder.gdn1.gamma[0].zero_()
+        bad.Encoder.gdn1.beta[0] = 0.0
+    net = _net(192, device).train()
+    x = _image(device)
+    noise = torch.from_numpy(synth.uniform(11, (2, 192, 4, 6), -0.5, 0.5).astype(np.float32)).to(device)
+    with torch.no_grad():
+        y_hat = torch.round(net.Encoder(x))
+
+    def overflow():
+        with torch.no_grad():
+            bad.evaluate(x)
+        assert kernels.h3_range_overflowed(device)
+
+    def finite(outs, modules, inp):
+        torch.cuda.synchronize()
+        named = [(f"out{i}", o) for i, o in enumerate(outs)] + [("input", inp.grad)]
+        named += [(n, p.grad) for m in modules for n, p in m.named_parameters()]
+        for n, t in named:
+            assert t is not None and bool(torch.isfinite(t).all()), n
+
+    overflow()
+    net.zero_grad(set_to_none=True)
+    xg = x.clone().requires_grad_(True)
+    clipped, mse, bpp = net.forward_train(xg, noise)
+    (LAM * mse + bpp).backward()
+    finite((clipped, mse, bpp), [net], xg)
+
+    overflow()
+    net.zero_grad(set_to_none=True)
+    xg = x.clone().requires_grad_(True)
+    y = net.Encoder(xg)
+    y.sum().backward()
+    finite((y,), [net.Encoder], xg)
+
+    overflow()
+    net.zero_grad(set_to_none=True)
+    yg = y_hat.clone().requires_grad_(True)
+    recon = net.Decoder(yg)
+    recon.sum().backward()
+    finite((recon,), [net.Decoder], yg)
+
+
 # ------------------------------------------------------------ backward in the forward's mode
 def _codec_loss(net, x, noise):
     _, mse, bpp = net.forward_train(x, noise)

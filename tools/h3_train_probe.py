@@ -6,7 +6,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from iclr_17_compression_amd import autograd, kernels, synth  # noqa: E402
+from iclr_17_compression_amd import chain, kernels, synth  # noqa: E402
 from iclr_17_compression_amd.model import ImageCompressor  # noqa: E402
 
 B, H, W = (int(v) for v in sys.argv[1:4]) if len(sys.argv) >= 4 else (1, 32, 32)
@@ -19,19 +19,17 @@ x = torch.from_numpy(synth.to_unit_float(synth.image_u8(5, B, H, W))).to(dev)
 noise = torch.from_numpy(synth.uniform(6, (B, N, H // 16, W // 16), -0.5, 0.5)).to(dev)
 enc = net.Encoder
 with torch.no_grad():
-    kernels.set_precision("x6")
-    _, sx = autograd.analysis_features_train(enc, x)
-    kernels.set_precision("h3")
-    _, sh = autograd.analysis_features_train(enc, x)
+    sx = chain.train_mode("x6").train_analysis(enc, x)
+    sh = chain.train_mode("h3").train_analysis(enc, x)
     for k in ("u1", "u2"):
-        a, b = sh[k], sx[k]
+        a, b = getattr(sh, k), getattr(sx, k)
         print(k, "nan", torch.isnan(a).sum().item(), "max rel", ((a - b).abs().max() / b.abs().max()).item())
     for k in ("a1s", "a2s"):
-        a, b = kernels.merge_planes(sh[k]), kernels.merge_planes(sx[k])
+        a, b = kernels.merge_planes(getattr(sh, k)), kernels.merge_planes(getattr(sx, k))
         print(k, "nan", torch.isnan(a).sum().item(), "max rel", ((a - b).abs().max() / b.abs().max()).item())
-    a2 = kernels.merge_h3(sh["a2h"])
+    a2 = kernels.merge_h3(sh.a2h)
     print("a2h nan", torch.isnan(a2).sum().item())
-    yt, bits, _, yh = kernels.conv3_quant_rate_h3(sh["a2h"], enc.packed_h3()[1], net.bitEstimator.packed(), noise)
+    yt, bits, _, yh = kernels.conv3_quant_rate_h3(sh.a2h, enc.packed_h3()[1], net.bitEstimator.packed(), noise)
     print("y_tilde nan", torch.isnan(yt).sum().item(), "bits nan", torch.isnan(bits).sum().item())
-    yr, _, _, _ = kernels.conv3_quant_rate_h3(sh["a2h"], enc.packed_h3()[1], net.bitEstimator.packed())
+    yr, _, _, _ = kernels.conv3_quant_rate_h3(sh.a2h, enc.packed_h3()[1], net.bitEstimator.packed())
     print("round-mode y_hat nan", torch.isnan(yr).sum().item())
