@@ -95,6 +95,11 @@ SIGNATURES = {
     "iclr17_rans_offsets": (_I, [_P, _I, _P, _P]),
     "iclr17_rans_pack": (_I, [_P, ctypes.c_long, _P, _I, _P, _P]),
     "iclr17_rans_decode": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "iclr17_pack_rate_step": (_I, [_P, _I, _F, _P, _P]),
+    "iclr17_quantise_step": (_I, [_P, _I64, _F, _P, _P, _P, _P]),
+    "iclr17_dequantise_step": (_I, [_P, _I64, _F, _P, _P]),
+    "iclr17_rate_sweep_partials": (_I, [_I, _I, _I]),
+    "iclr17_rate_sweep": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "iclr17_ms_ssim_workspace_size": (_SZ, [_I, _I, _I]),
     "iclr17_ms_ssim": (_I, [_P, _P, _I, _I, _I, _F, _P, _SZ, _P, _P]),
     "iclr17_ssim_workspace_size": (_SZ, [_I, _I, _I]),

@@ -24,9 +24,34 @@ bit-exactly in every mode; the synthesis transform then runs in the decoder's mo
 pixels may differ by one 8-bit step between modes. Within one mode the decoded bytes are
 reproducible and do not depend on the batch an image travelled in.
 
+Quantiser steps. One checkpoint gives many rates by scaling the quantiser: with a step Δ the
+coder codes ŷ = rint(y/Δ) under the rate model evaluated on Δ-wide bins, and the synthesis runs on
+Δ·ŷ. Δ comes from a ladder of 32 quarter-octave values (``step_size``; index 8 is Δ = 1).
+``compress_images(..., step=s)`` codes at one index; ``max_bytes=`` / ``bpp=`` give a budget on the
+whole blob, and each image gets the finest index that fits:
+
+  1. one analysis pass and one ``rate_sweep`` (the estimated bits of every image at all 32 indices)
+     per canvas batch;
+  2. per image the finest index, scanning 0 → 31, whose ⌈bits/8⌉ + header + 4P + 256P fits
+     (``choose_step``); the coarsest when no estimate fits;
+  3. the images are coded grouped by index;
+  4. an image whose actual blob exceeds its budget moves one index coarser and is coded again;
+  5. at index 31 that raises Iclr17Error.
+
+Stepped blobs have their own magic and carry the index in the first pad byte; everything else is
+the plain header, and the payload starts at the same byte:
+
+    struct "<4sBBHHBxIIQ":  magic b"I17Q" | version u8 = 1 | P | N | K | step u8 | pad | H | W |
+                            fingerprint
+
+Blobs coded with ``step=8`` are I17Q too, with the plain blob's payload; only the call without a
+rate option writes I17C. ``decompress_images`` takes both kinds in one call. The weights were
+trained at Δ = 1: away from the unit step the quality is whatever the model gives.
+
     python -m iclr_17_compression_amd.codec encode IN.png OUT.i17c --weights CKPT [--N 192]
+                                            [--step S | --max-bytes B | --bpp R]
     python -m iclr_17_compression_amd.codec decode IN.i17c OUT.png --weights CKPT
-    python -m iclr_17_compression_amd.codec eval IMG... --weights CKPT [--ms-ssim]
+    python -m iclr_17_compression_amd.codec eval IMG... --weights CKPT [--ms-ssim] [--steps 4,8,12]
 """
 from __future__ import annotations
 
@@ -52,6 +77,74 @@ HEADER = struct.Struct("<4sBBHHxxIIQ")
 assert HEADER.size == 28
 
 Header = namedtuple("Header", "P N K H W fingerprint")
+
+STEP_MAGIC = b"I17Q"
+STEP_HEADER = struct.Struct("<4sBBHHBxIIQ")
+assert STEP_HEADER.size == HEADER.size   # the payload starts at the same byte in both kinds
+
+# ------------------------------------------------------------------------------ ladder
+STEPS = 32
+UNIT_STEP = 8
+# the fp32 values nearest to 2^0, 2^¼, 2^½, 2^¾, as literals: the same bits on every host
+_STEP_MANTISSAS = (1.0, 1.1892070770263672, 1.4142135381698608, 1.6817928552627563)
+
+
+def step_size(s: int) -> float:
+    """Δ_s = M[s % 4] · 2^(s // 4 − 2) for the ladder index 0 ≤ s < 32: a quarter octave per
+    index from 0.25 to about 53.8, each exactly an fp32 value, Δ_8 = 1."""
+    if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= s < STEPS:
+        raise Iclr17Error(f"iclr17: codec: quantiser step index {s!r} is not an integer in 0..{STEPS - 1}")
+    return _STEP_MANTISSAS[int(s) % 4] * 2.0 ** (int(s) // 4 - 2)
+
+
+def choose_step(est_bits_row, budget: int, overhead: int) -> int:
+    """The budget rule's first pick for one image: the finest ladder index, scanning 0 → 31,
+    whose estimated size ⌈bits/8⌉ + overhead fits ``budget`` bytes. ``est_bits_row``: the image's
+    row of ``rate_sweep`` (one estimate per index). The row is not assumed monotone: the first
+    index that fits wins. Raises Iclr17Error when none fits."""
+    sizes = [math.ceil(float(b) / 8.0) + overhead for b in est_bits_row]
+    for s, size in enumerate(sizes):
+        if size <= budget:
+            return s
+    raise Iclr17Error(f"iclr17: codec: no quantiser step fits {budget} bytes (the smallest estimate "
+                      f"is {min(sizes)} bytes)" if sizes else "iclr17: codec: empty estimate row")
+
+
+def encode_to_budget(chosen: Sequence[int], budgets: Sequence[Optional[int]], encode,
+                     labels: Sequence[str]) -> Tuple[List[bytes], List[int]]:
+    """Steps 3–5 of the budget rule for one batch (a pure host function: the coding is
+    ``encode``). ``chosen``: each image's first ladder index; ``budgets``: its byte budget (None:
+    none); ``encode(members, s)`` codes the images ``members`` (ascending positions) at index s
+    and returns their blobs. Images are coded grouped by index; one whose blob exceeds its budget
+    moves one index coarser and is coded again, and at index 31 that raises, naming
+    ``labels[k]``, the budget and the size reached → (blobs, re-encodes per image)."""
+    chosen = list(chosen)
+    blobs: List[Optional[bytes]] = [None] * len(chosen)
+    reencodes = [0] * len(chosen)
+    todo = list(range(len(chosen)))
+    while todo:
+        again = []
+        for members in _group([chosen[k] for k in todo], len(todo)):
+            ks = [todo[m] for m in members]
+            s = chosen[ks[0]]
+            for k, blob in zip(ks, encode(ks, s)):
+                if budgets[k] is None or len(blob) <= budgets[k]:
+                    blobs[k] = blob
+                elif s == STEPS - 1:
+                    raise Iclr17Error(f"iclr17: codec: {labels[k]} does not fit its budget of "
+                                      f"{budgets[k]} bytes: the coarsest step gives {len(blob)}")
+                else:
+                    chosen[k] = s + 1
+                    reencodes[k] += 1
+                    again.append(k)
+        todo = sorted(again)
+    return blobs, reencodes
+
+
+def blob_overhead(P: int) -> int:
+    """Bytes of a blob that are not renormalisation words: the header, the P stream word counts
+    and each stream's 64 final rANS states."""
+    return HEADER.size + 4 * P + 256 * P
 
 
 # ------------------------------------------------------------------------------ canvas
@@ -104,14 +197,9 @@ def pack_header(P: int, N: int, K: int, H: int, W: int, fingerprint: int) -> byt
     return HEADER.pack(MAGIC, VERSION, P, N, K, H, W, fingerprint & (2 ** 64 - 1))
 
 
-def parse_header(blob: bytes, N: Optional[int] = None, fingerprint: Optional[int] = None) -> Header:
-    """The header of a blob; with ``N`` / ``fingerprint`` (the decoding model's) also checked
-    against them. The payload (blob[HEADER.size:]) is checked by ``decompress``."""
-    if len(blob) < HEADER.size:
-        raise Iclr17Error(f"iclr17: codec: truncated header ({len(blob)} of {HEADER.size} bytes)")
-    magic, version, P, n, K, H, W, fp = HEADER.unpack_from(blob)
-    if magic != MAGIC:
-        raise Iclr17Error(f"iclr17: codec: bad magic {magic!r} (not an I17C stream)")
+def _checked_header(kind, magic, version, P, n, K, H, W, fp, N, fingerprint) -> Header:
+    if magic != kind:
+        raise Iclr17Error(f"iclr17: codec: bad magic {magic!r} (not an {kind.decode()} stream)")
     if version != VERSION:
         raise Iclr17Error(f"iclr17: codec: unknown version {version} (this build reads {VERSION})")
     if H == 0 or W == 0:
@@ -122,6 +210,45 @@ def parse_header(blob: bytes, N: Optional[int] = None, fingerprint: Optional[int
         raise Iclr17Error(f"iclr17: codec: weights fingerprint mismatch (stream {fp:016x}, model "
                           f"{fingerprint:016x}): the stream was coded with other weights")
     return Header(P, n, K, H, W, fp)
+
+
+def parse_header(blob: bytes, N: Optional[int] = None, fingerprint: Optional[int] = None) -> Header:
+    """The header of a plain (I17C) blob; with ``N`` / ``fingerprint`` (the decoding model's) also
+    checked against them. The payload (blob[HEADER.size:]) is checked by ``decompress``."""
+    if len(blob) < HEADER.size:
+        raise Iclr17Error(f"iclr17: codec: truncated header ({len(blob)} of {HEADER.size} bytes)")
+    magic, version, P, n, K, H, W, fp = HEADER.unpack_from(blob)
+    return _checked_header(MAGIC, magic, version, P, n, K, H, W, fp, N, fingerprint)
+
+
+def pack_step_header(P: int, N: int, K: int, step: int, H: int, W: int, fingerprint: int) -> bytes:
+    """The header of a stepped blob: ``pack_header``'s fields under the magic I17Q, with the
+    ladder index in the first of the two pad bytes."""
+    step_size(step)
+    pack_header(P, N, K, H, W, fingerprint)   # the shared fields' range checks
+    return STEP_HEADER.pack(STEP_MAGIC, VERSION, P, N, K, int(step), H, W, fingerprint & (2 ** 64 - 1))
+
+
+def parse_step_header(blob: bytes, N: Optional[int] = None,
+                      fingerprint: Optional[int] = None) -> Tuple[Header, int]:
+    """The header of a stepped (I17Q) blob → (Header, ladder index), checked as ``parse_header``
+    checks a plain one; an index outside the ladder raises."""
+    if len(blob) < STEP_HEADER.size:
+        raise Iclr17Error(f"iclr17: codec: truncated header ({len(blob)} of {STEP_HEADER.size} bytes)")
+    magic, version, P, n, K, step, H, W, fp = STEP_HEADER.unpack_from(blob)
+    head = _checked_header(STEP_MAGIC, magic, version, P, n, K, H, W, fp, N, fingerprint)
+    if step >= STEPS:
+        raise Iclr17Error(f"iclr17: codec: quantiser step {step} in the stream (this build reads "
+                          f"0..{STEPS - 1})")
+    return head, step
+
+
+def parse_blob(blob: bytes, N: Optional[int] = None,
+               fingerprint: Optional[int] = None) -> Tuple[Header, Optional[int]]:
+    """The header of either kind of blob → (Header, ladder index | None for a plain blob)."""
+    if bytes(blob[:4]) == STEP_MAGIC:
+        return parse_step_header(blob, N, fingerprint)
+    return parse_header(blob, N, fingerprint), None
 
 
 # ------------------------------------------------------------------------------ batches
@@ -147,20 +274,76 @@ def upload_packed(images: Sequence[np.ndarray], device):
     return host.to(device, non_blocking=True), [int(o) for o in offsets], [im.shape[:2] for im in images]
 
 
+def rate_request(n: int, step=None, max_bytes=None, bpp=None):
+    """The rate options of ``compress_images`` for ``n`` images, checked on the host before any
+    device use → None (the plain path), ("step", index) or ("budget", per-image values, is_bpp).
+    At most one option; a budget is a scalar or one value per image."""
+    given = [k for k, v in (("step", step), ("max_bytes", max_bytes), ("bpp", bpp)) if v is not None]
+    if len(given) > 1:
+        raise Iclr17Error(f"iclr17: codec: {' and '.join(given)} given together (at most one of "
+                          "step, max_bytes, bpp)")
+    if not given:
+        return None
+    if step is not None:
+        step_size(step)
+        return "step", int(step)
+    value = max_bytes if max_bytes is not None else bpp
+    per = [value] * n if np.ndim(value) == 0 else list(np.asarray(value).reshape(-1))
+    if len(per) != n:
+        raise Iclr17Error(f"iclr17: codec: {given[0]} has {len(per)} values for {n} images")
+    if not all(np.isfinite(float(v)) and float(v) > 0 for v in per):
+        raise Iclr17Error(f"iclr17: codec: {given[0]} must be finite and positive")
+    return "budget", per, bpp is not None
+
+
 def compress_images(net, images, max_batch: int = 64,
                     streams_per_image: int = kernels.STREAMS_PER_IMAGE,
-                    K: int = kernels.ENTROPY_K) -> List[bytes]:
+                    K: int = kernels.ENTROPY_K, step: Optional[int] = None, max_bytes=None,
+                    bpp=None, stats: Optional[dict] = None) -> List[bytes]:
     imgs = [as_u8_hwc(im) for im in images]
+    request = rate_request(len(imgs), step, max_bytes, bpp)
     device = next(net.parameters()).device
-    fp, N = fingerprint(net), net.out_channel_N
+    fp, N, P = fingerprint(net), net.out_channel_N, streams_per_image
     blobs: List[Optional[bytes]] = [None] * len(imgs)
+    budgets: List[Optional[int]] = [None] * len(imgs)
+    if request is not None and request[0] == "budget":
+        for i, (im, v) in enumerate(zip(imgs, request[1])):
+            budgets[i] = int(math.floor(float(v) * im.shape[0] * im.shape[1] / 8)) if request[2] else int(v)
+    reencodes = [0] * len(imgs)
     for idx in group_by_canvas([im.shape[:2] for im in imgs], max_batch):
         group = [imgs[i] for i in idx]
         packed, offsets, shapes = upload_packed(group, device)
         x = kernels.image_ingest(packed, offsets, shapes, canvas(*shapes[0]))
-        enc = net.compress(x, streams_per_image=streams_per_image, K=K)
-        for i, (H, W), s in zip(idx, shapes, enc["strings"]):
-            blobs[i] = pack_header(streams_per_image, N, K, H, W, fp) + s
+        if request is None:
+            enc = net.compress(x, streams_per_image=P, K=K)
+            for i, (H, W), s in zip(idx, shapes, enc["strings"]):
+                blobs[i] = pack_header(P, N, K, H, W, fp) + s
+            continue
+        # one analysis pass per batch, however many steps and re-encodes follow
+        y = net.latents(x)
+        if request[0] == "step":
+            chosen = [request[1]] * len(idx)
+        else:
+            est = net.rate_sweep(y, latent=True).cpu().numpy()
+            chosen = []
+            for k, i in enumerate(idx):
+                try:
+                    chosen.append(choose_step(est[k], budgets[i], blob_overhead(P)))
+                except Iclr17Error:
+                    chosen.append(STEPS - 1)   # no estimate fits: the coarsest step decides below
+
+        def encode(ks, s):
+            sel = y if len(ks) == len(idx) else y[torch.tensor(ks, device=device)]
+            enc = net.compress_latents(sel, s, streams_per_image=P, K=K)
+            return [pack_step_header(P, N, K, s, *shapes[k], fp) + string
+                    for k, string in zip(ks, enc["strings"])]
+
+        coded, again = encode_to_budget(chosen, [budgets[i] for i in idx], encode,
+                                        [f"image {i} ({H}x{W})" for i, (H, W) in zip(idx, shapes)])
+        for i, blob, n in zip(idx, coded, again):
+            blobs[i], reencodes[i] = blob, n
+    if stats is not None:
+        stats["reencodes"] = reencodes
     return blobs
 
 
@@ -169,7 +352,8 @@ def decode_groups(net, blobs, max_batch: int, refs=None):
     image's Σ (decoded − original)² → ([uint8 HWC arrays], [int] | None)."""
     device = next(net.parameters()).device
     fp, N = fingerprint(net), net.out_channel_N
-    heads = [parse_header(b, N, fp) for b in blobs]
+    parsed = [parse_blob(b, N, fp) for b in blobs]
+    heads, steps = [h for h, _ in parsed], [s for _, s in parsed]
     for b, h in zip(blobs, heads):
         # decompress reads the payload as 16-bit words and checks the counts; an odd rest cannot
         # even be read that way
@@ -177,11 +361,11 @@ def decode_groups(net, blobs, max_batch: int, refs=None):
             raise Iclr17Error(f"iclr17: codec: truncated stream ({len(b)} bytes)")
     out: List[Optional[np.ndarray]] = [None] * len(blobs)
     sses: Optional[List[Optional[int]]] = [None] * len(blobs) if refs is not None else None
-    for idx in _group([canvas(h.H, h.W) + (h.P, h.K) for h in heads], max_batch):
+    for idx in _group([canvas(h.H, h.W) + (h.P, h.K, s) for h, s in parsed], max_batch):
         h0 = heads[idx[0]]
         Hc, Wc = canvas(h0.H, h0.W)
         dec = net.decompress([blobs[i][HEADER.size:] for i in idx], (Hc // 16, Wc // 16),
-                             streams_per_image=h0.P, K=h0.K, device=device)
+                             streams_per_image=h0.P, K=h0.K, device=device, step=steps[idx[0]])
         shapes = [(heads[i].H, heads[i].W) for i in idx]
         ref = None
         if refs is not None:
@@ -200,9 +384,10 @@ def decode_groups(net, blobs, max_batch: int, refs=None):
     return out, sses
 
 
-def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64) -> List[dict]:
+def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
+                    step: Optional[int] = None, max_bytes=None, bpp=None) -> List[dict]:
     imgs = [as_u8_hwc(im) for im in images]
-    blobs = compress_images(net, imgs, max_batch=max_batch)
+    blobs = compress_images(net, imgs, max_batch=max_batch, step=step, max_bytes=max_bytes, bpp=bpp)
     recons, sses = decode_groups(net, blobs, max_batch, refs=imgs)
     device = next(net.parameters()).device
     res = []
@@ -210,7 +395,7 @@ def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64)
         H, W = im.shape[:2]
         r = {"bytes": len(blob), "bpp": 8 * len(blob) / (H * W), "sse_u8": sse,
              "psnr_u8": 10.0 * math.log10(255.0 ** 2 * 3 * H * W / sse) if sse else math.inf,
-             "recon": rec}
+             "recon": rec, "step": parse_blob(blob)[1]}
         if want_msssim:
             r["ms_ssim"] = r["ms_ssim_db"] = None
             if kernels.query("iclr17_ms_ssim_workspace_size", 1, H, W):   # 0: too small for 5 levels
@@ -250,17 +435,24 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     enc = sub.add_parser("encode", parents=[common], help="IN.png OUT.i17c")
     enc.add_argument("input")
     enc.add_argument("output")
+    rate = enc.add_mutually_exclusive_group()
+    rate.add_argument("--step", type=int, default=None, help="ladder index 0..31 (8: the unit step)")
+    rate.add_argument("--max-bytes", type=int, default=None, help="byte budget of the output file")
+    rate.add_argument("--bpp", type=float, default=None, help="budget in bits per pixel of the file")
     dec = sub.add_parser("decode", parents=[common], help="IN.i17c OUT.png")
     dec.add_argument("input")
     dec.add_argument("output")
     ev = sub.add_parser("eval", parents=[common], help="IMG...: one JSON line per image and a mean")
     ev.add_argument("images", nargs="+")
     ev.add_argument("--ms-ssim", action="store_true")
+    ev.add_argument("--steps", default=None, help="ladder indices, e.g. 4,8,12: a row per image "
+                                                  "and step, and a mean per step")
     args = ap.parse_args(argv)
     net = _model(args)
     with kernels.precision_scope(args.precision or kernels.precision()):
         if args.cmd == "encode":
-            blob = net.compress_images([_load_image(args.input)])[0]
+            blob = net.compress_images([_load_image(args.input)], step=args.step,
+                                       max_bytes=args.max_bytes, bpp=args.bpp)[0]
             with open(args.output, "wb") as f:
                 f.write(blob)
         elif args.cmd == "decode":
@@ -270,16 +462,19 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             Image.fromarray(net.decompress_images([blob])[0]).save(args.output, format="PNG")
         else:
             imgs = [_load_image(p) for p in args.images]
-            rows = net.evaluate_images(imgs, want_msssim=args.ms_ssim)
-            for p, im, r in zip(args.images, imgs, rows):
-                print(json.dumps({"name": p, "H": im.shape[0], "W": im.shape[1], "bytes": r["bytes"],
-                                  "bpp": r["bpp"], "psnr_u8": r["psnr_u8"],
-                                  "ms_ssim": r.get("ms_ssim")}))
-            ms = [r["ms_ssim"] for r in rows if r.get("ms_ssim") is not None]
-            print(json.dumps({"name": "mean", "images": len(rows),
-                              "bpp": float(np.mean([r["bpp"] for r in rows])),
-                              "psnr_u8": float(np.mean([r["psnr_u8"] for r in rows])),
-                              "ms_ssim": float(np.mean(ms)) if ms else None}))
+            steps = [int(t) for t in args.steps.split(",")] if args.steps else [None]
+            for step in steps:
+                rows = net.evaluate_images(imgs, want_msssim=args.ms_ssim, step=step)
+                tag = {} if step is None else {"step": step}
+                for p, im, r in zip(args.images, imgs, rows):
+                    print(json.dumps({"name": p, **tag, "H": im.shape[0], "W": im.shape[1],
+                                      "bytes": r["bytes"], "bpp": r["bpp"], "psnr_u8": r["psnr_u8"],
+                                      "ms_ssim": r.get("ms_ssim")}))
+                ms = [r["ms_ssim"] for r in rows if r.get("ms_ssim") is not None]
+                print(json.dumps({"name": "mean", **tag, "images": len(rows),
+                                  "bpp": float(np.mean([r["bpp"] for r in rows])),
+                                  "psnr_u8": float(np.mean([r["psnr_u8"] for r in rows])),
+                                  "ms_ssim": float(np.mean(ms)) if ms else None}))
     return 0
 
 

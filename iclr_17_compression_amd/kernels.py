@@ -1192,6 +1192,85 @@ def _check_f64(t: Tensor) -> None:
         raise Iclr17Error("iclr17: partial sums must be a 2-D float64 GPU tensor")
 
 
+# ---------------------------------------------------------------- rate control (csrc/ratectl.hip)
+SWEEP_MAX_STEPS = 32
+
+
+def _step_value(step: float, what: str) -> float:
+    """A quantiser step as the fp32 value the kernels get; finite and > 0."""
+    d = float(np.float32(step))
+    if not (np.isfinite(d) and d > 0.0):
+        raise Iclr17Error(f"iclr17: {what}: the step {step!r} is not finite and positive")
+    return d
+
+
+def pack_rate_step(rate_packed: Tensor, N: int, step: float) -> Tensor:
+    """The step pack: ``rate_packed`` [11][N] with row 0 · step, so that F(step·u) is the packed
+    model of u and every rate / entropy kernel codes ŷ = rint(y/step) unchanged."""
+    _check(rate_packed, "rate table")
+    if rate_packed.numel() != 11 * N:
+        raise Iclr17Error(f"iclr17: pack_rate_step: packed rate parameters are not [11][{N}]")
+    d = _step_value(step, "pack_rate_step")
+    out = torch.empty_like(rate_packed)
+    call("iclr17_pack_rate_step", _p(rate_packed), N, ctypes.c_float(d), _p(out),
+         _stream(rate_packed))
+    return out
+
+
+def _step_status(status: Tensor, what: str) -> None:
+    st = int(status.item())
+    if st:
+        why = (["a latent is NaN"] if st & 1 else []) + (["|latent / step| > 32767"] if st & 2 else [])
+        raise Iclr17Error(f"iclr17: {what}: " + "; ".join(why))
+
+
+def quantise_step(y: Tensor, step: float):
+    """y (fp32, any shape) → (ŷ = rint(y/step), integer-valued fp32; step·ŷ), one pass. Raises on
+    a NaN and on |ŷ| > 32767 (what the entropy coder cannot carry)."""
+    _check(y, "latent")
+    d = _step_value(step, "quantise_step")
+    y = y.contiguous()
+    y_hat, y_deq = torch.empty_like(y), torch.empty_like(y)
+    status = torch.zeros(1, device=y.device, dtype=torch.int32)
+    call("iclr17_quantise_step", _p(y), y.numel(), ctypes.c_float(d), _p(y_hat), _p(y_deq),
+         _p(status), _stream(y))
+    _step_status(status, "quantise_step")
+    return y_hat, y_deq
+
+
+def dequantise_step(y_hat: Tensor, step: float) -> Tensor:
+    """step·ŷ (fp32, the shape of ŷ): the decoder's half of ``quantise_step``."""
+    _check(y_hat, "latent")
+    d = _step_value(step, "dequantise_step")
+    y_hat = y_hat.contiguous()
+    out = torch.empty_like(y_hat)
+    call("iclr17_dequantise_step", _p(y_hat), y_hat.numel(), ctypes.c_float(d), _p(out),
+         _stream(y_hat))
+    return out
+
+
+def rate_sweep(y: Tensor, rate_packed: Tensor, steps: Sequence[float]) -> Tensor:
+    """y fp32 NHWC [B,h,w,N], the UNscaled rate pack and 1..32 step sizes → float64 [B, S]: the
+    estimated bits of each image at each step, from one read of y; per step what
+    ``rate_bits(quantise_step(y, Δ)[0] as NCHW-shaped, pack_rate_step(…, Δ))`` sums to."""
+    _check(y, "latent", 4)
+    _check(rate_packed, "rate table")
+    B, h, w, N = y.shape
+    if rate_packed.numel() != 11 * N:
+        raise Iclr17Error(f"iclr17: rate_sweep: packed rate parameters are not [11][{N}]")
+    ds = [_step_value(s, "rate_sweep") for s in steps]
+    S = len(ds)
+    if not 1 <= S <= SWEEP_MAX_STEPS:
+        raise Iclr17Error(f"iclr17: rate_sweep: {S} steps (1..{SWEEP_MAX_STEPS})")
+    T = query("iclr17_rate_sweep_partials", h, w, N)
+    partial = torch.empty(B * S * max(T, 1), device=y.device, dtype=torch.float64)
+    bits = torch.empty(B, S, device=y.device, dtype=torch.float64)
+    arr = (ctypes.c_float * S)(*ds)
+    call("iclr17_rate_sweep", _p(y.contiguous()), B, h, w, N, _p(rate_packed),
+         ctypes.cast(arr, ctypes.c_void_p), S, _p(partial), _p(bits), _stream(y))
+    return bits
+
+
 # ---------------------------------------------------------------- image files (§1 f5)
 def _image_desc(what: str, nbytes: int, offsets, shapes, canvas) -> Tensor:
     """The int64 [B][4] descriptors {byte offset, H, W, 0} of uint8 HWC images packed in a buffer

@@ -169,6 +169,61 @@ class ImageCompressor(nn.Module):
             return clipped, 1 - ms_ssim_diff(clipped, input_image, data_range=1.0), bpp
         return clipped, mse, bpp
 
+    # ------------------------------------------------------------- rate control (codec.py)
+    @torch.no_grad()
+    def latents(self, x: torch.Tensor) -> torch.Tensor:
+        """The unquantised latent y of an image batch, fp32 NHWC [B, H/16, W/16, N]: the analysis
+        transform of the current precision mode (its conv3 rounds this very y to ŷ), with
+        ``compress``'s fall-back to the x6 chain when an activation does not fit the h3 form."""
+        mode = kernels.precision()
+        y = self.encode_latents(x, want_y=True, mode=mode)["y"]
+        if mode == "h3" and kernels.h3_range_overflowed(x.device):
+            with kernels.precision_scope("x6"):
+                y = self.encode_latents(x, want_y=True)["y"]
+        return y
+
+    @torch.no_grad()
+    def rate_sweep(self, x_or_y: torch.Tensor, steps=range(32),
+                   latent: Optional[bool] = None) -> torch.Tensor:
+        """Estimated bits of every image at every ladder step of ``steps`` (codec.step_size
+        indices, at most 32): float64 [B, S] on the device, from one analysis pass and one read
+        of y (kernels.rate_sweep). The argument is an image batch [B,3,H,W] or, with a second
+        dimension other than 3 or ``latent=True``, the NHWC latent of ``latents``."""
+        from . import codec
+        kernels._check(x_or_y, "image or latent", 4)
+        if latent is None:
+            latent = x_or_y.shape[1] != 3
+        y = x_or_y if latent else self.latents(x_or_y)
+        if y.shape[3] != self.out_channel_N:
+            raise kernels.Iclr17Error(f"iclr17: rate_sweep: the latent has {y.shape[3]} channels, "
+                                      f"the model {self.out_channel_N}")
+        return kernels.rate_sweep(y, self.bitEstimator.packed(),
+                                  [codec.step_size(s) for s in steps])
+
+    @torch.no_grad()
+    def compress_latents(self, y: torch.Tensor, step: int,
+                         streams_per_image: int = kernels.STREAMS_PER_IMAGE,
+                         K: int = kernels.ENTROPY_K) -> Dict[str, object]:
+        """``compress`` from the latent of ``latents`` at ladder step ``step``: ŷ = rint(y/Δ)
+        (kernels.quantise_step), then rANS with the step's tables. Returns ``compress``'s dict and
+        "y_hat" (NHWC)."""
+        from . import codec
+        y_hat, _ = kernels.quantise_step(y, codec.step_size(step))
+        return self._entropy_code(y_hat, self.bitEstimator.entropy_tables(K, step=step),
+                                  streams_per_image, K)
+
+    def _entropy_code(self, y_hat, tables, P, K):
+        B, h, w, N = y_hat.shape
+        words, offsets = kernels.rans_encode(y_hat, tables, K, P)
+        off = offsets.cpu().numpy()
+        wv = words.cpu().numpy().view("<u2")
+        strings = []
+        for b in range(B):
+            o = off[b * P:(b + 1) * P + 1]
+            strings.append(np.diff(o).astype("<u4").tobytes() + wv[o[0]:o[-1]].tobytes())
+        return {"strings": strings, "shape": (h, w), "streams_per_image": P, "K": K,
+                "y_hat": y_hat}
+
     # ------------------------------------------------------------- entropy coding (§8 f4)
     @torch.no_grad()
     def compress(self, x: torch.Tensor, streams_per_image: int = kernels.STREAMS_PER_IMAGE,
@@ -185,22 +240,18 @@ class ImageCompressor(nn.Module):
             # the stream sizes below synchronise anyway.
             with kernels.precision_scope("x6"):
                 y_hat = self.encode_latents(x)["y_hat"]
-        B, h, w, N = y_hat.shape
-        P = streams_per_image
-        words, offsets = kernels.rans_encode(y_hat, self.bitEstimator.entropy_tables(K), K, P)
-        off = offsets.cpu().numpy()
-        wv = words.cpu().numpy().view("<u2")
-        strings = []
-        for b in range(B):
-            o = off[b * P:(b + 1) * P + 1]
-            strings.append(np.diff(o).astype("<u4").tobytes() + wv[o[0]:o[-1]].tobytes())
-        return {"strings": strings, "shape": (h, w), "streams_per_image": P, "K": K}
+        enc = self._entropy_code(y_hat, self.bitEstimator.entropy_tables(K), streams_per_image, K)
+        del enc["y_hat"]
+        return enc
 
     @torch.no_grad()
     def decompress(self, strings, shape, streams_per_image: int = kernels.STREAMS_PER_IMAGE,
-                   K: int = kernels.ENTROPY_K, device=None) -> Dict[str, torch.Tensor]:
+                   K: int = kernels.ENTROPY_K, device=None,
+                   step: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """Inverse of ``compress``: byte strings → {"y_hat": NCHW latents, "x_hat": the clipped
-        reconstruction} (bit-identical latents; the synthesis as in ``forward``)."""
+        reconstruction} (bit-identical latents; the synthesis as in ``forward``). With ``step``
+        the inverse of ``compress_latents`` at that ladder step: the step's tables decode ŷ, and
+        the synthesis runs on Δ·ŷ as a general (non-integer) latent."""
         P, N = streams_per_image, self.out_channel_N
         h, w = shape
         device = device or next(self.parameters()).device
@@ -218,18 +269,25 @@ class ImageCompressor(nn.Module):
         off = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.int64)
         words = torch.from_numpy(np.concatenate(payload).view(np.int16).copy()).to(device)
         offsets = torch.from_numpy(off).to(device)
-        y_hat = kernels.rans_decode(words, offsets, self.bitEstimator.entropy_tables(K), B, h, w, N,
-                                    K, P)
+        y_hat = kernels.rans_decode(words, offsets, self.bitEstimator.entropy_tables(K, step=step),
+                                    B, h, w, N, K, P)
         m = chain.MODES[kernels.precision()]
-        clipped, _, _ = m.synthesis(self.Decoder, y_hat, m.latent_operand(y_hat), None, False, True,
-                                    None, False)
+        if step is None:
+            clipped, _, _ = m.synthesis(self.Decoder, y_hat, m.latent_operand(y_hat), None, False,
+                                        True, None, False)
+        else:
+            from . import codec
+            y_deq = kernels.dequantise_step(y_hat, codec.step_size(step))
+            clipped, _, _ = m.synthesis(self.Decoder, y_deq, m.latent_operand(y_deq), None, False,
+                                        False, None, False)
         return {"y_hat": y_hat.permute(0, 3, 1, 2).contiguous(), "x_hat": clipped}
 
     # ------------------------------------------------------------- image files (§1 f5, codec.py)
     @torch.no_grad()
     def compress_images(self, images, max_batch: int = 64,
                         streams_per_image: int = kernels.STREAMS_PER_IMAGE,
-                        K: int = kernels.ENTROPY_K):
+                        K: int = kernels.ENTROPY_K, step: Optional[int] = None,
+                        max_bytes=None, bpp=None, stats: Optional[dict] = None):
         """8-bit images of any sizes ≥ 1×1 (a sequence of uint8 HWC RGB arrays, numpy or torch) →
         one self-describing blob per image, in input order: codec.py's 28-byte header (true size,
         N, P, K, weights fingerprint) + the image's ``compress`` string. Images are batched by
@@ -237,15 +295,24 @@ class ImageCompressor(nn.Module):
         per batch; each batch is one pinned upload, kernels.image_ingest and ``compress`` as it
         stands (its x6 fall-back on an h3 overflow included). The precision mode is not recorded:
         the latents decode bit-exactly in every mode, decoded pixels may differ by one 8-bit step
-        between modes, and within one mode a blob does not depend on its batch."""
+        between modes, and within one mode a blob does not depend on its batch.
+
+        At most one of ``step`` / ``max_bytes`` / ``bpp`` selects another rate from the same
+        weights (codec.py, "Quantiser steps"): ``step`` a ladder index 0..31 (8 is Δ = 1),
+        ``max_bytes`` a byte budget on the whole blob and ``bpp`` one of ⌊bpp·H·W/8⌋ bytes, each
+        a scalar or one value per image; a budget picks per image the finest step that fits.
+        These blobs carry the magic I17Q and their step; ``stats`` (a dict) receives
+        "reencodes", the budget loop's re-encodes per image."""
         from . import codec
-        return codec.compress_images(self, images, max_batch, streams_per_image, K)
+        return codec.compress_images(self, images, max_batch, streams_per_image, K, step=step,
+                                     max_bytes=max_bytes, bpp=bpp, stats=stats)
 
     @torch.no_grad()
     def decompress_images(self, blobs, max_batch: int = 64):
         """Inverse of ``compress_images``: blobs → uint8 HWC numpy arrays of the true sizes, in
         input order (``decompress`` per canvas batch, then kernels.image_egress: round-half-even of
-        the clipped reconstruction·255, cropped). Raises Iclr17Error on a foreign or truncated
+        the clipped reconstruction·255, cropped). Plain (I17C) and stepped (I17Q) blobs may be
+        mixed; a batch holds blobs of one canvas, P, K and step. Raises Iclr17Error on a foreign or truncated
         blob, another N or other weights (the header's fingerprint). Within one precision mode
         the bytes are reproducible and independent of the batch; between modes a pixel may differ
         by one 8-bit step."""
@@ -253,15 +320,19 @@ class ImageCompressor(nn.Module):
         return codec.decode_groups(self, list(blobs), max_batch)[0]
 
     @torch.no_grad()
-    def evaluate_images(self, images, want_msssim: bool = False, max_batch: int = 64):
+    def evaluate_images(self, images, want_msssim: bool = False, max_batch: int = 64,
+                        step: Optional[int] = None, max_bytes=None, bpp=None):
         """The real codec path per image, compress_images then decompress_images, measured on
         the 8-bit decoded image as codecs are reported: a dict per image with ``bytes``, ``bpp`` =
         8·len(blob)/(H·W) (header included, true pixel count), ``sse_u8`` (int), ``psnr_u8`` =
         10·log10(255²·3HW / sse_u8) (float64; inf at 0), ``recon`` (uint8 HWC) and, with
         ``want_msssim``, ``ms_ssim`` / ``ms_ssim_db`` of the cropped pair (None for an image too
-        small for 5 levels). Precision as ``decompress_images``."""
+        small for 5 levels) and ``step`` (the blob's ladder step; None for a plain blob).
+        ``step`` / ``max_bytes`` / ``bpp`` as in ``compress_images``. Precision as
+        ``decompress_images``."""
         from . import codec
-        return codec.evaluate_images(self, images, want_msssim, max_batch)
+        return codec.evaluate_images(self, images, want_msssim, max_batch, step=step,
+                                     max_bytes=max_bytes, bpp=bpp)
 
     @torch.no_grad()
     def evaluate(self, x: torch.Tensor, want_y: bool = False,

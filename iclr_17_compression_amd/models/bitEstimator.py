@@ -5,6 +5,8 @@ the final layer has no ``a``) and init; forwards run gfx950 elementwise kernels.
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 from torch import nn
 
@@ -58,9 +60,23 @@ class BitEstimator(nn.Module):
         return self._pack.get("rtab", ps, lambda: kernels.rate_table(self.packed(force), self.channel),
                               force=force)
 
-    def entropy_tables(self, K: int = kernels.ENTROPY_K):
-        """Quantised CDFs for the entropy coder (cached like the packed parameters)."""
+    def step_packed(self, step: int):
+        """The packed table of ladder step ``step`` (codec.step_size): row 0 · Δ, made on the
+        device from ``packed()`` and cached like it."""
+        from ..codec import step_size
+        d = step_size(step)
         ps = self.params_in_order()
+        return self._pack.get(f"rate_s{step}", ps,
+                              lambda: kernels.pack_rate_step(self.packed(), self.channel, d))
+
+    def entropy_tables(self, K: int = kernels.ENTROPY_K, step: Optional[int] = None):
+        """Quantised CDFs for the entropy coder (cached like the packed parameters); with
+        ``step`` those of ŷ = rint(y/Δ_step), from ``step_packed(step)``."""
+        ps = self.params_in_order()
+        if step is not None:
+            return self._pack.get(
+                f"cdf{K}_s{step}", ps,
+                lambda: kernels.entropy_tables(self.step_packed(step), self.channel, K))
         return self._pack.get(f"cdf{K}", ps,
                               lambda: kernels.entropy_tables(self.packed(), self.channel, K),
                               )

@@ -273,6 +273,33 @@ int iclr17_rans_decode(const uint16_t* words, const int64_t* offsets, int B, int
                        int streams_per_image, const int32_t* cum, int K, float* y_hat,
                        int32_t* status, void* stream);
 
+/* ---------------------------------------------------------------- rate control (csrc/ratectl.hip)
+ * Many rates from one set of weights: with a quantiser step Δ the codec codes ŷ = rint(y/Δ) and
+ * synthesises from Δ·ŷ. The model's first layer is v·softplus(h1) + b1, so F(Δ·u) is the same
+ * function with row 0 of the packed rate parameters multiplied by Δ: the *step pack*, with which
+ * iclr17_entropy_tables, iclr17_rate_table, iclr17_rate_bits and the rANS entries code the scaled
+ * alphabet unchanged. A step must be finite and > 0. */
+/* step_packed[11][N] = rate_packed with row 0 · step (one fp32 product per channel). */
+int iclr17_pack_rate_step(const float* rate_packed, int N, float step, float* step_packed,
+                          void* stream);
+/* y_hat[i] = rintf(y[i] / step) (IEEE divide, half to even; integer-valued fp32) and
+ * y_deq[i] = step · y_hat[i], n elements of any layout. status |= 1 a NaN, 2 |ŷ| > 32767 (int32
+ * on the device, caller-zeroed). */
+int iclr17_quantise_step(const float* y, int64_t n, float step, float* y_hat, float* y_deq,
+                         int32_t* status, void* stream);
+/* y_deq[i] = step · y_hat[i] alone (the decoder's half of iclr17_quantise_step). */
+int iclr17_dequantise_step(const float* y_hat, int64_t n, float step, float* y_deq, void* stream);
+/* The estimated bits of every image at S ≤ 32 steps from one read of y (fp32 NHWC [B][h][w][N]):
+ * bits[b][s] = Σ element_bits(rintf(y/steps[s]), step pack of steps[s]) over image b — term for
+ * term and in the order of addition what iclr17_rate_bits(iclr17_quantise_step(y, steps[s]),
+ * iclr17_pack_rate_step(rate_packed, steps[s])) and iclr17_reduce_partials give. rate_packed is
+ * the UNscaled pack; steps is a host array, copied at the call. partial: B · S ·
+ * iclr17_rate_sweep_partials(h, w, N) doubles of scratch; bits: [B][S] doubles. Fixed order, no
+ * atomics: bitwise reproducible. */
+int iclr17_rate_sweep_partials(int h, int w, int N);
+int iclr17_rate_sweep(const float* y, int B, int h, int w, int N, const float* rate_packed,
+                      const float* steps, int S, double* partial, double* bits, void* stream);
+
 /* testKodak's MS-SSIM (train.py:178 → models/ms_ssim_torch.py:123-196): per-image
  * ms_ssim(x, y, data_range) of NCHW [B,3,H,W] fp32 images, 11-tap σ=1.5 window, 5 levels (each
  * level must be ≥ 11×11: H, W ≥ 161 or so), the reference's level weights and final product.
