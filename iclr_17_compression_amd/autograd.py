@@ -257,6 +257,68 @@ class CodecTrainFn(torch.autograd.Function):
         return (dx, None, None, None, *grads)
 
 
+RATE_PARAM_ORDER = ["f1.h", "f1.b", "f1.a", "f2.h", "f2.b", "f2.a", "f3.h", "f3.b", "f3.a", "f4.h",
+                    "f4.b"]
+
+
+class StepTrainFn(torch.autograd.Function):
+    """ImageCompressor training forward with a ladder step per image:
+    (clipped, bpp [B], mse of the unclipped recon [B]). ``steps_dev``: fp32 [B], Δ per image.
+    The analysis and synthesis halves are CodecTrainFn's; between them y (the mode's unrounded
+    conv3 output) goes through kernels.step_noise_rate, and the rate term of the backward through
+    its own kernel instead of deconv1's rate epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, noise, steps_dev, net, mode, *params):
+        ctx.set_materialize_grads(False)
+        enc, dec, be = net.Encoder, net.Decoder, net.bitEstimator
+        B, _, H, W = x.shape
+        m = chain.train_mode(mode)
+        saved_a = m.train_analysis(enc, x)
+        y = enc.y_nhwc(x, m.name, feats=saved_a)
+        rate = be.packed()
+        z, y_deq, bits_part = kernels.step_noise_rate(y, noise, steps_dev, rate)
+        # inside the chain train_analysis began: an overflow in either half ends in a NaN distortion
+        latent = m.chained_latent(y_deq)
+        clipped, recon, sse_part, saved_s = m.train_synthesis(dec, y_deq, latent, x)
+        bits, _ = kernels.reduce_partials(bits_part)
+        sse, _ = kernels.reduce_partials(sse_part)
+        ctx.net, ctx.mode = net, m.name
+        ctx.saved_a, ctx.saved_s = saved_a, saved_s
+        ctx.recon, ctx.x, ctx.rate, ctx.z, ctx.steps = recon, x, rate, z, steps_dev
+        ctx.pixels = float(H * W)
+        return clipped, (bits / (H * W)).float(), (sse / (3 * H * W)).float()
+
+    @staticmethod
+    def backward(ctx, g_clipped, g_bpp, g_mse):
+        net = ctx.net
+        enc, dec, be = net.Encoder, net.Decoder, net.bitEstimator
+        if g_clipped is None and g_mse is None:
+            g_recon = torch.zeros_like(ctx.recon)
+        else:
+            g_recon = kernels.grad_recon_images(ctx.recon, ctx.x, g_mse, g_clipped)
+        g_y, gs, _, _ = synthesis_backward(dec, ctx.saved_s, g_recon, mode=ctx.mode)
+        red = getattr(net, "_grad_reducer", None)
+        red = red if red is not None and red.active else None
+        if red is not None:   # the synthesis gradients all-reduce during the analysis backward
+            red.launch(list(dec.parameters()), _ordered(dec, "", gs))
+        rg = [None] * 11
+        if g_bpp is not None:
+            g_bits = (g_bpp.detach().float() / ctx.pixels).contiguous()
+            g_y, rpart = kernels.step_noise_rate_backward(ctx.z, g_y, ctx.steps, ctx.rate, g_bits)
+            rg = kernels.rate_param_grads(rpart, be.params_in_order())
+        ga = analysis_backward(enc, ctx.saved_a, g_y.contiguous(), mode=ctx.mode)
+        names = [n for n, _ in be.named_parameters()]
+        rmap = dict(zip(RATE_PARAM_ORDER, rg))
+        grads = _ordered(enc, "Encoder.", ga) + _ordered(dec, "Decoder.", gs) + \
+            [rmap[n] for n in names]
+        if red is not None:
+            red.launch(list(enc.parameters()) + list(be.parameters()),
+                       _ordered(enc, "", ga) + [rmap[n] for n in names])
+        ctx.saved_a = ctx.saved_s = ctx.recon = ctx.z = None
+        return (None, None, None, None, None, *grads)
+
+
 class MsSsimFn(torch.autograd.Function):
     """Per-image MS-SSIM [B] (kernels.ms_ssim, bitwise) with its backward: the forward keeps the
     derivative maps in a workspace (with the dY maps only when Y needs a gradient), the backward

@@ -165,6 +165,11 @@ class Mode:
         """The synthesis input form of an fp32 NHWC latent."""
         return y_nhwc
 
+    def chained_latent(self, y_nhwc):
+        """``latent_operand`` of a latent made inside a running chain (the stepped training
+        step's ỹ = Δ·z, between ``train_analysis`` and ``train_synthesis``): the chain goes on."""
+        return self.latent_operand(y_nhwc)
+
     def warm_h3(self, net) -> None:
         """Inside kernels.batched_h3_packs(), once ``warm``'s batch is written: the h3 layouts."""
 
@@ -325,6 +330,10 @@ class _H3(_X6):
     def latent_operand(self, y_nhwc):
         # a latent that enters the synthesis from outside starts a chain of its own
         self.begin(y_nhwc.device)
+        return kernels.h3_planes(y_nhwc, cm=kernels.DECONV_CM)
+
+    def chained_latent(self, y_nhwc):
+        # no begin(): that would clear a range flag the analysis half had just set
         return kernels.h3_planes(y_nhwc, cm=kernels.DECONV_CM)
 
     def conv3_operand(self, feats):

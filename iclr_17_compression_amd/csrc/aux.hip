@@ -223,7 +223,7 @@ __global__ void bitparm_kernel(const float* __restrict__ x, int64_t n, int C, in
 }
 
 // Autograd of the stand-alone BitEstimator / Bitparm forward (bitEstimator.py:20-42) for an
-// upstream gradient g = ∂L/∂out, op for op as rate_bwd_element (engine_fp32.hip) does for the
+// upstream gradient g = ∂L/∂out, op for op as rate_bwd_element (common.h) does for the
 // rate term. rp is the packed [11][C] table (softplus(h_k), b_k, tanh(a_k) for k = 1..3 at
 // slots 3k-3.., softplus(h4), b4 at 9, 10). MODE 0: the 4-layer BitEstimator; 1: one non-final
 // Bitparm (slots 0-2); 2: the final Bitparm (slots 9, 10). One workgroup per (channel, chunk of

@@ -157,6 +157,56 @@ __device__ __forceinline__ float element_bits(float z, const float* __restrict__
   return bits;
 }
 
+// The backward of element_bits at one element, as the autograd of model.py:71-78 /
+// bitEstimator.py:20-25 evaluates it: returns gsc · ∂bits/∂z and adds gsc · ∂bits/∂(row k of the
+// pack) into pg[k]. Shared by the rate epilogue of deconv1's dgrad (engine.h) and the stepped
+// training step (steptrain.hip).
+__device__ __forceinline__ float rate_bwd_element(float z, const float* __restrict__ rp, int C,
+                                                  int c, float gsc, float (&pg)[11]) {
+  float xs[2][4], Ts[2][3], F[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    float x = h == 0 ? z + 0.5f : z - 0.5f;
+    xs[h][0] = x;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float t = x * rp[(3 * k) * C + c] + rp[(3 * k + 1) * C + c];
+      const float T = tanhf(t);
+      x = t + T * rp[(3 * k + 2) * C + c];
+      Ts[h][k] = T;
+      xs[h][k + 1] = x;
+    }
+    const float t4 = x * rp[9 * C + c] + rp[10 * C + c];
+    F[h] = 1.0f / (1.0f + expf(-t4));
+  }
+  const float prob = F[0] - F[1];
+  const float raw = (-1.0f * logf(prob + 1e-10f)) / 0.693147182464599609375f;
+  const bool pass = raw >= 0.0f && raw <= 50.0f;          // clamp(·, 0, 50) backward mask
+  const float g0 = pass ? gsc : 0.0f;
+  const float gl = ((g0 / 0.693147182464599609375f) * -1.0f) / (prob + 1e-10f);
+  float dz = 0.0f;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float gF = h == 0 ? gl : -gl;
+    const float gt4 = (gF * (1.0f - F[h])) * F[h];        // sigmoid backward
+    pg[10] += gt4;                                          // b4
+    pg[9] += gt4 * xs[h][3];                                // softplus(h4)
+    float gx = gt4 * rp[9 * C + c];
+#pragma unroll
+    for (int k = 2; k >= 0; --k) {
+      const float T = Ts[h][k];
+      const float gT = gx * rp[(3 * k + 2) * C + c];
+      pg[3 * k + 2] += gx * T;                              // tanh(a_k)
+      const float gt = gx + gT * (1.0f - T * T);            // tanh backward
+      pg[3 * k + 1] += gt;                                  // b_k
+      pg[3 * k] += gt * xs[h][k];                           // softplus(h_k)
+      gx = gt * rp[(3 * k) * C + c];
+    }
+    dz += gx;
+  }
+  return dz;
+}
+
 // Exact three-way bf16 split of 8 floats: x = hi + mid + lo, each part a bf16 (truncation
 // split: hi = the top 8 significand bits, mid the next 8, lo the last 8, all exact in fp32).
 // Packed as bf16x8 fragments (u4 = 8 × 16 bits).

@@ -1271,6 +1271,76 @@ def rate_sweep(y: Tensor, rate_packed: Tensor, steps: Sequence[float]) -> Tensor
     return bits
 
 
+# ------------------------------------------------------------ stepped training (csrc/steptrain.hip)
+def _step_args(t: Tensor, steps_dev: Tensor, rate_packed: Tensor, what: str):
+    """An fp32 NHWC latent-shaped tensor, the [B] fp32 step sizes and the UNscaled pack, checked."""
+    _check(t, "latent", 4)
+    _check(steps_dev, "step sizes", 1)
+    _check(rate_packed, "rate table")
+    B, h, w, N = t.shape
+    if steps_dev.numel() != B:
+        raise Iclr17Error(f"iclr17: {what}: {steps_dev.numel()} step sizes for {B} images")
+    if rate_packed.numel() != 11 * N:
+        raise Iclr17Error(f"iclr17: {what}: packed rate parameters are not [11][{N}]")
+    return B, h, w, N
+
+
+def step_noise_rate(y: Tensor, noise: Tensor, steps_dev: Tensor, rate_packed: Tensor):
+    """The stepped noise quantiser and its rate: y fp32 NHWC [B,h,w,N], noise NCHW
+    [B,N,h,w], steps_dev fp32 [B] (Δ per image, finite and > 0), the UNscaled rate pack →
+    (z = y/Δ + u, ỹ = Δ·z, bit partials float64 [B, T]): per image what
+    ``rate_bits(z[b:b+1], pack_rate_step(rate_packed, N, Δ_b))`` gives, for ``reduce_partials``."""
+    B, h, w, N = _step_args(y, steps_dev, rate_packed, "step_noise_rate")
+    _check(noise, "noise", 4)
+    if tuple(noise.shape) != (B, N, h, w):
+        raise Iclr17Error(f"iclr17: noise must be {(B, N, h, w)} (got {tuple(noise.shape)})")
+    y = y.contiguous()
+    z, y_deq = torch.empty_like(y), torch.empty_like(y)
+    T = query("iclr17_rate_bits_partials", N, h, w)
+    partial = torch.empty(B, T, device=y.device, dtype=torch.float64)
+    call("iclr17_step_noise_rate", _p(y), _p(noise.contiguous()), B, h, w, N,
+         _p(steps_dev.contiguous()), _p(rate_packed), _p(z), _p(y_deq), _p(partial), _stream(y))
+    return z, y_deq, partial
+
+
+def step_noise_rate_backward(z: Tensor, g_deq: Tensor, steps_dev: Tensor, rate_packed: Tensor,
+                             g_bits: Tensor):
+    """Backward of ``step_noise_rate``: z and g_deq = ∂L/∂ỹ fp32 NHWC, g_bits fp32 [B] = ∂L/∂bits_b
+    → (∂L/∂y = g_deq + g_bits[b]·∂bits/∂z / Δ_b, rate partials [T, 11, N] for
+    ``rate_param_grads``, slot 0 being ∂/∂softplus(h1))."""
+    B, h, w, N = _step_args(z, steps_dev, rate_packed, "step_noise_rate_backward")
+    _check(g_deq, "latent gradient", 4)
+    _check(g_bits, "bit gradients", 1)
+    if tuple(g_deq.shape) != (B, h, w, N) or g_bits.numel() != B:
+        raise Iclr17Error("iclr17: step_noise_rate_backward: gradient shapes do not match the latent")
+    g_y = torch.empty_like(z)
+    T = B * query("iclr17_step_rate_bwd_partials", h, w)
+    part = torch.empty(T, 11, N, device=z.device, dtype=torch.float32)
+    call("iclr17_step_noise_rate_bwd", _p(z.contiguous()), _p(g_deq.contiguous()), B, h, w, N,
+         _p(steps_dev.contiguous()), _p(rate_packed), _p(g_bits.contiguous()), _p(g_y), _p(part),
+         _stream(z))
+    return g_y, part
+
+
+def grad_recon_images(recon: Tensor, x: Tensor, g_mse: Optional[Tensor],
+                      g_clip: Optional[Tensor]) -> Tensor:
+    """``grad_recon`` with one MSE weight per image: g_mse fp32 [B], the weight of image b's
+    mean((recon_b − x_b)²)."""
+    _check(recon, "recon", 4)
+    B = recon.shape[0]
+    out = torch.empty_like(recon)
+    gm = None
+    if g_mse is not None:
+        gm = g_mse.detach().reshape(-1).contiguous()
+        _check(gm, "MSE weights", 1)
+        if gm.numel() != B:
+            raise Iclr17Error(f"iclr17: grad_recon_images: {gm.numel()} MSE weights for {B} images")
+    gc = g_clip.detach().contiguous() if g_clip is not None else None
+    call("iclr17_grad_recon_images", _p(recon.contiguous()), _p(x.contiguous()), _p(gm), _p(gc), B,
+         recon.numel() // B, _p(out), _stream(recon))
+    return out
+
+
 # ---------------------------------------------------------------- image files (§1 f5)
 def _image_desc(what: str, nbytes: int, offsets, shapes, canvas) -> Tensor:
     """The int64 [B][4] descriptors {byte offset, H, W, 0} of uint8 HWC images packed in a buffer

@@ -151,22 +151,79 @@ class ImageCompressor(nn.Module):
         return CodecTrainFn.apply(x.contiguous(), noise.contiguous(), self, mode, *params)
 
     def forward_train(self, input_image, noise: Optional[torch.Tensor] = None,
-                      distortion: str = "mse"):
+                      distortion: str = "mse", steps=None):
         """The tuple train.py:97 unpacks, as model.py:81 intends:
         (clipped_recon, mse of the UNclipped recon (model.py:61), bpp), all differentiable.
 
         ``distortion="ms-ssim"`` returns (clipped_recon, 1 − mean MS-SSIM(clipped_recon, x), bpp)
         instead (losses.ms_ssim_diff on the clipped reconstruction, so the gradient reaches the
         codec's backward through the clamp). In the h3 mode a step whose activations do not fit
-        the form has a NaN reconstruction, and so a NaN distortion, as its mse would be."""
+        the form has a NaN reconstruction, and so a NaN distortion, as its mse would be.
+
+        ``steps`` (an int, a sequence or an integer tensor of B codec.step_size indices 0..31)
+        trains along the quantiser-step ladder: image b is quantised with the
+        noise proxy of the coder's convention at Δ_b, z = y/Δ_b + u, synthesised from Δ_b·z, and
+        its bits are the step pack's on z. The return is then per image, (clipped_recon,
+        dist [B], bpp [B]), all differentiable in the parameters; ``x.requires_grad`` is not
+        supported with ``steps``."""
         if distortion not in ("mse", "ms-ssim"):
             raise kernels.Iclr17Error(f"iclr17: distortion must be 'mse' or 'ms-ssim' "
                                       f"(got {distortion!r})")
+        if steps is not None:
+            return self._forward_train_steps(input_image, noise, distortion, steps)
         clipped, _, bpp, mse = self._train_outputs(input_image, noise, list(self.parameters()),
                                                    kernels.precision())
         if distortion == "ms-ssim":
             from .losses import ms_ssim_diff
             return clipped, 1 - ms_ssim_diff(clipped, input_image, data_range=1.0), bpp
+        return clipped, mse, bpp
+
+    @staticmethod
+    def _step_indices(steps, B: int):
+        """``forward_train``'s ``steps`` → B ladder indices, checked on the host."""
+        from . import codec
+        if isinstance(steps, torch.Tensor):
+            if steps.dtype.is_floating_point or steps.dtype in (torch.bool, torch.complex64,
+                                                                torch.complex128):
+                raise kernels.Iclr17Error(f"iclr17: forward_train: steps must be an integer tensor "
+                                          f"(got {steps.dtype})")
+            idx = [int(v) for v in steps.detach().reshape(-1).cpu().tolist()]
+        elif isinstance(steps, (int, np.integer)) and not isinstance(steps, bool):
+            idx = [int(steps)] * B
+        else:
+            try:
+                idx = list(steps)
+            except TypeError:
+                raise kernels.Iclr17Error(f"iclr17: forward_train: steps must be an int, a sequence "
+                                          f"or an integer tensor (got {steps!r})") from None
+        if len(idx) != B:
+            raise kernels.Iclr17Error(f"iclr17: forward_train: {len(idx)} steps for a batch of {B} "
+                                      "images")
+        for s in idx:
+            codec.step_size(s)   # raises on anything but an integer in 0..31
+        return [int(s) for s in idx]
+
+    def _forward_train_steps(self, x, noise, distortion, steps):
+        from . import codec
+        from .autograd import StepTrainFn
+        if not isinstance(x, torch.Tensor) or x.dim() != 4:
+            raise kernels.Iclr17Error("iclr17: forward_train: the image batch must be a 4-D tensor")
+        idx = self._step_indices(steps, x.shape[0])
+        if x.requires_grad:
+            raise kernels.Iclr17Error("iclr17: forward_train: steps with an image that requires a "
+                                      "gradient is not supported")
+        kernels._check(x, "image", 4)
+        if noise is None:
+            noise = self._latent_noise(x)
+        mode = kernels.precision()
+        self._warm_packs(backward=True, mode=mode)
+        steps_dev = torch.tensor([codec.step_size(s) for s in idx], dtype=torch.float32).to(
+            x.device, non_blocking=True)
+        clipped, bpp, mse = StepTrainFn.apply(x.contiguous(), noise.contiguous(), steps_dev, self,
+                                              mode, *self.parameters())
+        if distortion == "ms-ssim":
+            from .losses import ms_ssim_diff
+            return clipped, 1 - ms_ssim_diff(clipped, x, data_range=1.0, size_average=False), bpp
         return clipped, mse, bpp
 
     # ------------------------------------------------------------- rate control (codec.py)

@@ -28,7 +28,7 @@ import time
 import numpy as np
 import torch
 
-from . import data, kernels
+from . import codec, data, kernels
 from . import dist as idist
 from . import synth
 from .model import ImageCompressor, load_model, save_model
@@ -43,6 +43,9 @@ DEFAULTS = {  # train.py:15-29
     "out_channel_N": 128,
 }
 DISTORTIONS = ("mse", "ms-ssim")   # config key "distortion" (absent: "mse", the reference's loss)
+# config key "steps": [lo, hi] trains along the quantiser-step ladder: every image
+# of every batch draws a ladder index in lo..hi; "step_lambda" scales train_lambda per image
+STEP_LAMBDA_RULES = ("inverse-square", "constant")
 
 
 class AverageMeter:
@@ -75,7 +78,41 @@ def parse_config(path):
     if cfg.get("distortion", "mse") not in DISTORTIONS:
         raise ValueError(f"config: distortion must be one of {DISTORTIONS} "
                          f"(got {cfg['distortion']!r})")
+    if "steps" in cfg:
+        st = cfg["steps"]
+        ok = (isinstance(st, (list, tuple)) and len(st) == 2
+              and all(isinstance(v, int) and not isinstance(v, bool) for v in st)
+              and 0 <= st[0] <= st[1] < codec.STEPS)
+        if not ok:
+            raise ValueError(f"config: steps must be [lo, hi] with integers 0 <= lo <= hi <= "
+                             f"{codec.STEPS - 1} (got {st!r})")
+        if cfg.setdefault("step_lambda", STEP_LAMBDA_RULES[0]) not in STEP_LAMBDA_RULES:
+            raise ValueError(f"config: step_lambda must be one of {STEP_LAMBDA_RULES} "
+                             f"(got {cfg['step_lambda']!r})")
+    elif "step_lambda" in cfg:
+        raise ValueError("config: step_lambda needs steps")
     return cfg
+
+
+def sample_steps(lo, hi, batch, global_step, rank, seed):
+    """The ladder indices of one rank's batch at one step: ``batch`` independent uniform draws
+    from lo..hi (inclusive), a pure function of its arguments (a counter-based generator keyed by
+    seed, rank and global_step: no state to checkpoint, no device RNG)."""
+    rng = np.random.Generator(np.random.Philox(key=[int(seed) & (2 ** 64 - 1),
+                                                    (int(rank) << 40) ^ int(global_step)]))
+    return [int(v) for v in rng.integers(lo, hi + 1, size=batch)]
+
+
+def step_lambdas(lam, steps, rule="inverse-square"):
+    """λ per image. "inverse-square": λ_b = lam / Δ_b², exactly ``lam`` at the unit step (index
+    8). At high rate D ∝ Δ² and R ≈ −log₂Δ + c, so the slope dD/dR of the operating point
+    scales with Δ²: a fixed λ would pull every step towards one point of the curve, λ/Δ² keeps
+    each image at the trade-off its own step stands for. "constant": λ_b = lam."""
+    if rule not in STEP_LAMBDA_RULES:
+        raise ValueError(f"step_lambda must be one of {STEP_LAMBDA_RULES} (got {rule!r})")
+    if rule == "constant":
+        return [float(lam) for _ in steps]
+    return [float(lam) / codec.step_size(s) ** 2 for s in steps]
 
 
 def learning_rate(cfg, global_step):
@@ -236,16 +273,28 @@ def main(argv=None):
 def train_epoch(net, loader, optimizer, reducer, cfg, lam, lr, epoch, global_step, tot, args,
                 device):
     """train(), train.py:84-154: one pass over the loader's epoch. With the config's
-    "distortion": "ms-ssim" the loss is train_lambda · (1 − MS-SSIM(clipped, x)) + bpp."""
+    "distortion": "ms-ssim" the loss is train_lambda · (1 − MS-SSIM(clipped, x)) + bpp. With
+    "steps" every image draws a ladder index (``sample_steps``) and the loss is the batch mean of
+    λ_b · dist_b + bpp_b (``step_lambdas``); the meters log batch means."""
     logger.info("Epoch {} begin".format(epoch))
     net.train()
     msssim = cfg.get("distortion", "mse") == "ms-ssim"
+    ladder = cfg.get("steps")
     meters = {k: AverageMeter(cfg["print_freq"])
               for k in ("elapsed", "loss", "psnr", "bpp", "mse", "msssim")}
     for x in loader.epoch(epoch):
         t0 = time.time()
         global_step += 1
-        if msssim:
+        if ladder:
+            st = sample_steps(ladder[0], ladder[1], x.shape[0], global_step, idist.rank(),
+                              args.seed)
+            lams = torch.tensor(step_lambdas(lam, st, cfg["step_lambda"]), dtype=torch.float32)
+            clipped, dist, bpp = net.forward_train(x, distortion=cfg.get("distortion", "mse"),
+                                                   steps=st)
+            rd_loss = torch.mean(lams.to(x.device, non_blocking=True) * dist + bpp)
+            dist, bpp = dist.detach().mean(), bpp.detach().mean()
+            mse = dist
+        elif msssim:
             clipped, dist, bpp = net.forward_train(x, distortion="ms-ssim")
             rd_loss = lam * dist + bpp
         else:

@@ -300,6 +300,34 @@ int iclr17_rate_sweep_partials(int h, int w, int N);
 int iclr17_rate_sweep(const float* y, int B, int h, int w, int N, const float* rate_packed,
                       const float* steps, int S, double* partial, double* bits, void* stream);
 
+/* ------------------------------------------------------------ stepped training (csrc/steptrain.hip)
+ * The quantiser / rate part of a training step whose images each have a ladder step of their own
+ * (DESIGN.md §0h): the coder's convention above with the rounding replaced by noise. Per image b
+ * with Δ = steps_dev[b] (device fp32 [B]; finite and > 0, the caller's duty: they never reach the
+ * host here):  z = y/Δ + u (fp32 divide, then add),  ỹ = Δ·z,  bits_b = Σ element_bits(z, step
+ * pack of Δ). Any N ≥ 1 whose 11·N rate floats fit the LDS. No atomics: bitwise reproducible. */
+/* y, z, y_deq: fp32 NHWC [B][h][w][N]; noise: NCHW [B][N][h][w] (as conv3's noise quantiser reads
+ * it); rate_packed: the UNscaled pack. bits_partial: [B][iclr17_rate_bits_partials(N, h, w)]
+ * doubles, rate_bits' own partials of z (same chunks, thread map and order of addition), for
+ * iclr17_reduce_partials. */
+int iclr17_step_noise_rate(const float* y, const float* noise, int B, int h, int w, int N,
+                           const float* steps_dev, const float* rate_packed, float* z,
+                           float* y_deq, double* bits_partial, void* stream);
+/* g_y = g_deq + g_bits[b] · ∂bits_b/∂z / Δ (g_deq = ∂L/∂ỹ, g_bits: device fp32 [B]) and the
+ * rate-parameter partials rate_partial[B · iclr17_step_rate_bwd_partials(h, w)][11][N] in the
+ * slots iclr17_rate_param_grad reads: slot 0 is ∂/∂softplus(h1) (the step pack's partial times
+ * Δ), slots 1..10 as they are. g_y must not alias g_deq. */
+int iclr17_step_rate_bwd_partials(int h, int w);
+int iclr17_step_noise_rate_bwd(const float* z, const float* g_deq, int B, int h, int w, int N,
+                               const float* steps_dev, const float* rate_packed,
+                               const float* g_bits, float* g_y, float* rate_partial,
+                               void* stream);
+/* iclr17_grad_recon with one MSE weight per image: g_mse is a device fp32 [B] (nullable), the
+ * weight of mean over image b's per_image elements of (recon − x)²; g_clip as there. */
+int iclr17_grad_recon_images(const float* recon, const float* x, const float* g_mse,
+                             const float* g_clip, int B, int64_t per_image, float* g_recon,
+                             void* stream);
+
 /* testKodak's MS-SSIM (train.py:178 → models/ms_ssim_torch.py:123-196): per-image
  * ms_ssim(x, y, data_range) of NCHW [B,3,H,W] fp32 images, 11-tap σ=1.5 window, 5 levels (each
  * level must be ≥ 11×11: H, W ≥ 161 or so), the reference's level weights and final product.
