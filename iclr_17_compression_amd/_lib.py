@@ -100,6 +100,12 @@ SIGNATURES = {
     "iclr17_dequantise_step": (_I, [_P, _I64, _F, _P, _P]),
     "iclr17_rate_sweep_partials": (_I, [_I, _I, _I]),
     "iclr17_rate_sweep": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "iclr17_quantise_step_map": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "iclr17_dequantise_step_map": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "iclr17_rate_sweep_offsets": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "iclr17_rans_encode_map": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P,
+                                    ctypes.c_long, _P, _P, _P]),
+    "iclr17_rans_decode_map": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P]),
     "iclr17_step_noise_rate": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "iclr17_step_rate_bwd_partials": (_I, [_I, _I]),
     "iclr17_step_noise_rate_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

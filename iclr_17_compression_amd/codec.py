@@ -48,8 +48,30 @@ Blobs coded with ``step=8`` are I17Q too, with the plain blob's payload; only th
 rate option writes I17C. ``decompress_images`` takes both kinds in one call. The weights were
 trained at Δ = 1: away from the unit step the quality is whatever the model gives.
 
+Step maps (regions of interest). ``compress_images(..., step_offsets=maps, block=g)`` gives every
+block of g×g latent positions (g in 1, 2, 4, 8, 16; 16·g pixels square on the canvas) a step of its
+own. The latent of a canvas is h×w, the map mh×mw = ⌈h/g⌉×⌈w/g⌉ (``map_shape``), row-major, ragged at
+the bottom and right; position (i, j) reads block (i // g, j // g). ``maps`` holds per image None
+(all zero) or signed integer offsets [mh, mw] (``roi_offsets`` makes one from pixel boxes). With a
+base index — ``step``, what a budget picks, or 8 — block e is coded at the effective index
+clamp(base + offset, 0, 31): ŷ = rint(y/Δ_e), the synthesis runs on Δ_e·ŷ, and each channel's
+symbol is coded with that channel's table of step e. A budget works as above with one
+``rate_sweep_offsets`` per batch (the estimate of every image at all 32 *bases*), the map's bytes
+counted in the overhead, and a blob over budget moving the base one index coarser. The blob:
+
+    struct "<4sBBHHBBIIQ":  magic b"I17M" | version u8 = 1 | P | N | K | base u8 | log2 g u8 |
+                            H | W | fingerprint
+    then mh·mw bytes of effective indices (each < 32: the decoder needs no clamp rule), then the
+    payload as in the other kinds.
+
+Every call with ``step_offsets`` writes I17M, zero offsets included; without it the other two
+kinds are written byte for byte as before. ``decompress_images`` takes the three kinds mixed. No
+quality claim is made: the weights were trained at Δ = 1, and PSNR inside or outside a region is
+whatever the model gives.
+
     python -m iclr_17_compression_amd.codec encode IN.png OUT.i17c --weights CKPT [--N 192]
                                             [--step S | --max-bytes B | --bpp R]
+                                            [--roi X0,Y0,X1,Y1,OFF ...] [--block G]
     python -m iclr_17_compression_amd.codec decode IN.i17c OUT.png --weights CKPT
     python -m iclr_17_compression_amd.codec eval IMG... --weights CKPT [--ms-ssim] [--steps 4,8,12]
 """
@@ -81,6 +103,15 @@ Header = namedtuple("Header", "P N K H W fingerprint")
 STEP_MAGIC = b"I17Q"
 STEP_HEADER = struct.Struct("<4sBBHHBxIIQ")
 assert STEP_HEADER.size == HEADER.size   # the payload starts at the same byte in both kinds
+
+MAP_MAGIC = b"I17M"
+MAP_HEADER = struct.Struct("<4sBBHHBBIIQ")
+assert MAP_HEADER.size == HEADER.size    # the map starts where the other kinds' payload does
+DEFAULT_BLOCK = 4                        # block edge in latent positions: 64×64 pixels
+
+# what parse_blob gives for a mapped blob in place of a ladder index: the base index, the block
+# edge g, the effective indices (uint8 [mh, mw]) and the byte at which the payload starts
+StepMap = namedtuple("StepMap", "base block indices payload")
 
 # ------------------------------------------------------------------------------ ladder
 STEPS = 32
@@ -243,12 +274,120 @@ def parse_step_header(blob: bytes, N: Optional[int] = None,
     return head, step
 
 
-def parse_blob(blob: bytes, N: Optional[int] = None,
-               fingerprint: Optional[int] = None) -> Tuple[Header, Optional[int]]:
-    """The header of either kind of blob → (Header, ladder index | None for a plain blob)."""
+def pack_map_header(P: int, N: int, K: int, base: int, block: int, H: int, W: int,
+                    fingerprint: int, indices) -> bytes:
+    """The header of a mapped blob and its map: ``pack_header``'s fields under the magic I17M with
+    the base index and log2 of the block edge in the two pad bytes, then the mh·mw effective
+    ladder indices (``map_shape``), one byte each, row-major."""
+    step_size(base)
+    pack_header(P, N, K, H, W, fingerprint)   # the shared fields' range checks
+    mh, mw = map_shape(H, W, block)
+    a = np.asarray(indices)
+    if a.dtype.kind not in "iu" or a.shape != (mh, mw) or a.min() < 0 or a.max() >= STEPS:
+        raise Iclr17Error(f"iclr17: codec: the step map of a {H}x{W} image with block {block} is "
+                          f"[{mh}, {mw}] ladder indices 0..{STEPS - 1} (got {a.dtype} {a.shape})")
+    return MAP_HEADER.pack(MAP_MAGIC, VERSION, P, N, K, int(base), kernels.MAP_BLOCKS.index(block), H, W,
+                           fingerprint & (2 ** 64 - 1)) + a.astype(np.uint8).tobytes()
+
+
+def parse_map_header(blob: bytes, N: Optional[int] = None,
+                     fingerprint: Optional[int] = None) -> Tuple[Header, StepMap]:
+    """The header and map of a mapped (I17M) blob → (Header, StepMap), checked as ``parse_header``
+    checks a plain one; a base or map byte outside the ladder, a block edge above 16 and a
+    truncated map raise."""
+    if len(blob) < MAP_HEADER.size:
+        raise Iclr17Error(f"iclr17: codec: truncated header ({len(blob)} of {MAP_HEADER.size} bytes)")
+    magic, version, P, n, K, base, lg, H, W, fp = MAP_HEADER.unpack_from(blob)
+    head = _checked_header(MAP_MAGIC, magic, version, P, n, K, H, W, fp, N, fingerprint)
+    if base >= STEPS:
+        raise Iclr17Error(f"iclr17: codec: quantiser step {base} in the stream (this build reads "
+                          f"0..{STEPS - 1})")
+    if lg > 4:
+        raise Iclr17Error(f"iclr17: codec: step-map block of 2^{lg} latent positions in the stream "
+                          "(this build reads 2^0..2^4)")
+    mh, mw = map_shape(H, W, 1 << lg)
+    end = MAP_HEADER.size + mh * mw
+    if len(blob) < end:
+        raise Iclr17Error(f"iclr17: codec: truncated step map ({len(blob) - MAP_HEADER.size} of "
+                          f"{mh * mw} bytes)")
+    indices = np.frombuffer(bytes(blob[MAP_HEADER.size:end]), dtype=np.uint8).reshape(mh, mw)
+    if indices.size and int(indices.max()) >= STEPS:
+        raise Iclr17Error(f"iclr17: codec: quantiser step {int(indices.max())} in the stream's step "
+                          f"map (this build reads 0..{STEPS - 1})")
+    return head, StepMap(base, 1 << lg, indices, end)
+
+
+def parse_blob(blob: bytes, N: Optional[int] = None, fingerprint: Optional[int] = None):
+    """The header of any kind of blob → (Header, ladder index | None for a plain blob | StepMap
+    for a mapped one)."""
     if bytes(blob[:4]) == STEP_MAGIC:
         return parse_step_header(blob, N, fingerprint)
+    if bytes(blob[:4]) == MAP_MAGIC:
+        return parse_map_header(blob, N, fingerprint)
     return parse_header(blob, N, fingerprint), None
+
+
+# ------------------------------------------------------------------------------ step maps
+def map_shape(H: int, W: int, block: int = DEFAULT_BLOCK) -> Tuple[int, int]:
+    """(mh, mw) of the step map of an H×W image: its canvas's latent is h×w = canvas/16, a block
+    is ``block``×``block`` latent positions (1, 2, 4, 8 or 16), and mh×mw = ⌈h/block⌉×⌈w/block⌉."""
+    Hc, Wc = canvas(H, W)
+    return kernels.map_shape(Hc // 16, Wc // 16, block)
+
+
+def effective_indices(base: int, offsets) -> np.ndarray:
+    """clamp(base + offset, 0, 31) per block as uint8: what the stream's map holds."""
+    step_size(base)
+    return np.clip(int(base) + np.asarray(offsets, dtype=np.int64), 0, STEPS - 1).astype(np.uint8)
+
+
+def roi_offsets(H: int, W: int, boxes, block: int = DEFAULT_BLOCK) -> np.ndarray:
+    """Step offsets of an H×W image from pixel boxes → int32 [mh, mw] (``map_shape``). ``boxes``:
+    (x0, y0, x1, y1, offset) with x0 ≤ x < x1, y0 ≤ y < y1 in pixels; a block (16·block pixels
+    square on the canvas) that intersects a box gets its offset, where boxes overlap the most
+    negative (finest) offset wins, and every other block gets 0."""
+    mh, mw = map_shape(H, W, block)
+    side = 16 * block
+    out = np.zeros((mh, mw), dtype=np.int32)
+    hit = np.zeros((mh, mw), dtype=bool)
+    for box in boxes:
+        if len(box) != 5:
+            raise Iclr17Error(f"iclr17: codec: a box is (x0, y0, x1, y1, offset) (got {box!r})")
+        x0, y0, x1, y1, off = box
+        if isinstance(off, bool) or not isinstance(off, (int, np.integer)):
+            raise Iclr17Error(f"iclr17: codec: a box's offset is an integer (got {off!r})")
+        x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, mw * side), min(y1, mh * side)
+        if x0 >= x1 or y0 >= y1:
+            continue   # empty, or outside the canvas
+        rows = slice(int(y0 // side), int(-(-y1 // side)))
+        cols = slice(int(x0 // side), int(-(-x1 // side)))
+        out[rows, cols] = np.where(hit[rows, cols], np.minimum(out[rows, cols], off), off)
+        hit[rows, cols] = True
+    return out
+
+
+def checked_offsets(shapes: Sequence[Tuple[int, int]], step_offsets, block: int) -> List[np.ndarray]:
+    """``compress_images``'s ``step_offsets`` for images of sizes ``shapes``, checked on the host:
+    one entry per image, each None (all zero) or an integer array [mh, mw] → int8 arrays, the
+    values cut to −31..31 (beyond that the clamp to the ladder gives the same index)."""
+    if isinstance(step_offsets, np.ndarray) and step_offsets.ndim == 2:
+        step_offsets = [step_offsets]
+    if len(step_offsets) != len(shapes):
+        raise Iclr17Error(f"iclr17: codec: step_offsets has {len(step_offsets)} entries for "
+                          f"{len(shapes)} images")
+    out = []
+    for i, ((H, W), off) in enumerate(zip(shapes, step_offsets)):
+        mh, mw = map_shape(H, W, block)
+        if off is None:
+            out.append(np.zeros((mh, mw), dtype=np.int8))
+            continue
+        a = off.detach().cpu().numpy() if isinstance(off, torch.Tensor) else np.asarray(off)
+        if a.dtype.kind not in "iu" or a.shape != (mh, mw):
+            raise Iclr17Error(f"iclr17: codec: step_offsets[{i}] must be integers of shape "
+                              f"[{mh}, {mw}] for a {H}x{W} image with block {block} (got {a.dtype} "
+                              f"{tuple(a.shape)})")
+        out.append(np.clip(a.astype(np.int64), 1 - STEPS, STEPS - 1).astype(np.int8))
+    return out
 
 
 # ------------------------------------------------------------------------------ batches
@@ -274,16 +413,17 @@ def upload_packed(images: Sequence[np.ndarray], device):
     return host.to(device, non_blocking=True), [int(o) for o in offsets], [im.shape[:2] for im in images]
 
 
-def rate_request(n: int, step=None, max_bytes=None, bpp=None):
+def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None):
     """The rate options of ``compress_images`` for ``n`` images, checked on the host before any
     device use → None (the plain path), ("step", index) or ("budget", per-image values, is_bpp).
-    At most one option; a budget is a scalar or one value per image."""
+    At most one option; a budget is a scalar or one value per image. ``step_offsets`` goes with
+    any one of them, the option then giving the base index; alone it means the unit step."""
     given = [k for k, v in (("step", step), ("max_bytes", max_bytes), ("bpp", bpp)) if v is not None]
     if len(given) > 1:
         raise Iclr17Error(f"iclr17: codec: {' and '.join(given)} given together (at most one of "
                           "step, max_bytes, bpp)")
     if not given:
-        return None
+        return None if step_offsets is None else ("step", UNIT_STEP)
     if step is not None:
         step_size(step)
         return "step", int(step)
@@ -299,9 +439,13 @@ def rate_request(n: int, step=None, max_bytes=None, bpp=None):
 def compress_images(net, images, max_batch: int = 64,
                     streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                     K: int = kernels.ENTROPY_K, step: Optional[int] = None, max_bytes=None,
-                    bpp=None, stats: Optional[dict] = None) -> List[bytes]:
+                    bpp=None, stats: Optional[dict] = None, step_offsets=None,
+                    block: int = DEFAULT_BLOCK) -> List[bytes]:
     imgs = [as_u8_hwc(im) for im in images]
-    request = rate_request(len(imgs), step, max_bytes, bpp)
+    request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets)
+    per_image = None
+    if step_offsets is not None:
+        per_image = checked_offsets([im.shape[:2] for im in imgs], step_offsets, block)
     device = next(net.parameters()).device
     fp, N, P = fingerprint(net), net.out_channel_N, streams_per_image
     blobs: List[Optional[bytes]] = [None] * len(imgs)
@@ -321,22 +465,33 @@ def compress_images(net, images, max_batch: int = 64,
             continue
         # one analysis pass per batch, however many steps and re-encodes follow
         y = net.latents(x)
+        # with step offsets: the batch's maps [B, mh, mw]; a step is then the BASE index, and a
+        # blob also carries its map
+        offs = None if per_image is None else np.stack([per_image[i] for i in idx])
+        overhead = blob_overhead(P) + (0 if offs is None else offs[0].size)
         if request[0] == "step":
             chosen = [request[1]] * len(idx)
         else:
-            est = net.rate_sweep(y, latent=True).cpu().numpy()
+            est = (net.rate_sweep(y, latent=True) if offs is None
+                   else net.rate_sweep_offsets(y, offs, block)).cpu().numpy()
             chosen = []
             for k, i in enumerate(idx):
                 try:
-                    chosen.append(choose_step(est[k], budgets[i], blob_overhead(P)))
+                    chosen.append(choose_step(est[k], budgets[i], overhead))
                 except Iclr17Error:
                     chosen.append(STEPS - 1)   # no estimate fits: the coarsest step decides below
 
         def encode(ks, s):
             sel = y if len(ks) == len(idx) else y[torch.tensor(ks, device=device)]
-            enc = net.compress_latents(sel, s, streams_per_image=P, K=K)
-            return [pack_step_header(P, N, K, s, *shapes[k], fp) + string
-                    for k, string in zip(ks, enc["strings"])]
+            if offs is None:
+                enc = net.compress_latents(sel, s, streams_per_image=P, K=K)
+                return [pack_step_header(P, N, K, s, *shapes[k], fp) + string
+                        for k, string in zip(ks, enc["strings"])]
+            emap = effective_indices(s, offs[ks])
+            enc = net.compress_latents(sel, None, streams_per_image=P, K=K, step_map=emap,
+                                       block=block)
+            return [pack_map_header(P, N, K, s, block, *shapes[k], fp, m) + string
+                    for k, m, string in zip(ks, emap, enc["strings"])]
 
         coded, again = encode_to_budget(chosen, [budgets[i] for i in idx], encode,
                                         [f"image {i} ({H}x{W})" for i, (H, W) in zip(idx, shapes)])
@@ -354,18 +509,25 @@ def decode_groups(net, blobs, max_batch: int, refs=None):
     fp, N = fingerprint(net), net.out_channel_N
     parsed = [parse_blob(b, N, fp) for b in blobs]
     heads, steps = [h for h, _ in parsed], [s for _, s in parsed]
-    for b, h in zip(blobs, heads):
+    starts = [s.payload if isinstance(s, StepMap) else HEADER.size for s in steps]
+    for b, h, start in zip(blobs, heads, starts):
         # decompress reads the payload as 16-bit words and checks the counts; an odd rest cannot
         # even be read that way
-        if len(b) < HEADER.size + 4 * h.P or (len(b) - HEADER.size) % 2:
+        if len(b) < start + 4 * h.P or (len(b) - start) % 2:
             raise Iclr17Error(f"iclr17: codec: truncated stream ({len(b)} bytes)")
     out: List[Optional[np.ndarray]] = [None] * len(blobs)
     sses: Optional[List[Optional[int]]] = [None] * len(blobs) if refs is not None else None
-    for idx in _group([canvas(h.H, h.W) + (h.P, h.K, s) for h, s in parsed], max_batch):
-        h0 = heads[idx[0]]
+    # a batch: one canvas, P, K and step; mapped blobs of one block edge batch whatever their maps
+    keys = [canvas(h.H, h.W) + (h.P, h.K, ("map", s.block) if isinstance(s, StepMap) else s)
+            for h, s in parsed]
+    for idx in _group(keys, max_batch):
+        h0, s0 = heads[idx[0]], steps[idx[0]]
         Hc, Wc = canvas(h0.H, h0.W)
-        dec = net.decompress([blobs[i][HEADER.size:] for i in idx], (Hc // 16, Wc // 16),
-                             streams_per_image=h0.P, K=h0.K, device=device, step=steps[idx[0]])
+        how = {"step": s0}
+        if isinstance(s0, StepMap):
+            how = {"step_map": np.stack([steps[i].indices for i in idx]), "block": s0.block}
+        dec = net.decompress([blobs[i][starts[i]:] for i in idx], (Hc // 16, Wc // 16),
+                             streams_per_image=h0.P, K=h0.K, device=device, **how)
         shapes = [(heads[i].H, heads[i].W) for i in idx]
         ref = None
         if refs is not None:
@@ -385,9 +547,11 @@ def decode_groups(net, blobs, max_batch: int, refs=None):
 
 
 def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
-                    step: Optional[int] = None, max_bytes=None, bpp=None) -> List[dict]:
+                    step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
+                    block: int = DEFAULT_BLOCK) -> List[dict]:
     imgs = [as_u8_hwc(im) for im in images]
-    blobs = compress_images(net, imgs, max_batch=max_batch, step=step, max_bytes=max_bytes, bpp=bpp)
+    blobs = compress_images(net, imgs, max_batch=max_batch, step=step, max_bytes=max_bytes, bpp=bpp,
+                            step_offsets=step_offsets, block=block)
     recons, sses = decode_groups(net, blobs, max_batch, refs=imgs)
     device = next(net.parameters()).device
     res = []
@@ -396,6 +560,8 @@ def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
         r = {"bytes": len(blob), "bpp": 8 * len(blob) / (H * W), "sse_u8": sse,
              "psnr_u8": 10.0 * math.log10(255.0 ** 2 * 3 * H * W / sse) if sse else math.inf,
              "recon": rec, "step": parse_blob(blob)[1]}
+        if isinstance(r["step"], StepMap):   # a mapped blob: its base index, and the map beside it
+            r["step_map"], r["block"], r["step"] = r["step"].indices, r["step"].block, r["step"].base
         if want_msssim:
             r["ms_ssim"] = r["ms_ssim_db"] = None
             if kernels.query("iclr17_ms_ssim_workspace_size", 1, H, W):   # 0: too small for 5 levels
@@ -424,6 +590,20 @@ def _model(args):
     return net.to(torch.device("cuda:0")).eval()
 
 
+def _boxes(texts: Sequence[str]) -> List[Tuple[int, int, int, int, int]]:
+    """--roi X0,Y0,X1,Y1,OFF arguments as ``roi_offsets`` boxes."""
+    boxes = []
+    for t in texts:
+        try:
+            box = tuple(int(v) for v in t.split(","))
+        except ValueError:
+            box = ()
+        if len(box) != 5:
+            raise Iclr17Error(f"iclr17: codec: --roi takes X0,Y0,X1,Y1,OFF as five integers (got {t!r})")
+        boxes.append(box)
+    return boxes
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     common = argparse.ArgumentParser(add_help=False)
     common.add_argument("--weights", required=True, help="checkpoint (model.load_model)")
@@ -439,6 +619,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     rate.add_argument("--step", type=int, default=None, help="ladder index 0..31 (8: the unit step)")
     rate.add_argument("--max-bytes", type=int, default=None, help="byte budget of the output file")
     rate.add_argument("--bpp", type=float, default=None, help="budget in bits per pixel of the file")
+    enc.add_argument("--roi", action="append", default=None, metavar="X0,Y0,X1,Y1,OFF",
+                     help="a pixel box whose blocks get the ladder offset OFF (negative: finer); "
+                          "repeatable, the finest offset wins where boxes overlap")
+    enc.add_argument("--block", type=int, default=DEFAULT_BLOCK, choices=kernels.MAP_BLOCKS,
+                     help="block edge of the step map in latent positions (16 pixels each)")
     dec = sub.add_parser("decode", parents=[common], help="IN.i17c OUT.png")
     dec.add_argument("input")
     dec.add_argument("output")
@@ -451,8 +636,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     net = _model(args)
     with kernels.precision_scope(args.precision or kernels.precision()):
         if args.cmd == "encode":
-            blob = net.compress_images([_load_image(args.input)], step=args.step,
-                                       max_bytes=args.max_bytes, bpp=args.bpp)[0]
+            image, roi = _load_image(args.input), {}
+            if args.roi:
+                roi = {"step_offsets": [roi_offsets(*image.shape[:2], _boxes(args.roi), args.block)],
+                       "block": args.block}
+            blob = net.compress_images([image], step=args.step, max_bytes=args.max_bytes,
+                                       bpp=args.bpp, **roi)[0]
             with open(args.output, "wb") as f:
                 f.write(blob)
         elif args.cmd == "decode":

@@ -157,6 +157,30 @@ __device__ __forceinline__ float element_bits(float z, const float* __restrict__
   return bits;
 }
 
+// bitparm_cdf with the parameters of one channel in registers and row 0 given separately (the
+// step pack's row 0): the same separate fp32 ops in the same order. Shared by the
+// rate sweeps of ratectl.hip and stepmap.hip.
+__device__ __forceinline__ float cdf_regs(float v, float sp0, const float (&p)[kRateRows]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float sp = k == 0 ? sp0 : p[3 * k + 0];
+    const float t = v * sp + p[3 * k + 1];
+    v = t + tanhf(t) * p[3 * k + 2];
+  }
+  const float t = v * p[9] + p[10];
+  return 1.0f / (1.0f + expf(-t));
+}
+
+// element_bits on cdf_regs
+__device__ __forceinline__ float bits_regs(float z, float sp0, const float (&p)[kRateRows]) {
+  const float hi = cdf_regs(z + 0.5f, sp0, p);
+  const float lo = cdf_regs(z - 0.5f, sp0, p);
+  const float prob = hi - lo;
+  float bits = (-1.0f * logf(prob + 1e-10f)) / 0.693147182464599609375f;
+  bits = fminf(fmaxf(bits, 0.0f), 50.0f);
+  return bits;
+}
+
 // The backward of element_bits at one element, as the autograd of model.py:71-78 /
 // bitEstimator.py:20-25 evaluates it: returns gsc · ∂bits/∂z and adds gsc · ∂bits/∂(row k of the
 // pack) into pg[k]. Shared by the rate epilogue of deconv1's dgrad (engine.h) and the stepped

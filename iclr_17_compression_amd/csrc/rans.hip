@@ -15,6 +15,9 @@
 // ordered by lane (ballot + prefix count), so the stream stays one word sequence. The encoder
 // writes back to front into its own scratch slot; the offsets scan and the pack kernel then
 // concatenate the streams. The CDF tables are staged in LDS.
+//
+// encode_map_kernel / decode_map_kernel are the same coder with a table set per block of latent
+// positions: see "step maps" below.
 #include "common.h"
 
 namespace iclr17 {
@@ -271,6 +274,231 @@ __global__ void __launch_bounds__(W) decode_kernel(const unsigned short* __restr
   if (lane == 0 && bad) atomicOr(status, bad);
 }
 
+// ----------------------------------------------------------------------------- step maps (§0i)
+// The same coder with a table row per symbol: the symbol of channel c at latent position (i, j)
+// of image b is coded with row slot·N + c of the stacked tables cum[S][N][2K + 3], slot =
+// slots[b][i >> lg][j >> lg]. Stream layout, symbol order, lane ownership, word order and escapes
+// are encode_kernel's and decode_kernel's.
+//
+// S·N tables do not fit the LDS (32 steps × 192 channels × 67 ints = 1.6 MB), and a stream walks
+// its channels in order, so the LDS holds a WINDOW: the rows of wc consecutive channels for all S
+// slots, sc[slot][wc][2K + 3]. When a block's leading channel (the decoder walks up, the encoder
+// down) has left the window, the wave stages the next one (one wave per workgroup: the barrier
+// is cheap). A lane whose channel lies outside the window — a block that straddles its edge, or
+// a latent so small that a block of 64 symbols spans more channels than the window holds — reads
+// its row from global memory. wc = 0: no window, every row from global memory.
+struct MapTab {
+  const int* cum;               // [S][N][2K + 3]
+  const unsigned char* slots;   // [B][mhw]
+  int S, w, mw, mhw, lg;
+  int wc;                       // channels per LDS window
+};
+
+struct TabRow {   // one symbol's table row, in the window or in global memory
+  const int* l;
+  const int* g;
+  bool in;
+  __device__ __forceinline__ int operator[](int i) const { return in ? l[i] : g[i]; }
+};
+
+struct Window {
+  int c0 = 0, n = 0;   // channels [c0, c0 + n) are staged
+};
+
+// stage channels [c0, c0 + n) of every slot (n ≤ wc); all lanes call it
+__device__ __forceinline__ void stage_window(const MapTab& m, int N, int TS, int c0, int n,
+                                             int* sc) {
+  __syncthreads();   // every lane is done with the window that goes
+  for (int s = 0; s < m.S; ++s) {
+    const int* src = m.cum + ((long)s * N + c0) * TS;
+    int* dst = sc + (long)s * m.wc * TS;
+    for (int i = threadIdx.x; i < n * TS; i += W) dst[i] = src[i];
+  }
+  __syncthreads();
+}
+
+// the row of symbol i (channel cl of the stream's group) of stream (b, grp)
+__device__ __forceinline__ TabRow map_row(const MapTab& m, const StreamGeo& g, int TS,
+                                          const Window& win, const int* sc, int b, int grp,
+                                          int i) {
+  const int cl = i / g.HW, pix = i - cl * g.HW;
+  const int r = pix / m.w, q = pix - r * m.w;
+  int slot = m.slots[(long)b * m.mhw + (r >> m.lg) * m.mw + (q >> m.lg)];
+  slot = slot < m.S ? slot : m.S - 1;   // the caller checked the map; never read past the tables
+  const int c = grp * g.cpg + cl;
+  TabRow t;
+  t.in = c >= win.c0 && c < win.c0 + win.n;
+  t.l = sc + ((long)slot * m.wc + (c - win.c0)) * TS;
+  t.g = m.cum + ((long)slot * g.N + c) * TS;
+  return t;
+}
+
+__global__ void __launch_bounds__(W) encode_map_kernel(const float* __restrict__ y, StreamGeo g,
+                                                       MapTab m, int K,
+                                                       unsigned short* __restrict__ scratch,
+                                                       long cap, unsigned* __restrict__ lengths,
+                                                       int* __restrict__ status) {
+  extern __shared__ int sc[];
+  const int NS = 2 * K + 2, TS = NS + 1;
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int b = s / g.P, grp = s - b * g.P;
+  unsigned short* out = scratch + (long)s * cap;
+  long ptr = cap;
+  unsigned x = kL;
+  int bad = 0;
+  const int nsym = g.cpg * g.HW;
+  const int nblk = (nsym + W - 1) / W;
+  Window win;
+  for (int blk = nblk - 1; blk >= 0; --blk) {
+    if (m.wc > 0) {   // the encoder walks down: restage once the block's last channel is below
+      const int last = blk * W + W - 1 < nsym ? blk * W + W - 1 : nsym - 1;
+      const int chi = grp * g.cpg + last / g.HW;
+      if (win.n == 0 || chi < win.c0) {
+        const int c0 = chi - m.wc + 1 > grp * g.cpg ? chi - m.wc + 1 : grp * g.cpg;
+        win.c0 = c0;
+        win.n = chi - c0 + 1;
+        stage_window(m, g.N, TS, win.c0, win.n, sc);
+      }
+    }
+    const int i = blk * W + lane;
+    const bool act = i < nsym;
+    int sym = 0, pay = -1;
+    TabRow cc = map_row(m, g, TS, win, sc, b, grp, act ? i : 0);
+    if (act) {
+      const long e = sym_index(g, b, grp, i);
+      const float v = y[e];
+      const float r = rintf(v);
+      if (!(r == v)) { bad |= ST_NONINT; sym = K; }   // NaN / non-integer
+      else if (fabsf(v) > 32767.f) { bad |= ST_RANGE; sym = K; }
+      else {
+        const int iv = (int)v;
+        sym = (iv >= -K && iv <= K) ? iv + K : NS - 1;
+        if (sym == NS - 1) pay = iv + 32768;
+      }
+    }
+    // sub-round B: escape payloads (uniform, freq 1: always one word out)
+    {
+      const bool need = pay >= 0;
+      const int2 rc = lane_rank(need, lane);
+      if (need) {
+        out[ptr - rc.y + rc.x] = (unsigned short)(x & 0xffffu);
+        x = ((x >> 16) << 16) + (unsigned)pay;
+      }
+      ptr -= rc.y;
+    }
+    // sub-round A: the symbols
+    {
+      const unsigned start = (unsigned)cc[sym], f = (unsigned)cc[sym + 1] - start;
+      const bool need = act && x >= (f << 16);
+      const int2 rc = lane_rank(need, lane);
+      if (need) {
+        out[ptr - rc.y + rc.x] = (unsigned short)(x & 0xffffu);
+        x >>= 16;
+      }
+      ptr -= rc.y;
+      if (act) x = ((x / f) << 16) + (x % f) + start;
+    }
+  }
+  ptr -= 2 * W;
+  out[ptr + 2 * lane] = (unsigned short)(x >> 16);
+  out[ptr + 2 * lane + 1] = (unsigned short)(x & 0xffffu);
+  if (lane == 0) lengths[s] = (unsigned)(cap - ptr);
+  bad = wave_or(bad);
+  if (lane == 0 && bad) atomicOr(status, bad);
+}
+
+__global__ void __launch_bounds__(W) decode_map_kernel(const unsigned short* __restrict__ words,
+                                                       const long* __restrict__ offsets,
+                                                       StreamGeo g, MapTab m, int K,
+                                                       float* __restrict__ y,
+                                                       int* __restrict__ status) {
+  extern __shared__ int sc[];
+  const int NS = 2 * K + 2, TS = NS + 1;
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int b = s / g.P, grp = s - b * g.P;
+  const unsigned short* in = words + offsets[s];
+  const long n = offsets[s + 1] - offsets[s];
+  int bad = 0;
+  if (n < 2 * W) {   // the whole workgroup (one wave) leaves: no barrier follows
+    if (lane == 0) atomicOr(status, ST_OVERRUN);
+    return;
+  }
+  unsigned x = ((unsigned)in[2 * lane] << 16) | in[2 * lane + 1];
+  long ptr = 2 * W;
+  auto word = [&](bool need, int& fail) -> unsigned {
+    const int2 rc = lane_rank(need, lane);
+    unsigned w = 0;
+    if (need) {
+      if (ptr + rc.x < n) w = in[ptr + rc.x];
+      else fail |= ST_OVERRUN;
+    }
+    ptr += rc.y;
+    return w;
+  };
+  const int nsym = g.cpg * g.HW;
+  const int nblk = (nsym + W - 1) / W;
+  Window win;
+  for (int blk = 0; blk < nblk; ++blk) {
+    if (m.wc > 0) {   // the decoder walks up: restage once the block's first channel is above
+      const int clo = grp * g.cpg + blk * W / g.HW;
+      if (win.n == 0 || clo >= win.c0 + win.n) {
+        const int end = (grp + 1) * g.cpg;
+        win.c0 = clo;
+        win.n = end - clo < m.wc ? end - clo : m.wc;
+        stage_window(m, g.N, TS, win.c0, win.n, sc);
+      }
+    }
+    const int i = blk * W + lane;
+    const bool act = i < nsym;
+    int v = 0;
+    bool esc = false;
+    if (act) {
+      const TabRow cc = map_row(m, g, TS, win, sc, b, grp, i);
+      const unsigned slot = x & 0xffffu;
+      int lo = 0, hi = NS;   // cc[lo] ≤ slot < cc[hi]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned)cc[mid] <= slot) lo = mid; else hi = mid;
+      }
+      const unsigned start = (unsigned)cc[lo], f = (unsigned)cc[lo + 1] - start;
+      x = f * (x >> 16) + slot - start;
+      v = lo - K;
+      esc = lo == NS - 1;
+    }
+    {   // sub-round A: renormalise after the symbols
+      const bool need = act && x < kL;
+      const unsigned w = word(need, bad);
+      if (need) x = (x << 16) | w;
+    }
+    {   // sub-round B: escape payloads
+      unsigned u = 0;
+      if (esc) {
+        u = x & 0xffffu;
+        x >>= 16;
+      }
+      const unsigned w = word(esc, bad);
+      if (esc) {
+        x = (x << 16) | w;
+        v = (int)u - 32768;
+      }
+    }
+    if (act) y[sym_index(g, b, grp, i)] = (float)v;
+  }
+  if (x != kL) bad |= ST_TRAIL;
+  if (lane == 0 && ptr != n) bad |= ST_TRAIL;
+  bad = wave_or(bad);
+  if (lane == 0 && bad) atomicOr(status, bad);
+}
+
+// The window of a map launch: as many channels as the S slots' rows allow in 64 KiB of LDS, at
+// most the stream's; 0 (every row from global memory) when asked or when one channel does not fit.
+int map_window(int S, int K, int cpg, int window) {
+  if (!window) return 0;
+  const long per_channel = (long)S * (2 * K + 3) * sizeof(int);
+  const long wc = 64 * 1024 / per_channel;
+  return (int)(wc < cpg ? wc : cpg);
+}
+
 }  // namespace
 }  // namespace iclr17
 
@@ -341,6 +569,53 @@ int iclr17_rans_decode(const uint16_t* words, const int64_t* offsets, int B, int
                      (const unsigned short*)words, (const long*)offsets, g, (const int*)cum, K,
                      y_hat, (int*)status);
   return check_launch("rans_decode");
+}
+
+int iclr17_rans_encode_map(const float* y_hat, int B, int h, int w, int N, int streams_per_image,
+                           const int32_t* cum, int S, int K, const uint8_t* slots, int log2_g,
+                           int window, uint16_t* scratch, long scratch_words, uint32_t* lengths,
+                           int32_t* status, void* stream) {
+  const long cap = iclr17_rans_capacity(h, w, N, streams_per_image);
+  ICLR17_REQUIRE(y_hat && cum && slots && scratch && lengths && status && B > 0 && cap > 0 &&
+                     K >= 1 && K <= 1024,
+                 ICLR17_EINVAL, "rans_encode_map: bad arguments");
+  ICLR17_REQUIRE(S >= 1 && S <= 32, ICLR17_EINVAL, "rans_encode_map: S=%d table sets (1..32)", S);
+  ICLR17_REQUIRE(log2_g >= 0 && log2_g <= 4, ICLR17_EINVAL,
+                 "rans_encode_map: log2 of the block edge is %d (0..4)", log2_g);
+  const int ns = B * streams_per_image;
+  ICLR17_REQUIRE(scratch_words >= cap * ns, ICLR17_EINVAL,
+                 "rans_encode_map: scratch of %ld words < %ld", scratch_words, cap * ns);
+  StreamGeo g{h * w, N, N / streams_per_image, streams_per_image};
+  const int gb = 1 << log2_g, mh = (h + gb - 1) / gb, mw = (w + gb - 1) / gb;
+  MapTab m{(const int*)cum, (const unsigned char*)slots, S, w, mw, mh * mw, log2_g,
+           map_window(S, K, g.cpg, window)};
+  const size_t shm = (size_t)S * m.wc * (2 * K + 3) * sizeof(int);
+  hipLaunchKernelGGL(encode_map_kernel, dim3(ns), dim3(W), shm, (hipStream_t)stream, y_hat, g, m,
+                     K, (unsigned short*)scratch, cap, (unsigned*)lengths, (int*)status);
+  return check_launch("rans_encode_map");
+}
+
+int iclr17_rans_decode_map(const uint16_t* words, const int64_t* offsets, int B, int h, int w,
+                           int N, int streams_per_image, const int32_t* cum, int S, int K,
+                           const uint8_t* slots, int log2_g, int window, float* y_hat,
+                           int32_t* status, void* stream) {
+  ICLR17_REQUIRE(words && offsets && cum && slots && y_hat && status && B > 0 && h > 0 && w > 0 &&
+                     N > 0 && streams_per_image > 0 && N % streams_per_image == 0 && K >= 1 &&
+                     K <= 1024,
+                 ICLR17_EINVAL, "rans_decode_map: bad arguments");
+  ICLR17_REQUIRE(S >= 1 && S <= 32, ICLR17_EINVAL, "rans_decode_map: S=%d table sets (1..32)", S);
+  ICLR17_REQUIRE(log2_g >= 0 && log2_g <= 4, ICLR17_EINVAL,
+                 "rans_decode_map: log2 of the block edge is %d (0..4)", log2_g);
+  const int ns = B * streams_per_image;
+  StreamGeo g{h * w, N, N / streams_per_image, streams_per_image};
+  const int gb = 1 << log2_g, mh = (h + gb - 1) / gb, mw = (w + gb - 1) / gb;
+  MapTab m{(const int*)cum, (const unsigned char*)slots, S, w, mw, mh * mw, log2_g,
+           map_window(S, K, g.cpg, window)};
+  const size_t shm = (size_t)S * m.wc * (2 * K + 3) * sizeof(int);
+  hipLaunchKernelGGL(decode_map_kernel, dim3(ns), dim3(W), shm, (hipStream_t)stream,
+                     (const unsigned short*)words, (const long*)offsets, g, m, K, y_hat,
+                     (int*)status);
+  return check_launch("rans_decode_map");
 }
 
 }  // extern "C"

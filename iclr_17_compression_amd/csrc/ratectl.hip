@@ -29,29 +29,6 @@ struct Steps {
   float d[kSweepMax];
 };
 
-// bitparm_cdf (common.h) with the parameters of one channel in registers and row 0 given
-// separately (the step pack's row 0): the same separate fp32 ops in the same order.
-__device__ __forceinline__ float cdf_regs(float v, float sp0, const float (&p)[kRateRows]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float sp = k == 0 ? sp0 : p[3 * k + 0];
-    const float t = v * sp + p[3 * k + 1];
-    v = t + tanhf(t) * p[3 * k + 2];
-  }
-  const float t = v * p[9] + p[10];
-  return 1.0f / (1.0f + expf(-t));
-}
-
-// element_bits (common.h) on cdf_regs
-__device__ __forceinline__ float bits_regs(float z, float sp0, const float (&p)[kRateRows]) {
-  const float hi = cdf_regs(z + 0.5f, sp0, p);
-  const float lo = cdf_regs(z - 0.5f, sp0, p);
-  const float prob = hi - lo;
-  float bits = (-1.0f * logf(prob + 1e-10f)) / 0.693147182464599609375f;
-  bits = fminf(fmaxf(bits, 0.0f), 50.0f);
-  return bits;
-}
-
 // One workgroup per (image, 4096-element chunk of its NHWC latent). LDS: the 11·C rate floats,
 // staged once, then one fp32 accumulator per (step, thread), so that the step loop needs no
 // unrolling (32 inlined copies of the model would not fit the instruction cache). A thread

@@ -1271,6 +1271,162 @@ def rate_sweep(y: Tensor, rate_packed: Tensor, steps: Sequence[float]) -> Tensor
     return bits
 
 
+# ------------------------------------------------------- per-block steps (csrc/stepmap.hip, rans.hip)
+MAP_BLOCKS = (1, 2, 4, 8, 16)   # block edges g of a step map, in latent positions
+
+
+def map_shape(h: int, w: int, block: int) -> Tuple[int, int]:
+    """(mh, mw) = (⌈h/g⌉, ⌈w/g⌉): the step map of an h×w latent with g×g blocks."""
+    if isinstance(block, bool) or block not in MAP_BLOCKS:
+        raise Iclr17Error(f"iclr17: step map: the block edge {block!r} is not one of {MAP_BLOCKS}")
+    return -(-h // block), -(-w // block)
+
+
+def _map_on(device, m, what: str, name: str, B: int, h: int, w: int, block: int, lo: int, hi: int,
+            dtype) -> Tensor:
+    """A per-block map (numpy or torch, any integer type, on any device) checked on the host —
+    shape [B, mh, mw], integer values in lo..hi — and uploaded as ``dtype``."""
+    mh, mw = map_shape(h, w, block)
+    a = m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m)
+    if a.dtype.kind not in "iu" or a.shape != (B, mh, mw):
+        raise Iclr17Error(f"iclr17: {what}: {name} must be integers of shape [{B}, {mh}, {mw}] "
+                          f"(got {a.dtype} {tuple(a.shape)})")
+    if a.size and (int(a.min()) < lo or int(a.max()) > hi):
+        raise Iclr17Error(f"iclr17: {what}: {name} must lie in {lo}..{hi} (got "
+                          f"{int(a.min())}..{int(a.max())})")
+    return torch.from_numpy(np.ascontiguousarray(a.astype(dtype))).to(device)
+
+
+def _ladder_arg(steps: Sequence[float], what: str):
+    ds = [_step_value(s, what) for s in steps]
+    if len(ds) != SWEEP_MAX_STEPS:
+        raise Iclr17Error(f"iclr17: {what}: {len(ds)} ladder steps ({SWEEP_MAX_STEPS})")
+    return ctypes.cast((ctypes.c_float * SWEEP_MAX_STEPS)(*ds), ctypes.c_void_p)
+
+
+def quantise_step_map(y: Tensor, indices, block: int, steps: Sequence[float]):
+    """y fp32 NHWC [B,h,w,N], ladder indices per block ([B, mh, mw], each 0..31; ``map_shape``)
+    and the 32 ladder step sizes → (ŷ = rint(y/Δ), Δ·ŷ) with Δ = steps[index of the element's
+    block]: ``quantise_step`` with a step per block, one pass, the same errors."""
+    _check(y, "latent", 4)
+    B, h, w, N = y.shape
+    idx = _map_on(y.device, indices, "quantise_step_map", "indices", B, h, w, block, 0,
+                  SWEEP_MAX_STEPS - 1, np.uint8)
+    arr = _ladder_arg(steps, "quantise_step_map")
+    y = y.contiguous()
+    y_hat, y_deq = torch.empty_like(y), torch.empty_like(y)
+    status = torch.zeros(1, device=y.device, dtype=torch.int32)
+    call("iclr17_quantise_step_map", _p(y), B, h, w, N, _p(idx), MAP_BLOCKS.index(block), arr,
+         _p(y_hat), _p(y_deq), _p(status), _stream(y))
+    _step_status(status, "quantise_step_map")
+    return y_hat, y_deq
+
+
+def dequantise_step_map(y_hat: Tensor, indices, block: int, steps: Sequence[float]) -> Tensor:
+    """Δ·ŷ with Δ per block: the decoder's half of ``quantise_step_map``."""
+    _check(y_hat, "latent", 4)
+    B, h, w, N = y_hat.shape
+    idx = _map_on(y_hat.device, indices, "dequantise_step_map", "indices", B, h, w, block, 0,
+                  SWEEP_MAX_STEPS - 1, np.uint8)
+    arr = _ladder_arg(steps, "dequantise_step_map")
+    y_hat = y_hat.contiguous()
+    out = torch.empty_like(y_hat)
+    call("iclr17_dequantise_step_map", _p(y_hat), B, h, w, N, _p(idx), MAP_BLOCKS.index(block), arr,
+         _p(out), _stream(y_hat))
+    return out
+
+
+def rate_sweep_offsets(y: Tensor, rate_packed: Tensor, steps: Sequence[float], offsets,
+                       block: int) -> Tensor:
+    """``rate_sweep`` at all 32 base indices with a signed ladder offset per block ([B, mh, mw],
+    −31..31) → float64 [B, 32]: row s sums every element at step clamp(s + offset, 0, 31). Zero
+    offsets give ``rate_sweep(y, rate_packed, steps)`` bit for bit."""
+    _check(y, "latent", 4)
+    _check(rate_packed, "rate table")
+    B, h, w, N = y.shape
+    if rate_packed.numel() != 11 * N:
+        raise Iclr17Error(f"iclr17: rate_sweep_offsets: packed rate parameters are not [11][{N}]")
+    off = _map_on(y.device, offsets, "rate_sweep_offsets", "offsets", B, h, w, block,
+                  1 - SWEEP_MAX_STEPS, SWEEP_MAX_STEPS - 1, np.int8)
+    arr = _ladder_arg(steps, "rate_sweep_offsets")
+    T = query("iclr17_rate_sweep_partials", h, w, N)
+    partial = torch.empty(B * SWEEP_MAX_STEPS * max(T, 1), device=y.device, dtype=torch.float64)
+    bits = torch.empty(B, SWEEP_MAX_STEPS, device=y.device, dtype=torch.float64)
+    call("iclr17_rate_sweep_offsets", _p(y.contiguous()), B, h, w, N, _p(rate_packed), arr, _p(off),
+         MAP_BLOCKS.index(block), _p(partial), _p(bits), _stream(y))
+    return bits
+
+
+# The mapped entropy coder's table source (DESIGN.md §0i): a window of channels staged in LDS, or
+# every row read from global memory. Both give the same words; the defaults are the measured ones
+# (profiles/stepmap_ab.txt). The encoder reads two table entries per symbol and is faster from
+# global memory at every number of table sets; the decoder's binary search (7 dependent reads) is
+# faster from the window until restaging, whose volume grows with the number of sets, outweighs it.
+RANS_MAP_DECODE_WINDOW_SETS = 16   # the decoder stages a window up to this many table sets
+
+
+def _stacked_tables(cum: Tensor, N: int, K: int, what: str) -> int:
+    if (not isinstance(cum, torch.Tensor) or cum.device.type != "cuda" or cum.dtype != torch.int32
+            or cum.dim() != 3 or cum.shape[1:] != (N, 2 * K + 3)
+            or not 1 <= cum.shape[0] <= SWEEP_MAX_STEPS):
+        raise Iclr17Error(f"iclr17: {what}: the stacked tables must be an int32 GPU tensor "
+                          f"[1..{SWEEP_MAX_STEPS}, {N}, {2 * K + 3}]")
+    return cum.shape[0]
+
+
+def rans_encode_map(y_hat: Tensor, cum: Tensor, slots, block: int, K: int = ENTROPY_K,
+                    streams_per_image: int = STREAMS_PER_IMAGE, window: Optional[bool] = None):
+    """``rans_encode`` with a table set per block: ``cum`` int32 [S, N, 2K + 3] (S ≤ 32 stacked
+    ``entropy_tables``), ``slots`` [B, mh, mw] with values < S; the symbol of channel c in a
+    block of slot t is coded with ``cum[t, c]``. → (words, offsets) as ``rans_encode``.
+    ``window``: stage the tables in an LDS window (None: no, the measured default)."""
+    _check(y_hat, "latent", 4)
+    B, h, w, N = y_hat.shape
+    P = streams_per_image
+    S = _stacked_tables(cum, N, K, "rans_encode_map")
+    sl = _map_on(y_hat.device, slots, "rans_encode_map", "slots", B, h, w, block, 0, S - 1, np.uint8)
+    cap = query("iclr17_rans_capacity", h, w, N, P)
+    if cap <= 0:
+        raise Iclr17Error(f"iclr17: rans_encode_map: N={N} not divisible into {P} streams")
+    dev = y_hat.device
+    scratch = torch.empty(B * P * cap, device=dev, dtype=torch.int16)
+    lengths = torch.empty(B * P, device=dev, dtype=torch.int32)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    st = _stream(y_hat)
+    call("iclr17_rans_encode_map", _p(y_hat.contiguous()), B, h, w, N, P, _p(cum.contiguous()), S, K,
+         _p(sl), MAP_BLOCKS.index(block), int(bool(window)),
+         _p(scratch), scratch.numel(), _p(lengths), _p(status), st)
+    offsets = torch.empty(B * P + 1, device=dev, dtype=torch.int64)
+    call("iclr17_rans_offsets", _p(lengths), B * P, _p(offsets), st)
+    total = int(offsets[-1].item())
+    words = torch.empty(max(total, 1), device=dev, dtype=torch.int16)
+    call("iclr17_rans_pack", _p(scratch), cap, _p(offsets), B * P, _p(words), st)
+    _rans_status(status, "rans_encode_map")
+    return words[:total], offsets
+
+
+def rans_decode_map(words: Tensor, offsets: Tensor, cum: Tensor, slots, block: int, B: int, h: int,
+                    w: int, N: int, K: int = ENTROPY_K, streams_per_image: int = STREAMS_PER_IMAGE,
+                    window: Optional[bool] = None) -> Tensor:
+    """Inverse of ``rans_encode_map`` → ŷ NHWC fp32 [B,h,w,N]. ``window``: stage the tables in an
+    LDS window (None: up to RANS_MAP_DECODE_WINDOW_SETS table sets, the measured default)."""
+    P = streams_per_image
+    S = _stacked_tables(cum, N, K, "rans_decode_map")
+    if offsets.numel() != B * P + 1 or N % P:
+        raise Iclr17Error("iclr17: rans_decode_map: offsets do not match B x streams_per_image")
+    dev = cum.device
+    sl = _map_on(dev, slots, "rans_decode_map", "slots", B, h, w, block, 0, S - 1, np.uint8)
+    y = torch.empty(B, h, w, N, device=dev, dtype=torch.float32)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    words = words.contiguous() if words.numel() else torch.zeros(1, device=dev, dtype=torch.int16)
+    call("iclr17_rans_decode_map", _p(words), _p(offsets.contiguous()), B, h, w, N, P,
+         _p(cum.contiguous()), S, K, _p(sl), MAP_BLOCKS.index(block),
+         int(S <= RANS_MAP_DECODE_WINDOW_SETS if window is None else bool(window)), _p(y),
+         _p(status), _stream(y))
+    _rans_status(status, "rans_decode_map")
+    return y
+
+
 # ------------------------------------------------------------ stepped training (csrc/steptrain.hip)
 def _step_args(t: Tensor, steps_dev: Tensor, rate_packed: Tensor, what: str):
     """An fp32 NHWC latent-shaped tensor, the [B] fp32 step sizes and the UNscaled pack, checked."""

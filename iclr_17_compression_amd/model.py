@@ -258,20 +258,60 @@ class ImageCompressor(nn.Module):
                                   [codec.step_size(s) for s in steps])
 
     @torch.no_grad()
-    def compress_latents(self, y: torch.Tensor, step: int,
+    def rate_sweep_offsets(self, y: torch.Tensor, offsets, block: int = 4) -> torch.Tensor:
+        """``rate_sweep`` of the NHWC latent ``y`` at all 32 BASE indices with a ladder offset per
+        block (``offsets``: integers [B, mh, mw], codec.map_shape): float64 [B, 32], row s summing
+        every element at index clamp(s + offset, 0, 31) (kernels.rate_sweep_offsets)."""
+        from . import codec
+        kernels._check(y, "latent", 4)
+        if y.shape[3] != self.out_channel_N:
+            raise kernels.Iclr17Error(f"iclr17: rate_sweep_offsets: the latent has {y.shape[3]} "
+                                      f"channels, the model {self.out_channel_N}")
+        return kernels.rate_sweep_offsets(y, self.bitEstimator.packed(),
+                                          [codec.step_size(s) for s in range(codec.STEPS)],
+                                          offsets, block)
+
+    def _map_tables(self, step_map, K):
+        """A step map's ladder indices [B, mh, mw] → (the stacked tables of the indices it uses,
+        ascending, and the map translated to their slots)."""
+        m = np.asarray(step_map)
+        if m.dtype.kind not in "iu" or m.ndim != 3 or not m.size or m.min() < 0 or m.max() > 31:
+            raise kernels.Iclr17Error("iclr17: step_map must be ladder indices 0..31 of shape "
+                                      f"[B, mh, mw] (got {m.dtype} {m.shape})")
+        used = [int(e) for e in np.unique(m)]
+        slot = np.zeros(32, dtype=np.uint8)
+        slot[used] = np.arange(len(used), dtype=np.uint8)
+        return self.bitEstimator.stacked_tables(K, used), slot[m]
+
+    @torch.no_grad()
+    def compress_latents(self, y: torch.Tensor, step: Optional[int],
                          streams_per_image: int = kernels.STREAMS_PER_IMAGE,
-                         K: int = kernels.ENTROPY_K) -> Dict[str, object]:
+                         K: int = kernels.ENTROPY_K, step_map=None,
+                         block: int = 4) -> Dict[str, object]:
         """``compress`` from the latent of ``latents`` at ladder step ``step``: ŷ = rint(y/Δ)
         (kernels.quantise_step), then rANS with the step's tables. Returns ``compress``'s dict and
-        "y_hat" (NHWC)."""
+        "y_hat" (NHWC). With ``step_map`` (ladder indices per block, integers [B, mh, mw] for
+        blocks of ``block``×``block`` latent positions; ``step`` is then None) every block is
+        quantised at its own step and coded with that step's tables (kernels.quantise_step_map,
+        kernels.rans_encode_map)."""
         from . import codec
-        y_hat, _ = kernels.quantise_step(y, codec.step_size(step))
-        return self._entropy_code(y_hat, self.bitEstimator.entropy_tables(K, step=step),
-                                  streams_per_image, K)
+        if step_map is None:
+            y_hat, _ = kernels.quantise_step(y, codec.step_size(step))
+            return self._entropy_code(y_hat, self.bitEstimator.entropy_tables(K, step=step),
+                                      streams_per_image, K)
+        if step is not None:
+            raise kernels.Iclr17Error("iclr17: compress_latents: step and step_map given together")
+        tables, slots = self._map_tables(step_map, K)
+        y_hat, _ = kernels.quantise_step_map(y, step_map, block,
+                                             [codec.step_size(s) for s in range(codec.STEPS)])
+        return self._entropy_code(y_hat, tables, streams_per_image, K, slots, block)
 
-    def _entropy_code(self, y_hat, tables, P, K):
+    def _entropy_code(self, y_hat, tables, P, K, slots=None, block=None):
         B, h, w, N = y_hat.shape
-        words, offsets = kernels.rans_encode(y_hat, tables, K, P)
+        if slots is None:
+            words, offsets = kernels.rans_encode(y_hat, tables, K, P)
+        else:
+            words, offsets = kernels.rans_encode_map(y_hat, tables, slots, block, K, P)
         off = offsets.cpu().numpy()
         wv = words.cpu().numpy().view("<u2")
         strings = []
@@ -303,12 +343,15 @@ class ImageCompressor(nn.Module):
 
     @torch.no_grad()
     def decompress(self, strings, shape, streams_per_image: int = kernels.STREAMS_PER_IMAGE,
-                   K: int = kernels.ENTROPY_K, device=None,
-                   step: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                   K: int = kernels.ENTROPY_K, device=None, step: Optional[int] = None,
+                   step_map=None, block: int = 4) -> Dict[str, torch.Tensor]:
         """Inverse of ``compress``: byte strings → {"y_hat": NCHW latents, "x_hat": the clipped
         reconstruction} (bit-identical latents; the synthesis as in ``forward``). With ``step``
         the inverse of ``compress_latents`` at that ladder step: the step's tables decode ŷ, and
-        the synthesis runs on Δ·ŷ as a general (non-integer) latent."""
+        the synthesis runs on Δ·ŷ as a general (non-integer) latent. With ``step_map`` /
+        ``block`` the inverse of ``compress_latents(step_map=…)``."""
+        if step is not None and step_map is not None:
+            raise kernels.Iclr17Error("iclr17: decompress: step and step_map given together")
         P, N = streams_per_image, self.out_channel_N
         h, w = shape
         device = device or next(self.parameters()).device
@@ -326,10 +369,21 @@ class ImageCompressor(nn.Module):
         off = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.int64)
         words = torch.from_numpy(np.concatenate(payload).view(np.int16).copy()).to(device)
         offsets = torch.from_numpy(off).to(device)
-        y_hat = kernels.rans_decode(words, offsets, self.bitEstimator.entropy_tables(K, step=step),
-                                    B, h, w, N, K, P)
+        if step_map is None:
+            y_hat = kernels.rans_decode(words, offsets,
+                                        self.bitEstimator.entropy_tables(K, step=step),
+                                        B, h, w, N, K, P)
+        else:
+            tables, slots = self._map_tables(step_map, K)
+            y_hat = kernels.rans_decode_map(words, offsets, tables, slots, block, B, h, w, N, K, P)
         m = chain.MODES[kernels.precision()]
-        if step is None:
+        if step_map is not None:
+            from . import codec
+            y_deq = kernels.dequantise_step_map(y_hat, step_map, block,
+                                                [codec.step_size(s) for s in range(codec.STEPS)])
+            clipped, _, _ = m.synthesis(self.Decoder, y_deq, m.latent_operand(y_deq), None, False,
+                                        False, None, False)
+        elif step is None:
             clipped, _, _ = m.synthesis(self.Decoder, y_hat, m.latent_operand(y_hat), None, False,
                                         True, None, False)
         else:
@@ -344,7 +398,8 @@ class ImageCompressor(nn.Module):
     def compress_images(self, images, max_batch: int = 64,
                         streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                         K: int = kernels.ENTROPY_K, step: Optional[int] = None,
-                        max_bytes=None, bpp=None, stats: Optional[dict] = None):
+                        max_bytes=None, bpp=None, stats: Optional[dict] = None,
+                        step_offsets=None, block: int = 4):
         """8-bit images of any sizes ≥ 1×1 (a sequence of uint8 HWC RGB arrays, numpy or torch) →
         one self-describing blob per image, in input order: codec.py's 28-byte header (true size,
         N, P, K, weights fingerprint) + the image's ``compress`` string. Images are batched by
@@ -359,18 +414,26 @@ class ImageCompressor(nn.Module):
         ``max_bytes`` a byte budget on the whole blob and ``bpp`` one of ⌊bpp·H·W/8⌋ bytes, each
         a scalar or one value per image; a budget picks per image the finest step that fits.
         These blobs carry the magic I17Q and their step; ``stats`` (a dict) receives
-        "reencodes", the budget loop's re-encodes per image."""
+        "reencodes", the budget loop's re-encodes per image.
+
+        ``step_offsets`` codes regions of interest (codec.py, "Step maps"): per image None or a
+        signed integer offset per block of ``block``×``block`` latent positions ([mh, mw],
+        codec.map_shape; codec.roi_offsets makes one from pixel boxes). A block is coded at
+        ladder index clamp(base + offset, 0, 31), the base being ``step``, what a budget picks,
+        or 8; these blobs carry the magic I17M and their map. No quality claim is made."""
         from . import codec
         return codec.compress_images(self, images, max_batch, streams_per_image, K, step=step,
-                                     max_bytes=max_bytes, bpp=bpp, stats=stats)
+                                     max_bytes=max_bytes, bpp=bpp, stats=stats,
+                                     step_offsets=step_offsets, block=block)
 
     @torch.no_grad()
     def decompress_images(self, blobs, max_batch: int = 64):
         """Inverse of ``compress_images``: blobs → uint8 HWC numpy arrays of the true sizes, in
         input order (``decompress`` per canvas batch, then kernels.image_egress: round-half-even of
-        the clipped reconstruction·255, cropped). Plain (I17C) and stepped (I17Q) blobs may be
-        mixed; a batch holds blobs of one canvas, P, K and step. Raises Iclr17Error on a foreign or truncated
-        blob, another N or other weights (the header's fingerprint). Within one precision mode
+        the clipped reconstruction·255, cropped). Plain (I17C), stepped (I17Q) and mapped (I17M)
+        blobs may be mixed; a batch holds blobs of one canvas, P, K and step (mapped ones: of one
+        block edge). Raises Iclr17Error on a foreign or truncated blob, a corrupt step map,
+        another N or other weights (the header's fingerprint). Within one precision mode
         the bytes are reproducible and independent of the batch; between modes a pixel may differ
         by one 8-bit step."""
         from . import codec
@@ -378,18 +441,21 @@ class ImageCompressor(nn.Module):
 
     @torch.no_grad()
     def evaluate_images(self, images, want_msssim: bool = False, max_batch: int = 64,
-                        step: Optional[int] = None, max_bytes=None, bpp=None):
+                        step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
+                        block: int = 4):
         """The real codec path per image, compress_images then decompress_images, measured on
         the 8-bit decoded image as codecs are reported: a dict per image with ``bytes``, ``bpp`` =
         8·len(blob)/(H·W) (header included, true pixel count), ``sse_u8`` (int), ``psnr_u8`` =
         10·log10(255²·3HW / sse_u8) (float64; inf at 0), ``recon`` (uint8 HWC) and, with
         ``want_msssim``, ``ms_ssim`` / ``ms_ssim_db`` of the cropped pair (None for an image too
         small for 5 levels) and ``step`` (the blob's ladder step; None for a plain blob).
-        ``step`` / ``max_bytes`` / ``bpp`` as in ``compress_images``. Precision as
-        ``decompress_images``."""
+        ``step`` / ``max_bytes`` / ``bpp`` / ``step_offsets`` / ``block`` as in
+        ``compress_images``; a mapped blob's row has its base index as ``step`` and also
+        ``step_map`` and ``block``. Precision as ``decompress_images``."""
         from . import codec
         return codec.evaluate_images(self, images, want_msssim, max_batch, step=step,
-                                     max_bytes=max_bytes, bpp=bpp)
+                                     max_bytes=max_bytes, bpp=bpp, step_offsets=step_offsets,
+                                     block=block)
 
     @torch.no_grad()
     def evaluate(self, x: torch.Tensor, want_y: bool = False,

@@ -81,6 +81,22 @@ class BitEstimator(nn.Module):
                               lambda: kernels.entropy_tables(self.packed(), self.channel, K),
                               )
 
+    def stacked_tables(self, K: int, steps):
+        """``entropy_tables(K, step=s)`` of the ladder steps ``steps`` (ascending, distinct)
+        stacked as int32 [S, C, 2K + 3] for the mapped entropy coder. The last stack is kept (one
+        per K, not one per set of steps: a stack is up to 32 table sets), so a run of calls with
+        the same steps stacks once."""
+        ps = self.params_in_order()
+        steps = tuple(int(s) for s in steps)
+
+        def build():
+            return steps, torch.stack([self.entropy_tables(K, step=s) for s in steps])
+
+        kept = self._pack.get(f"cdf{K}_map", ps, build)
+        if kept[0] != steps:
+            kept = self._pack.get(f"cdf{K}_map", ps, build, force=True)
+        return kept[1]
+
     def forward(self, x):
         # bitEstimator.py:38-42
         from ..autograd import BitEstimatorFn, needs_grad

@@ -300,6 +300,47 @@ int iclr17_rate_sweep_partials(int h, int w, int N);
 int iclr17_rate_sweep(const float* y, int B, int h, int w, int N, const float* rate_packed,
                       const float* steps, int S, double* partial, double* bits, void* stream);
 
+/* ------------------------------------------------------ per-block steps (csrc/stepmap.hip, rans.hip)
+ * A quantiser step per block of latent positions: region-of-interest coding. A
+ * block is g×g positions of the h×w latent, g = 2^log2_g with log2_g = 0..4; a map holds
+ * mh×mw = ⌈h/g⌉×⌈w/g⌉ entries per image, row-major, position (i, j) reading entry
+ * (i >> log2_g, j >> log2_g), and every channel of a position shares the entry. `steps` is a
+ * host array of the 32 ladder step sizes, copied at the call (each finite and > 0). */
+/* iclr17_quantise_step with the step of each element looked up: Δ = steps[indices[b][block]]
+ * (indices: device u8 [B][mh][mw], each < 32). y, y_hat, y_deq: fp32 NHWC [B][h][w][N]; status
+ * as there. */
+int iclr17_quantise_step_map(const float* y, int B, int h, int w, int N, const uint8_t* indices,
+                             int log2_g, const float* steps, float* y_hat, float* y_deq,
+                             int32_t* status, void* stream);
+/* y_deq = Δ · y_hat alone (the decoder's half of iclr17_quantise_step_map). */
+int iclr17_dequantise_step_map(const float* y_hat, int B, int h, int w, int N,
+                               const uint8_t* indices, int log2_g, const float* steps,
+                               float* y_deq, void* stream);
+/* iclr17_rate_sweep over all 32 bases with a signed offset per block (offsets: device i8
+ * [B][mh][mw]): bits[b][s] = Σ element_bits(rintf(y/Δ), step pack of Δ) with Δ =
+ * steps[clamp(s + offset, 0, 31)] per element. rate_sweep's chunks, thread map and order of
+ * addition: with zero offsets bits equals iclr17_rate_sweep(…, steps, 32, …) bit for bit, and with
+ * one offset c for a whole image its row s is that sweep's row clamp(s + c). partial: B · 32 ·
+ * iclr17_rate_sweep_partials(h, w, N) doubles of scratch; bits: [B][32] doubles. */
+int iclr17_rate_sweep_offsets(const float* y, int B, int h, int w, int N,
+                              const float* rate_packed, const float* steps, const int8_t* offsets,
+                              int log2_g, double* partial, double* bits, void* stream);
+/* iclr17_rans_encode / iclr17_rans_decode with a table row per symbol: the symbol of channel c
+ * at a position of block e is coded with row slots[b][e]·N + c of the stacked tables cum
+ * [S][N][2K + 3] (S ≤ 32 table sets; slots: device u8 [B][mh][mw], each < S). Streams, symbol
+ * order, words, capacity, offsets, pack and status bits are the plain entries'. window != 0: the
+ * rows of a window of consecutive channels (all S sets, up to 64 KiB) are staged in LDS and
+ * restaged as the stream walks past; rows outside it, and every row with window == 0, are read
+ * from global memory. Both give the same words. */
+int iclr17_rans_encode_map(const float* y_hat, int B, int h, int w, int N, int streams_per_image,
+                           const int32_t* cum, int S, int K, const uint8_t* slots, int log2_g,
+                           int window, uint16_t* scratch, long scratch_words, uint32_t* lengths,
+                           int32_t* status, void* stream);
+int iclr17_rans_decode_map(const uint16_t* words, const int64_t* offsets, int B, int h, int w,
+                           int N, int streams_per_image, const int32_t* cum, int S, int K,
+                           const uint8_t* slots, int log2_g, int window, float* y_hat,
+                           int32_t* status, void* stream);
+
 /* ------------------------------------------------------------ stepped training (csrc/steptrain.hip)
  * The quantiser / rate part of a training step whose images each have a ladder step of their own
  * (DESIGN.md §0h): the coder's convention above with the rounding replaced by noise. Per image b
