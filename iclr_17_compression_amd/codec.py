@@ -69,11 +69,23 @@ kinds are written byte for byte as before. ``decompress_images`` takes the three
 quality claim is made: the weights were trained at Δ = 1, and PSNR inside or outside a region is
 whatever the model gives.
 
+RDO. ``compress_images(..., rdo=λ)`` quantises rate–distortion optimised: at the
+step Δ each element of channel c sends, instead of r = rint(y/Δ) whatever it costs, the level among
+r, its neighbour toward zero and zero of least  bits + λ·g_c·Δ²·(level − y/Δ)²,  the bits being
+the rate model's own and g the ``rdo_weights`` (default ``ImageCompressor.synthesis_gains()``: the
+squared pixel response of the synthesis to a unit impulse in the channel, mean 1). It is an
+encoder-side choice: the blobs are ordinary I17Q ones, nothing of ``rdo`` is recorded and the
+decoder is unchanged. ``rdo`` goes with ``step``, ``max_bytes`` or ``bpp`` and alone means the unit
+step; a budget then estimates with the optimised levels' bits (``rate_sweep(..., rdo=)``). With
+``step_offsets`` it raises: per-block RDO is not built. The estimate is the rate model's; the
+coder's escape cost beyond ±K is not modelled. No quality claim is made.
+
     python -m iclr_17_compression_amd.codec encode IN.png OUT.i17c --weights CKPT [--N 192]
                                             [--step S | --max-bytes B | --bpp R]
-                                            [--roi X0,Y0,X1,Y1,OFF ...] [--block G]
+                                            [--roi X0,Y0,X1,Y1,OFF ...] [--block G] [--rdo L]
     python -m iclr_17_compression_amd.codec decode IN.i17c OUT.png --weights CKPT
     python -m iclr_17_compression_amd.codec eval IMG... --weights CKPT [--ms-ssim] [--steps 4,8,12]
+                                            [--rdo L]
 """
 from __future__ import annotations
 
@@ -413,17 +425,37 @@ def upload_packed(images: Sequence[np.ndarray], device):
     return host.to(device, non_blocking=True), [int(o) for o in offsets], [im.shape[:2] for im in images]
 
 
-def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None):
+RDO_WITH_MAP = ("iclr17: codec: rdo with step_offsets / a step map: per-block rate–distortion "
+                "optimised quantisation is not built")
+
+
+def rdo_value(rdo) -> float:
+    """``rdo`` (λ of rate–distortion optimised quantisation) checked on the host: a real number,
+    not a bool, finite (as an fp32 value too) and ≥ 0 → float."""
+    if isinstance(rdo, bool) or not isinstance(rdo, (int, float, np.integer, np.floating)):
+        raise Iclr17Error(f"iclr17: codec: rdo must be a real number (got {rdo!r})")
+    lam = float(rdo)
+    if not (math.isfinite(lam) and 0.0 <= lam <= float(np.finfo(np.float32).max)):
+        raise Iclr17Error(f"iclr17: codec: rdo must be finite and >= 0 (got {rdo!r})")
+    return lam
+
+
+def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None, rdo=None):
     """The rate options of ``compress_images`` for ``n`` images, checked on the host before any
     device use → None (the plain path), ("step", index) or ("budget", per-image values, is_bpp).
     At most one option; a budget is a scalar or one value per image. ``step_offsets`` goes with
-    any one of them, the option then giving the base index; alone it means the unit step."""
+    any one of them, the option then giving the base index; alone it means the unit step. So does
+    ``rdo`` (``rdo_value`` checks it); ``rdo`` with ``step_offsets`` raises."""
+    if rdo is not None:
+        rdo_value(rdo)
+        if step_offsets is not None:
+            raise Iclr17Error(RDO_WITH_MAP)
     given = [k for k, v in (("step", step), ("max_bytes", max_bytes), ("bpp", bpp)) if v is not None]
     if len(given) > 1:
         raise Iclr17Error(f"iclr17: codec: {' and '.join(given)} given together (at most one of "
                           "step, max_bytes, bpp)")
     if not given:
-        return None if step_offsets is None else ("step", UNIT_STEP)
+        return None if step_offsets is None and rdo is None else ("step", UNIT_STEP)
     if step is not None:
         step_size(step)
         return "step", int(step)
@@ -440,9 +472,10 @@ def compress_images(net, images, max_batch: int = 64,
                     streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                     K: int = kernels.ENTROPY_K, step: Optional[int] = None, max_bytes=None,
                     bpp=None, stats: Optional[dict] = None, step_offsets=None,
-                    block: int = DEFAULT_BLOCK) -> List[bytes]:
+                    block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None) -> List[bytes]:
     imgs = [as_u8_hwc(im) for im in images]
-    request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets)
+    request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets, rdo)
+    how = {} if rdo is None else {"rdo": rdo, "rdo_weights": rdo_weights}
     per_image = None
     if step_offsets is not None:
         per_image = checked_offsets([im.shape[:2] for im in imgs], step_offsets, block)
@@ -472,7 +505,7 @@ def compress_images(net, images, max_batch: int = 64,
         if request[0] == "step":
             chosen = [request[1]] * len(idx)
         else:
-            est = (net.rate_sweep(y, latent=True) if offs is None
+            est = (net.rate_sweep(y, latent=True, **how) if offs is None
                    else net.rate_sweep_offsets(y, offs, block)).cpu().numpy()
             chosen = []
             for k, i in enumerate(idx):
@@ -484,7 +517,7 @@ def compress_images(net, images, max_batch: int = 64,
         def encode(ks, s):
             sel = y if len(ks) == len(idx) else y[torch.tensor(ks, device=device)]
             if offs is None:
-                enc = net.compress_latents(sel, s, streams_per_image=P, K=K)
+                enc = net.compress_latents(sel, s, streams_per_image=P, K=K, **how)
                 return [pack_step_header(P, N, K, s, *shapes[k], fp) + string
                         for k, string in zip(ks, enc["strings"])]
             emap = effective_indices(s, offs[ks])
@@ -548,10 +581,10 @@ def decode_groups(net, blobs, max_batch: int, refs=None):
 
 def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
                     step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
-                    block: int = DEFAULT_BLOCK) -> List[dict]:
+                    block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None) -> List[dict]:
     imgs = [as_u8_hwc(im) for im in images]
     blobs = compress_images(net, imgs, max_batch=max_batch, step=step, max_bytes=max_bytes, bpp=bpp,
-                            step_offsets=step_offsets, block=block)
+                            step_offsets=step_offsets, block=block, rdo=rdo, rdo_weights=rdo_weights)
     recons, sses = decode_groups(net, blobs, max_batch, refs=imgs)
     device = next(net.parameters()).device
     res = []
@@ -624,6 +657,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                           "repeatable, the finest offset wins where boxes overlap")
     enc.add_argument("--block", type=int, default=DEFAULT_BLOCK, choices=kernels.MAP_BLOCKS,
                      help="block edge of the step map in latent positions (16 pixels each)")
+    enc.add_argument("--rdo", type=float, default=None, metavar="L",
+                     help="rate-distortion optimised quantisation with lambda L >= 0 (alone: at "
+                          "the unit step; not with --roi)")
     dec = sub.add_parser("decode", parents=[common], help="IN.i17c OUT.png")
     dec.add_argument("input")
     dec.add_argument("output")
@@ -632,6 +668,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ev.add_argument("--ms-ssim", action="store_true")
     ev.add_argument("--steps", default=None, help="ladder indices, e.g. 4,8,12: a row per image "
                                                   "and step, and a mean per step")
+    ev.add_argument("--rdo", type=float, default=None, metavar="L",
+                    help="rate-distortion optimised quantisation with lambda L >= 0")
     args = ap.parse_args(argv)
     net = _model(args)
     with kernels.precision_scope(args.precision or kernels.precision()):
@@ -641,7 +679,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 roi = {"step_offsets": [roi_offsets(*image.shape[:2], _boxes(args.roi), args.block)],
                        "block": args.block}
             blob = net.compress_images([image], step=args.step, max_bytes=args.max_bytes,
-                                       bpp=args.bpp, **roi)[0]
+                                       bpp=args.bpp, rdo=args.rdo, **roi)[0]
             with open(args.output, "wb") as f:
                 f.write(blob)
         elif args.cmd == "decode":
@@ -653,8 +691,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             imgs = [_load_image(p) for p in args.images]
             steps = [int(t) for t in args.steps.split(",")] if args.steps else [None]
             for step in steps:
-                rows = net.evaluate_images(imgs, want_msssim=args.ms_ssim, step=step)
+                rows = net.evaluate_images(imgs, want_msssim=args.ms_ssim, step=step,
+                                           rdo=args.rdo)
                 tag = {} if step is None else {"step": step}
+                if args.rdo is not None:
+                    tag["rdo"] = args.rdo
                 for p, im, r in zip(args.images, imgs, rows):
                     print(json.dumps({"name": p, **tag, "H": im.shape[0], "W": im.shape[1],
                                       "bytes": r["bytes"], "bpp": r["bpp"], "psnr_u8": r["psnr_u8"],

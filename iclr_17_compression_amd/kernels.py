@@ -1271,6 +1271,59 @@ def rate_sweep(y: Tensor, rate_packed: Tensor, steps: Sequence[float]) -> Tensor
     return bits
 
 
+# ------------------------------------- rate–distortion optimised quantisation (csrc/rdoq.hip)
+def _rdo_args(y: Tensor, rate_packed: Tensor, lam: Tensor, what: str):
+    _check(y, "latent", 4)
+    _check(rate_packed, "rate table")
+    B, h, w, N = y.shape
+    if rate_packed.numel() != 11 * N:
+        raise Iclr17Error(f"iclr17: {what}: packed rate parameters are not [11][{N}]")
+    if not isinstance(lam, torch.Tensor) or lam.dtype != torch.float32 or lam.device != y.device \
+            or tuple(lam.shape) != (N,):
+        raise Iclr17Error(f"iclr17: {what}: lam must be an fp32 tensor of shape [{N}] on the "
+                          "latent's device")
+    if not bool((torch.isfinite(lam) & (lam >= 0)).all()):
+        raise Iclr17Error(f"iclr17: {what}: lam must be finite and >= 0")
+    return B, h, w, N, lam.contiguous()
+
+
+def quantise_rdo(y: Tensor, rate_packed: Tensor, step: float, lam: Tensor):
+    """y fp32 NHWC [B,h,w,N], the UNscaled rate pack, a step Δ and lam (fp32 [N] on the device,
+    finite and ≥ 0) → (ŷ, Δ·ŷ, float64 [B] estimated bits of ŷ). Per element the level among
+    r = rint(y/Δ), r − sign(r) and 0 of least bits + lam[c]·Δ²·(level − y/Δ)² (DESIGN.md §0j);
+    the bits are what ``rate_bits(ŷ, pack_rate_step(…, Δ))`` sums to. Raises as
+    ``quantise_step``."""
+    B, h, w, N, lam = _rdo_args(y, rate_packed, lam, "quantise_rdo")
+    d = _step_value(step, "quantise_rdo")
+    y = y.contiguous()
+    y_hat, y_deq = torch.empty_like(y), torch.empty_like(y)
+    T = query("iclr17_rate_sweep_rdo_partials", h, w, N)
+    partial = torch.empty(B * max(T, 1), device=y.device, dtype=torch.float64)
+    bits = torch.empty(B, device=y.device, dtype=torch.float64)
+    status = torch.zeros(1, device=y.device, dtype=torch.int32)
+    call("iclr17_quantise_rdo", _p(y), B, h, w, N, _p(rate_packed), ctypes.c_float(d), _p(lam),
+         _p(y_hat), _p(y_deq), _p(partial), _p(bits), _p(status), _stream(y))
+    _step_status(status, "quantise_rdo")
+    return y_hat, y_deq, bits
+
+
+def rate_sweep_rdo(y: Tensor, rate_packed: Tensor, steps: Sequence[float], lam: Tensor) -> Tensor:
+    """``rate_sweep`` with ``quantise_rdo``'s choice inside → float64 [B, S]: column s is
+    ``quantise_rdo(y, rate_packed, steps[s], lam)``'s bits, every step from one read of y."""
+    B, h, w, N, lam = _rdo_args(y, rate_packed, lam, "rate_sweep_rdo")
+    ds = [_step_value(s, "rate_sweep_rdo") for s in steps]
+    S = len(ds)
+    if not 1 <= S <= SWEEP_MAX_STEPS:
+        raise Iclr17Error(f"iclr17: rate_sweep_rdo: {S} steps (1..{SWEEP_MAX_STEPS})")
+    T = query("iclr17_rate_sweep_rdo_partials", h, w, N)
+    partial = torch.empty(B * S * max(T, 1), device=y.device, dtype=torch.float64)
+    bits = torch.empty(B, S, device=y.device, dtype=torch.float64)
+    arr = (ctypes.c_float * S)(*ds)
+    call("iclr17_rate_sweep_rdo", _p(y.contiguous()), B, h, w, N, _p(rate_packed),
+         ctypes.cast(arr, ctypes.c_void_p), S, _p(lam), _p(partial), _p(bits), _stream(y))
+    return bits
+
+
 # ------------------------------------------------------- per-block steps (csrc/stepmap.hip, rans.hip)
 MAP_BLOCKS = (1, 2, 4, 8, 16)   # block edges g of a step map, in latent positions
 

@@ -25,6 +25,7 @@ import torch.nn as nn
 from . import chain, kernels
 from .models import *  # noqa: F401,F403
 from .models import Analysis_net_17, BitEstimator, Synthesis_net_17
+from .packcache import PackCache
 
 
 def save_model(model, iter, name):
@@ -240,13 +241,56 @@ class ImageCompressor(nn.Module):
         return y
 
     @torch.no_grad()
+    def synthesis_gains(self) -> torch.Tensor:
+        """The channel weights of rate–distortion optimised quantisation: fp32 [N]
+        on the device, g_c = Σ over pixels of (synthesis of a unit impulse in channel c at the
+        centre of an 8×8 zero latent − synthesis of the zero latent)², unclipped, normalised to
+        mean 1. One Decoder call on N + 1 latents (the response is 57 pixels wide and fits the
+        128×128 output), in the x6 mode whatever the current one; a linearisation of the synthesis
+        at zero and no more. Cached until a parameter changes."""
+        sd = self.state_dict()
+        keys = sorted(sd)
+        cache = self.__dict__.setdefault("_codec_cache", PackCache())
+
+        def build() -> torch.Tensor:
+            N = self.out_channel_N
+            dev = next(self.parameters()).device
+            probe = torch.zeros(N + 1, N, 8, 8, device=dev, dtype=torch.float32)
+            probe[torch.arange(N), torch.arange(N), 4, 4] = 1.0
+            with kernels.precision_scope("x6"):
+                out = self.Decoder(probe)
+            g = ((out[:N] - out[N:]) ** 2).sum(dim=(1, 2, 3))
+            return (g / g.mean()).contiguous()
+
+        return cache.get("synthesis_gains", [sd[k] for k in keys], build)
+
+    def _rdo_lam(self, rdo, rdo_weights, what: str) -> torch.Tensor:
+        """lam[c] = rdo · weight_c for kernels.quantise_rdo / rate_sweep_rdo: fp32 [N] on the
+        device; the weights default to ``synthesis_gains``."""
+        from . import codec
+        lam = codec.rdo_value(rdo)
+        N = self.out_channel_N
+        dev = next(self.parameters()).device
+        if rdo_weights is None:
+            g = self.synthesis_gains()
+        else:
+            g = torch.as_tensor(rdo_weights, dtype=torch.float32).to(dev)
+            if tuple(g.shape) != (N,):
+                raise kernels.Iclr17Error(f"iclr17: {what}: rdo_weights must have shape [{N}] "
+                                          f"(got {tuple(g.shape)})")
+        return (g * lam).contiguous()
+
+    @torch.no_grad()
     def rate_sweep(self, x_or_y: torch.Tensor, steps=range(32),
-                   latent: Optional[bool] = None) -> torch.Tensor:
+                   latent: Optional[bool] = None, rdo=None, rdo_weights=None) -> torch.Tensor:
         """Estimated bits of every image at every ladder step of ``steps`` (codec.step_size
         indices, at most 32): float64 [B, S] on the device, from one analysis pass and one read
         of y (kernels.rate_sweep). The argument is an image batch [B,3,H,W] or, with a second
-        dimension other than 3 or ``latent=True``, the NHWC latent of ``latents``."""
+        dimension other than 3 or ``latent=True``, the NHWC latent of ``latents``. With ``rdo``
+        (λ ≥ 0; ``rdo_weights``: [N] channel weights, default ``synthesis_gains``) the bits of the
+        rate–distortion optimised levels (kernels.rate_sweep_rdo)."""
         from . import codec
+        lam = None if rdo is None else self._rdo_lam(rdo, rdo_weights, "rate_sweep")
         kernels._check(x_or_y, "image or latent", 4)
         if latent is None:
             latent = x_or_y.shape[1] != 3
@@ -254,6 +298,9 @@ class ImageCompressor(nn.Module):
         if y.shape[3] != self.out_channel_N:
             raise kernels.Iclr17Error(f"iclr17: rate_sweep: the latent has {y.shape[3]} channels, "
                                       f"the model {self.out_channel_N}")
+        if lam is not None:
+            return kernels.rate_sweep_rdo(y, self.bitEstimator.packed(),
+                                          [codec.step_size(s) for s in steps], lam)
         return kernels.rate_sweep(y, self.bitEstimator.packed(),
                                   [codec.step_size(s) for s in steps])
 
@@ -287,14 +334,29 @@ class ImageCompressor(nn.Module):
     def compress_latents(self, y: torch.Tensor, step: Optional[int],
                          streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                          K: int = kernels.ENTROPY_K, step_map=None,
-                         block: int = 4) -> Dict[str, object]:
+                         block: int = 4, rdo=None, rdo_weights=None) -> Dict[str, object]:
         """``compress`` from the latent of ``latents`` at ladder step ``step``: ŷ = rint(y/Δ)
         (kernels.quantise_step), then rANS with the step's tables. Returns ``compress``'s dict and
         "y_hat" (NHWC). With ``step_map`` (ladder indices per block, integers [B, mh, mw] for
         blocks of ``block``×``block`` latent positions; ``step`` is then None) every block is
         quantised at its own step and coded with that step's tables (kernels.quantise_step_map,
-        kernels.rans_encode_map)."""
+        kernels.rans_encode_map).
+
+        With ``rdo`` (λ ≥ 0, finite; ``rdo_weights``: [N] channel weights, default
+        ``synthesis_gains``) the levels are rate–distortion optimised (kernels.quantise_rdo,
+        DESIGN.md §0j) and coded with the step's same tables; the dict gains "est_bits", the
+        model's estimate of ŷ per image (float64 [B] on the device). Not with ``step_map``."""
         from . import codec
+        if rdo is not None:
+            if step_map is not None:
+                raise kernels.Iclr17Error(codec.RDO_WITH_MAP)
+            lam = self._rdo_lam(rdo, rdo_weights, "compress_latents")
+            y_hat, _, est = kernels.quantise_rdo(y, self.bitEstimator.packed(),
+                                                 codec.step_size(step), lam)
+            enc = self._entropy_code(y_hat, self.bitEstimator.entropy_tables(K, step=step),
+                                     streams_per_image, K)
+            enc["est_bits"] = est
+            return enc
         if step_map is None:
             y_hat, _ = kernels.quantise_step(y, codec.step_size(step))
             return self._entropy_code(y_hat, self.bitEstimator.entropy_tables(K, step=step),
@@ -399,7 +461,7 @@ class ImageCompressor(nn.Module):
                         streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                         K: int = kernels.ENTROPY_K, step: Optional[int] = None,
                         max_bytes=None, bpp=None, stats: Optional[dict] = None,
-                        step_offsets=None, block: int = 4):
+                        step_offsets=None, block: int = 4, rdo=None, rdo_weights=None):
         """8-bit images of any sizes ≥ 1×1 (a sequence of uint8 HWC RGB arrays, numpy or torch) →
         one self-describing blob per image, in input order: codec.py's 28-byte header (true size,
         N, P, K, weights fingerprint) + the image's ``compress`` string. Images are batched by
@@ -420,11 +482,18 @@ class ImageCompressor(nn.Module):
         signed integer offset per block of ``block``×``block`` latent positions ([mh, mw],
         codec.map_shape; codec.roi_offsets makes one from pixel boxes). A block is coded at
         ladder index clamp(base + offset, 0, 31), the base being ``step``, what a budget picks,
-        or 8; these blobs carry the magic I17M and their map. No quality claim is made."""
+        or 8; these blobs carry the magic I17M and their map. No quality claim is made.
+
+        ``rdo`` (λ ≥ 0, finite) quantises rate–distortion optimised (codec.py, "RDO"): each
+        level is the cheapest of rint(y/Δ), its neighbour toward zero and zero under
+        bits + λ·g_c·Δ²·error², with ``rdo_weights`` [N] as g (default ``synthesis_gains``). It goes
+        with ``step`` or a budget and alone means the unit step; the blobs are ordinary I17Q ones
+        and record nothing of it. With ``step_offsets`` it raises (per-block RDO is not built)."""
         from . import codec
         return codec.compress_images(self, images, max_batch, streams_per_image, K, step=step,
                                      max_bytes=max_bytes, bpp=bpp, stats=stats,
-                                     step_offsets=step_offsets, block=block)
+                                     step_offsets=step_offsets, block=block, rdo=rdo,
+                                     rdo_weights=rdo_weights)
 
     @torch.no_grad()
     def decompress_images(self, blobs, max_batch: int = 64):
@@ -442,20 +511,20 @@ class ImageCompressor(nn.Module):
     @torch.no_grad()
     def evaluate_images(self, images, want_msssim: bool = False, max_batch: int = 64,
                         step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
-                        block: int = 4):
+                        block: int = 4, rdo=None, rdo_weights=None):
         """The real codec path per image, compress_images then decompress_images, measured on
         the 8-bit decoded image as codecs are reported: a dict per image with ``bytes``, ``bpp`` =
         8·len(blob)/(H·W) (header included, true pixel count), ``sse_u8`` (int), ``psnr_u8`` =
         10·log10(255²·3HW / sse_u8) (float64; inf at 0), ``recon`` (uint8 HWC) and, with
         ``want_msssim``, ``ms_ssim`` / ``ms_ssim_db`` of the cropped pair (None for an image too
         small for 5 levels) and ``step`` (the blob's ladder step; None for a plain blob).
-        ``step`` / ``max_bytes`` / ``bpp`` / ``step_offsets`` / ``block`` as in
-        ``compress_images``; a mapped blob's row has its base index as ``step`` and also
-        ``step_map`` and ``block``. Precision as ``decompress_images``."""
+        ``step`` / ``max_bytes`` / ``bpp`` / ``step_offsets`` / ``block`` / ``rdo`` /
+        ``rdo_weights`` as in ``compress_images``; a mapped blob's row has its base index as
+        ``step`` and also ``step_map`` and ``block``. Precision as ``decompress_images``."""
         from . import codec
         return codec.evaluate_images(self, images, want_msssim, max_batch, step=step,
                                      max_bytes=max_bytes, bpp=bpp, step_offsets=step_offsets,
-                                     block=block)
+                                     block=block, rdo=rdo, rdo_weights=rdo_weights)
 
     @torch.no_grad()
     def evaluate(self, x: torch.Tensor, want_y: bool = False,

@@ -300,6 +300,32 @@ int iclr17_rate_sweep_partials(int h, int w, int N);
 int iclr17_rate_sweep(const float* y, int B, int h, int w, int N, const float* rate_packed,
                       const float* steps, int S, double* partial, double* bits, void* stream);
 
+/* ----------------------------------------- rate–distortion optimised quantisation (csrc/rdoq.hip)
+ * An encoder-side choice of the level; the stream and the decoder are unchanged.
+ * Per element of channel c at step Δ: t = y/Δ (IEEE fp32 divide), r = rintf(t), candidates r,
+ * r − sign(r) (r ≠ 0) and 0 (|r| ≥ 2) in that order, cost J(v) = bits(v) + w·(v − t)² in fp32 with
+ * w = lam[c]·Δ·Δ (left to right) and bits the model's on the step pack of Δ (−log2(F(v + ½) −
+ * F(v − ½) + 1e-10) clamped to [0, 50]); the pick is the first candidate of least J (a strict <
+ * moves it on). lam: device fp32 [N], each finite and ≥ 0 (the caller checks). The estimate is
+ * the rate model's, as iclr17_rate_sweep's: the coder's escape cost beyond ±K is not modelled. */
+/* y (fp32 NHWC [B][h][w][N]) → y_hat (the picks, integer-valued fp32), y_deq = step · y_hat and
+ * bits[b] = Σ bits(y_hat) over image b: term for term what iclr17_rate_bits(y_hat,
+ * iclr17_pack_rate_step(rate_packed, step)) and iclr17_reduce_partials give. rate_packed is the
+ * UNscaled pack. partial: B · iclr17_rate_sweep_rdo_partials(h, w, N) doubles of scratch; bits:
+ * [B] doubles. status as iclr17_quantise_step's, on r (such an element is written as r). Fixed
+ * order, no atomics in a sum: bitwise reproducible, and independent of the batch. */
+int iclr17_rate_sweep_rdo_partials(int h, int w, int N);
+int iclr17_quantise_rdo(const float* y, int B, int h, int w, int N, const float* rate_packed,
+                        float step, const float* lam, float* y_hat, float* y_deq, double* partial,
+                        double* bits, int32_t* status, void* stream);
+/* iclr17_rate_sweep with the choice above inside: bits[b][s] is iclr17_quantise_rdo's bits[b] at
+ * steps[s], S ≤ 32 steps from one read of y. steps is a host array, copied at the call. partial:
+ * B · S · iclr17_rate_sweep_rdo_partials(h, w, N) doubles of scratch; bits: [B][S] doubles.
+ * ICLR17_EUNSUPPORTED when (12 + S)·N + 4096 floats do not fit the LDS of a workgroup. */
+int iclr17_rate_sweep_rdo(const float* y, int B, int h, int w, int N, const float* rate_packed,
+                          const float* steps, int S, const float* lam, double* partial,
+                          double* bits, void* stream);
+
 /* ------------------------------------------------------ per-block steps (csrc/stepmap.hip, rans.hip)
  * A quantiser step per block of latent positions: region-of-interest coding. A
  * block is g×g positions of the h×w latent, g = 2^log2_g with log2_g = 0..4; a map holds
