@@ -109,6 +109,12 @@ SIGNATURES = {
     "iclr17_rans_encode_map": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P,
                                     ctypes.c_long, _P, _P, _P]),
     "iclr17_rans_decode_map": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "iclr17_rans_tiled_capacity": (ctypes.c_long, [_I, _I, _I]),
+    "iclr17_rans_tiled_streams": (_I, [_I, _I, _I, _I]),
+    "iclr17_rans_encode_tiled": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, ctypes.c_long,
+                                      _P, _P, _P]),
+    "iclr17_rans_decode_tiled": (_I, [_P, ctypes.c_long, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I,
+                                      _I, _P, _I, _I, _P, ctypes.c_long, _P, _P]),
     "iclr17_step_noise_rate": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "iclr17_step_rate_bwd_partials": (_I, [_I, _I]),
     "iclr17_step_noise_rate_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

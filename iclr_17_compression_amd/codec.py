@@ -80,10 +80,40 @@ step; a budget then estimates with the optimised levels' bits (``rate_sweep(...,
 ``step_offsets`` it raises: per-block RDO is not built. The estimate is the rate model's; the
 coder's escape cost beyond ±K is not modelled. No quality claim is made.
 
+Tiled streams. ``compress_images(..., tile=t)`` (t in 8, 16, 32, 64 latent positions: 128 to 1024
+pixels square) codes the same latents with independent streams per spatial tile.
+The h×w latent of the canvas is cut into th×tw = ⌈h/t⌉×⌈w/t⌉ tiles (``tile_shape``), ragged at the
+bottom and right; there is one stream per (tile row, tile column, channel group), in that order,
+with the tile's symbols in (channel, row, column) order: the words of a tile are the words the
+plain coder gives that tile as a latent of its own. Only the layout changes: the quantiser, the
+tables and the levels are those of the untiled call with the same ``step``, budget or ``rdo``, and
+the decoded latents and pixels are the same. A budget counts the real overhead, 28 + th·tw·P·260
+bytes (``tiled_blob_overhead``). ``tile`` with ``step_offsets`` raises: tiled step maps are not
+built. The blob:
+
+    struct "<4sBBHHBBIIQ":  magic b"I17T" | version u8 = 1 | P | N | K | step u8 | log2 t u8 |
+                            H | W | fingerprint
+    then th·tw·P little-endian uint32 word counts (tile row, tile column, group), then the words.
+
+It always carries a ladder index: a call with ``tile`` and no rate option writes index 8 and codes
+``compress``'s own ŷ. ``decompress_images`` takes the four kinds mixed.
+
+Region decode. ``decompress_region(blob, box)`` returns the pixels of ``box`` = (x0, y0, x1, y1)
+(half-open, inside the image), byte for byte the crop of the full decode, from the tiles it needs
+alone. The synthesis is deconv 5×5/s2/p2, IGDN, deconv 5×5/s2/p2, IGDN, deconv 9×9/s4/p4; IGDN is
+pointwise in space, output o of a 5×5/s2/p2 deconv reads inputs ⌈(o − 2)/2⌉ … ⌊(o + 2)/2⌋ and output
+o of the 9×9/s4/p4 one ⌈(o − 4)/4⌉ … ⌊(o + 4)/4⌋. ``region_window`` maps the box's first and last
+pixel through the three layers (at most one latent position up and left of the box's own and two
+down and right), clamps to the latent, and takes the tiles that cover that rectangle; those
+streams are decoded into a compact latent, which is dequantised and synthesised as an image of
+its own, and ``image_egress`` runs on the crop.
+
     python -m iclr_17_compression_amd.codec encode IN.png OUT.i17c --weights CKPT [--N 192]
                                             [--step S | --max-bytes B | --bpp R]
                                             [--roi X0,Y0,X1,Y1,OFF ...] [--block G] [--rdo L]
+                                            [--tile T]
     python -m iclr_17_compression_amd.codec decode IN.i17c OUT.png --weights CKPT
+                                            [--region X0,Y0,X1,Y1]
     python -m iclr_17_compression_amd.codec eval IMG... --weights CKPT [--ms-ssim] [--steps 4,8,12]
                                             [--rdo L]
 """
@@ -124,6 +154,18 @@ DEFAULT_BLOCK = 4                        # block edge in latent positions: 64×6
 # what parse_blob gives for a mapped blob in place of a ladder index: the base index, the block
 # edge g, the effective indices (uint8 [mh, mw]) and the byte at which the payload starts
 StepMap = namedtuple("StepMap", "base block indices payload")
+
+TILE_MAGIC = b"I17T"
+TILE_HEADER = struct.Struct("<4sBBHHBBIIQ")
+assert TILE_HEADER.size == HEADER.size   # the count table starts where the other kinds' payload does
+
+# what parse_blob gives for a tiled blob in place of a ladder index: the ladder index, the tile
+# edge t, the streams' word counts (int64 [th, tw, P]) and the byte at which the words start
+TileInfo = namedtuple("TileInfo", "step tile counts words")
+
+# region_window's answer: the latent rectangle (i0, j0, i1, j1) and the tile rectangle (r0, c0, r1,
+# c1), both half-open, and the box's (x, y) inside the reconstruction of the tile rectangle
+RegionWindow = namedtuple("RegionWindow", "latent tiles offset")
 
 # ------------------------------------------------------------------------------ ladder
 STEPS = 32
@@ -188,6 +230,20 @@ def blob_overhead(P: int) -> int:
     """Bytes of a blob that are not renormalisation words: the header, the P stream word counts
     and each stream's 64 final rANS states."""
     return HEADER.size + 4 * P + 256 * P
+
+
+def tile_shape(H: int, W: int, tile: int) -> Tuple[int, int]:
+    """(th, tw) of an H×W image coded with tiles of ``tile``×``tile`` latent positions (8, 16, 32 or
+    64): its canvas's latent is h×w = canvas/16, and th×tw = ⌈h/tile⌉×⌈w/tile⌉."""
+    Hc, Wc = canvas(H, W)
+    return kernels.tile_grid(Hc // 16, Wc // 16, tile)
+
+
+def tiled_blob_overhead(P: int, H: int, W: int, tile: int) -> int:
+    """``blob_overhead`` of a tiled blob of an H×W image: the header, and per stream — th·tw·P of
+    them — its word count and its 64 final rANS states."""
+    th, tw = tile_shape(H, W, tile)
+    return TILE_HEADER.size + th * tw * P * (4 + 256)
 
 
 # ------------------------------------------------------------------------------ canvas
@@ -329,14 +385,98 @@ def parse_map_header(blob: bytes, N: Optional[int] = None,
     return head, StepMap(base, 1 << lg, indices, end)
 
 
+def pack_tile_header(P: int, N: int, K: int, step: int, tile: int, H: int, W: int,
+                     fingerprint: int) -> bytes:
+    """The header of a tiled blob: ``pack_header``'s fields under the magic I17T with the ladder
+    index and log2 of the tile edge in the two pad bytes."""
+    step_size(step)
+    pack_header(P, N, K, H, W, fingerprint)   # the shared fields' range checks
+    tile_shape(H, W, tile)                    # the tile edge's
+    return TILE_HEADER.pack(TILE_MAGIC, VERSION, P, N, K, int(step), kernels.TILES.index(tile) + 3,
+                            H, W, fingerprint & (2 ** 64 - 1))
+
+
+def parse_tile_header(blob: bytes, N: Optional[int] = None,
+                      fingerprint: Optional[int] = None) -> Tuple[Header, TileInfo]:
+    """The header and count table of a tiled (I17T) blob → (Header, TileInfo), checked as
+    ``parse_header`` checks a plain one; a step outside the ladder, a tile edge this build does
+    not read, a truncated count table, counts that do not sum to the words that follow and an odd
+    rest raise. All of it on the host: nothing of a bad blob reaches the device."""
+    if len(blob) < TILE_HEADER.size:
+        raise Iclr17Error(f"iclr17: codec: truncated header ({len(blob)} of {TILE_HEADER.size} bytes)")
+    magic, version, P, n, K, step, lg, H, W, fp = TILE_HEADER.unpack_from(blob)
+    head = _checked_header(TILE_MAGIC, magic, version, P, n, K, H, W, fp, N, fingerprint)
+    if step >= STEPS:
+        raise Iclr17Error(f"iclr17: codec: quantiser step {step} in the stream (this build reads "
+                          f"0..{STEPS - 1})")
+    if not 3 <= lg <= 6:
+        raise Iclr17Error(f"iclr17: codec: tiles of 2^{lg} latent positions in the stream (this "
+                          "build reads 2^3..2^6)")
+    if P < 1:
+        raise Iclr17Error("iclr17: codec: a tiled stream with no channel groups")
+    th, tw = tile_shape(H, W, 1 << lg)
+    end = TILE_HEADER.size + 4 * th * tw * P
+    if len(blob) < end:
+        raise Iclr17Error(f"iclr17: codec: truncated tile count table ({len(blob) - TILE_HEADER.size} "
+                          f"of {4 * th * tw * P} bytes)")
+    if (len(blob) - end) % 2:
+        raise Iclr17Error(f"iclr17: codec: truncated stream ({len(blob)} bytes)")
+    counts = np.frombuffer(bytes(blob[TILE_HEADER.size:end]), dtype="<u4").astype(np.int64)
+    if int(counts.sum()) != (len(blob) - end) // 2:
+        raise Iclr17Error(f"iclr17: codec: the tile counts sum to {int(counts.sum())} words, the "
+                          f"stream holds {(len(blob) - end) // 2}")
+    return head, TileInfo(step, 1 << lg, counts.reshape(th, tw, P), end)
+
+
 def parse_blob(blob: bytes, N: Optional[int] = None, fingerprint: Optional[int] = None):
     """The header of any kind of blob → (Header, ladder index | None for a plain blob | StepMap
-    for a mapped one)."""
+    for a mapped one | TileInfo for a tiled one)."""
     if bytes(blob[:4]) == STEP_MAGIC:
         return parse_step_header(blob, N, fingerprint)
     if bytes(blob[:4]) == MAP_MAGIC:
         return parse_map_header(blob, N, fingerprint)
+    if bytes(blob[:4]) == TILE_MAGIC:
+        return parse_tile_header(blob, N, fingerprint)
     return parse_header(blob, N, fingerprint), None
+
+
+# ------------------------------------------------------------------------------ regions
+def _checked_box(H: int, W: int, box) -> Tuple[int, int, int, int]:
+    try:
+        x0, y0, x1, y1 = box
+        ok = all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) for v in box)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
+        raise Iclr17Error(f"iclr17: codec: a region is (x0, y0, x1, y1) in pixels, half-open, not "
+                          f"empty and inside the {H}x{W} image (got {box!r})")
+    return int(x0), int(y0), int(x1), int(y1)
+
+
+def _latent_span(lo: int, hi: int, n: int) -> Tuple[int, int]:
+    """The latent positions, first and last, that the synthesis reads for the output pixels
+    lo..hi of one axis with n latent positions: back through deconv 9×9/s4/p4 and two deconvs
+    5×5/s2/p2 (the module docstring has the rule), each layer's range clamped to its grid."""
+    for k, p, size in ((4, 4, 4 * n), (2, 2, 2 * n), (2, 2, n)):
+        lo = max(-((p - lo) // k), 0)          # ⌈(lo − p)/k⌉
+        hi = min((hi + p) // k, size - 1)      # ⌊(hi + p)/k⌋
+    return lo, hi
+
+
+def region_window(H: int, W: int, tile: int, box) -> RegionWindow:
+    """What a decoder needs for the pixels ``box`` = (x0, y0, x1, y1) (half-open, inside the H×W
+    image) of an image coded with tiles of ``tile`` latent positions → RegionWindow: the rectangle
+    of the latent those pixels depend on and no more (from the layer geometry, module docstring),
+    the rectangle of tiles that covers it, both half-open, and where the box lies in the
+    reconstruction of that tile rectangle, in pixels (x, y). A pure host function."""
+    x0, y0, x1, y1 = _checked_box(H, W, box)
+    Hc, Wc = canvas(H, W)
+    kernels.tile_grid(Hc // 16, Wc // 16, tile)
+    i0, i1 = _latent_span(y0, y1 - 1, Hc // 16)
+    j0, j1 = _latent_span(x0, x1 - 1, Wc // 16)
+    r0, c0, r1, c1 = i0 // tile, j0 // tile, i1 // tile + 1, j1 // tile + 1
+    return RegionWindow((i0, j0, i1 + 1, j1 + 1), (r0, c0, r1, c1),
+                        (x0 - 16 * tile * c0, y0 - 16 * tile * r0))
 
 
 # ------------------------------------------------------------------------------ step maps
@@ -425,6 +565,8 @@ def upload_packed(images: Sequence[np.ndarray], device):
     return host.to(device, non_blocking=True), [int(o) for o in offsets], [im.shape[:2] for im in images]
 
 
+TILE_WITH_MAP = ("iclr17: codec: tile with step_offsets / a step map: tiled step maps are not "
+                 "built")
 RDO_WITH_MAP = ("iclr17: codec: rdo with step_offsets / a step map: per-block rate–distortion "
                 "optimised quantisation is not built")
 
@@ -440,12 +582,22 @@ def rdo_value(rdo) -> float:
     return lam
 
 
-def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None, rdo=None):
+def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None, rdo=None,
+                 tile=None):
     """The rate options of ``compress_images`` for ``n`` images, checked on the host before any
     device use → None (the plain path), ("step", index) or ("budget", per-image values, is_bpp).
     At most one option; a budget is a scalar or one value per image. ``step_offsets`` goes with
     any one of them, the option then giving the base index; alone it means the unit step. So does
-    ``rdo`` (``rdo_value`` checks it); ``rdo`` with ``step_offsets`` raises."""
+    ``rdo`` (``rdo_value`` checks it); ``rdo`` with ``step_offsets`` raises. ``tile`` (the tile
+    edge of tiled streams: 8, 16, 32 or 64) changes the layout and not the rate: it goes with every
+    option but ``step_offsets``, with which it raises, and does not change the answer."""
+    if tile is not None:
+        if (isinstance(tile, bool) or not isinstance(tile, (int, np.integer))
+                or tile not in kernels.TILES):
+            raise Iclr17Error(f"iclr17: codec: tile must be one of {kernels.TILES} latent positions "
+                              f"(got {tile!r})")
+        if step_offsets is not None:
+            raise Iclr17Error(TILE_WITH_MAP)
     if rdo is not None:
         rdo_value(rdo)
         if step_offsets is not None:
@@ -472,9 +624,10 @@ def compress_images(net, images, max_batch: int = 64,
                     streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                     K: int = kernels.ENTROPY_K, step: Optional[int] = None, max_bytes=None,
                     bpp=None, stats: Optional[dict] = None, step_offsets=None,
-                    block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None) -> List[bytes]:
+                    block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None,
+                    tile: Optional[int] = None) -> List[bytes]:
     imgs = [as_u8_hwc(im) for im in images]
-    request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets, rdo)
+    request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets, rdo, tile)
     how = {} if rdo is None else {"rdo": rdo, "rdo_weights": rdo_weights}
     per_image = None
     if step_offsets is not None:
@@ -491,6 +644,11 @@ def compress_images(net, images, max_batch: int = 64,
         group = [imgs[i] for i in idx]
         packed, offsets, shapes = upload_packed(group, device)
         x = kernels.image_ingest(packed, offsets, shapes, canvas(*shapes[0]))
+        if request is None and tile is not None:   # compress's own ŷ, tiled, at the unit index
+            enc = net.compress(x, streams_per_image=P, K=K, tile=tile)
+            for i, (H, W), s in zip(idx, shapes, enc["strings"]):
+                blobs[i] = pack_tile_header(P, N, K, UNIT_STEP, tile, H, W, fp) + s
+            continue
         if request is None:
             enc = net.compress(x, streams_per_image=P, K=K)
             for i, (H, W), s in zip(idx, shapes, enc["strings"]):
@@ -502,6 +660,8 @@ def compress_images(net, images, max_batch: int = 64,
         # blob also carries its map
         offs = None if per_image is None else np.stack([per_image[i] for i in idx])
         overhead = blob_overhead(P) + (0 if offs is None else offs[0].size)
+        if tile is not None:
+            overhead = tiled_blob_overhead(P, *shapes[0], tile)   # one canvas: one tile grid
         if request[0] == "step":
             chosen = [request[1]] * len(idx)
         else:
@@ -516,6 +676,10 @@ def compress_images(net, images, max_batch: int = 64,
 
         def encode(ks, s):
             sel = y if len(ks) == len(idx) else y[torch.tensor(ks, device=device)]
+            if tile is not None:
+                enc = net.compress_latents(sel, s, streams_per_image=P, K=K, tile=tile, **how)
+                return [pack_tile_header(P, N, K, s, tile, *shapes[k], fp) + string
+                        for k, string in zip(ks, enc["strings"])]
             if offs is None:
                 enc = net.compress_latents(sel, s, streams_per_image=P, K=K, **how)
                 return [pack_step_header(P, N, K, s, *shapes[k], fp) + string
@@ -550,15 +714,21 @@ def decode_groups(net, blobs, max_batch: int, refs=None):
             raise Iclr17Error(f"iclr17: codec: truncated stream ({len(b)} bytes)")
     out: List[Optional[np.ndarray]] = [None] * len(blobs)
     sses: Optional[List[Optional[int]]] = [None] * len(blobs) if refs is not None else None
-    # a batch: one canvas, P, K and step; mapped blobs of one block edge batch whatever their maps
-    keys = [canvas(h.H, h.W) + (h.P, h.K, ("map", s.block) if isinstance(s, StepMap) else s)
-            for h, s in parsed]
+    # a batch: one canvas, P, K and step; mapped blobs of one block edge batch whatever their
+    # maps, tiled blobs of one step and tile edge together
+    def kind(s):
+        if isinstance(s, StepMap):
+            return "map", s.block
+        return ("tile", s.step, s.tile) if isinstance(s, TileInfo) else s
+    keys = [canvas(h.H, h.W) + (h.P, h.K, kind(s)) for h, s in parsed]
     for idx in _group(keys, max_batch):
         h0, s0 = heads[idx[0]], steps[idx[0]]
         Hc, Wc = canvas(h0.H, h0.W)
         how = {"step": s0}
         if isinstance(s0, StepMap):
             how = {"step_map": np.stack([steps[i].indices for i in idx]), "block": s0.block}
+        if isinstance(s0, TileInfo):
+            how = {"step": s0.step, "tile": s0.tile}
         dec = net.decompress([blobs[i][starts[i]:] for i in idx], (Hc // 16, Wc // 16),
                              streams_per_image=h0.P, K=h0.K, device=device, **how)
         shapes = [(heads[i].H, heads[i].W) for i in idx]
@@ -579,12 +749,62 @@ def decode_groups(net, blobs, max_batch: int, refs=None):
     return out, sses
 
 
+def decode_region(net, blob, box, stats: Optional[dict] = None) -> np.ndarray:
+    """``ImageCompressor.decompress_region``: the pixels ``box`` of one blob → uint8 [y1 − y0,
+    x1 − x0, 3]. A tiled blob: the streams of ``region_window``'s tile rectangle are decoded into
+    a compact latent (kernels.rans_decode_tiled), dequantised with the blob's step and synthesised
+    as an image of its own; ``image_egress`` runs on the crop (from the 16-pixel grid line above
+    and left of it: the egress takes canvases of multiples of 16). Any other blob is decoded
+    whole and cropped."""
+    from . import chain
+    device = next(net.parameters()).device
+    head, info = parse_blob(blob, net.out_channel_N, fingerprint(net))
+    x0, y0, x1, y1 = _checked_box(head.H, head.W, box)
+    if not isinstance(info, TileInfo):
+        full = decode_groups(net, [blob], 1)[0][0]
+        if stats is not None:
+            stats["streams_decoded"] = stats["streams_total"] = head.P
+        return np.ascontiguousarray(full[y0:y1, x0:x1])
+    P, N, K, t = head.P, head.N, head.K, info.tile
+    win = region_window(head.H, head.W, t, (x0, y0, x1, y1))
+    r0, c0, r1, c1 = win.tiles
+    Hc, Wc = canvas(head.H, head.W)
+    # the rectangle's streams, in stream order, out of the blob's words
+    flat = info.counts.reshape(-1)
+    first = np.concatenate([[0], np.cumsum(flat)])
+    th, tw = info.counts.shape[:2]
+    picked = [(r * tw + c) * P + g for r in range(r0, r1) for c in range(c0, c1) for g in range(P)]
+    words = np.frombuffer(bytes(blob[info.words:]), dtype="<u2")
+    parts = [words[first[k]:first[k + 1]] for k in picked]
+    off = np.concatenate([[0], np.cumsum([len(q) for q in parts])]).astype(np.int64)
+    packed = np.concatenate(parts).view(np.int16).copy()
+    y_hat = kernels.rans_decode_tiled(torch.from_numpy(packed).to(device),
+                                      torch.from_numpy(off).to(device),
+                                      net.bitEstimator.entropy_tables(K, step=info.step), 1,
+                                      Hc // 16, Wc // 16, N, t, K, P, rect=win.tiles)
+    if stats is not None:
+        stats["streams_decoded"], stats["streams_total"] = len(picked), int(flat.size)
+    y_deq = kernels.dequantise_step(y_hat, step_size(info.step))
+    m = chain.MODES[kernels.precision()]
+    clipped, _, _ = m.synthesis(net.Decoder, y_deq, m.latent_operand(y_deq), None, False, False,
+                                None, False)
+    dx, dy = win.offset
+    X0, Y0 = dx // 16 * 16, dy // 16 * 16
+    X1, Y1 = -(-(dx + x1 - x0) // 16) * 16, -(-(dy + y1 - y0) // 16) * 16
+    shape = (dy - Y0 + y1 - y0, dx - X0 + x1 - x0)
+    dst, _ = kernels.image_egress(clipped[:, :, Y0:Y1, X0:X1].contiguous(), [0], [shape])
+    out = dst.numpy()[:3 * shape[0] * shape[1]].reshape(shape[0], shape[1], 3)
+    return np.ascontiguousarray(out[dy - Y0:, dx - X0:])
+
+
 def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
                     step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
-                    block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None) -> List[dict]:
+                    block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None,
+                    tile: Optional[int] = None) -> List[dict]:
     imgs = [as_u8_hwc(im) for im in images]
     blobs = compress_images(net, imgs, max_batch=max_batch, step=step, max_bytes=max_bytes, bpp=bpp,
-                            step_offsets=step_offsets, block=block, rdo=rdo, rdo_weights=rdo_weights)
+                            step_offsets=step_offsets, block=block, rdo=rdo, rdo_weights=rdo_weights,
+                            tile=tile)
     recons, sses = decode_groups(net, blobs, max_batch, refs=imgs)
     device = next(net.parameters()).device
     res = []
@@ -595,6 +815,8 @@ def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
              "recon": rec, "step": parse_blob(blob)[1]}
         if isinstance(r["step"], StepMap):   # a mapped blob: its base index, and the map beside it
             r["step_map"], r["block"], r["step"] = r["step"].indices, r["step"].block, r["step"].base
+        if isinstance(r["step"], TileInfo):  # a tiled blob: its ladder index, and the tile edge
+            r["tile"], r["step"] = r["step"].tile, r["step"].step
         if want_msssim:
             r["ms_ssim"] = r["ms_ssim_db"] = None
             if kernels.query("iclr17_ms_ssim_workspace_size", 1, H, W):   # 0: too small for 5 levels
@@ -637,6 +859,17 @@ def _boxes(texts: Sequence[str]) -> List[Tuple[int, int, int, int, int]]:
     return boxes
 
 
+def _region(text: str) -> Tuple[int, int, int, int]:
+    """A --region X0,Y0,X1,Y1 argument as a ``decompress_region`` box."""
+    try:
+        box = tuple(int(v) for v in text.split(","))
+    except ValueError:
+        box = ()
+    if len(box) != 4:
+        raise Iclr17Error(f"iclr17: codec: --region takes X0,Y0,X1,Y1 as four integers (got {text!r})")
+    return box
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     common = argparse.ArgumentParser(add_help=False)
     common.add_argument("--weights", required=True, help="checkpoint (model.load_model)")
@@ -660,9 +893,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     enc.add_argument("--rdo", type=float, default=None, metavar="L",
                      help="rate-distortion optimised quantisation with lambda L >= 0 (alone: at "
                           "the unit step; not with --roi)")
+    enc.add_argument("--tile", type=int, default=None, choices=kernels.TILES, metavar="T",
+                     help="independent streams per tile of T x T latent positions (16 pixels "
+                          "each; 8, 16, 32 or 64): parallel coding of a large image and region "
+                          "decode (not with --roi)")
     dec = sub.add_parser("decode", parents=[common], help="IN.i17c OUT.png")
     dec.add_argument("input")
     dec.add_argument("output")
+    dec.add_argument("--region", default=None, metavar="X0,Y0,X1,Y1",
+                     help="decode this pixel box alone (half-open); of a tiled stream only the "
+                          "tiles it needs are decoded")
     ev = sub.add_parser("eval", parents=[common], help="IMG...: one JSON line per image and a mean")
     ev.add_argument("images", nargs="+")
     ev.add_argument("--ms-ssim", action="store_true")
@@ -679,14 +919,18 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 roi = {"step_offsets": [roi_offsets(*image.shape[:2], _boxes(args.roi), args.block)],
                        "block": args.block}
             blob = net.compress_images([image], step=args.step, max_bytes=args.max_bytes,
-                                       bpp=args.bpp, rdo=args.rdo, **roi)[0]
+                                       bpp=args.bpp, rdo=args.rdo, tile=args.tile, **roi)[0]
             with open(args.output, "wb") as f:
                 f.write(blob)
         elif args.cmd == "decode":
             from PIL import Image
             with open(args.input, "rb") as f:
                 blob = f.read()
-            Image.fromarray(net.decompress_images([blob])[0]).save(args.output, format="PNG")
+            if args.region is None:
+                image = net.decompress_images([blob])[0]
+            else:
+                image = net.decompress_region(blob, _region(args.region))
+            Image.fromarray(image).save(args.output, format="PNG")
         else:
             imgs = [_load_image(p) for p in args.images]
             steps = [int(t) for t in args.steps.split(",")] if args.steps else [None]

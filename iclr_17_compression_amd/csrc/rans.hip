@@ -499,6 +499,269 @@ int map_window(int S, int K, int cpg, int window) {
   return (int)(wc < cpg ? wc : cpg);
 }
 
+// ----------------------------------------------------------------------------- tiles (§0k)
+// The same coder with a stream per spatial tile: the h×w latent is cut into tiles of t×t
+// positions (t = 2^lg; ragged at the bottom and right), one stream per (image, tile row, tile
+// column, channel group) in that order, symbols in (channel, row in tile, column in tile) order.
+// Lane ownership, block order, escapes, word groups and status bits are encode_kernel's and
+// decode_kernel's, so a tile's words are the oracle's encode_stream of its sequence.
+//
+// A launch codes the streams of a rectangle of tiles, nr×nc from tile (r0, c0), against a tensor
+// [B][oh][ow][N] whose origin is the rectangle's first position: the whole grid and the whole
+// latent for the encoder and a full decode, a few tiles and a compact window for a region decode.
+// Every stream's place follows from its index and this geometry, which the host has checked; no
+// address comes from device memory.
+//
+// WAVES waves share one workgroup and one staged table set, one stream each.
+struct TileGeo {
+  int h, w, N, cpg, P;   // the latent, its channels, channels per group, groups
+  int lg;                // log2 of the tile edge
+  int r0, c0, nr, nc;    // the rectangle of tiles
+  int oh, ow;            // the tensor's rows and columns
+  int ns;                // streams of the launch: B·nr·nc·P
+};
+
+// n / d for a divisor that is the same for the whole wave and every n below a bound known when
+// the stream starts: one multiply where m = ⌊2^32/d⌋ + 1 is exact (n·d < 2^32, d > 1), the
+// division otherwise. Worth 2 % of the tiled encoder and nothing measurable in the decoder (§0k).
+struct Divisor {
+  unsigned d, m;
+  bool fast;
+  __device__ __forceinline__ void set(unsigned divisor, unsigned long long bound) {
+    d = divisor;
+    fast = d > 1 && bound * d < (1ull << 32);
+    m = fast ? (unsigned)((1ull << 32) / d) + 1u : 0u;
+  }
+  __device__ __forceinline__ unsigned operator()(unsigned n) const {
+    return fast ? __umulhi(n, m) : n / d;
+  }
+};
+
+struct TileStream {
+  int b, grp;
+  int i0, j0;    // the tile's origin in the tensor
+  int th, tw;    // its extent
+  Divisor by_hw, by_tw;
+};
+
+__device__ __forceinline__ TileStream tile_stream(const TileGeo& g, int s) {
+  TileStream d;
+  d.grp = s % g.P;
+  int q = s / g.P;
+  const int tc = q % g.nc;
+  q /= g.nc;
+  const int tr = q % g.nr;
+  d.b = q / g.nr;
+  const int t = 1 << g.lg;
+  d.i0 = tr * t;
+  d.j0 = tc * t;
+  d.th = min(t, g.h - (g.r0 + tr) * t);
+  d.tw = min(t, g.w - (g.c0 + tc) * t);
+  d.by_hw.set((unsigned)(d.th * d.tw), (unsigned long long)g.cpg * d.th * d.tw + W);
+  d.by_tw.set((unsigned)d.tw, (unsigned long long)d.th * d.tw);
+  return d;
+}
+
+// symbol i of the stream: its channel within the group and its element of the tensor
+__device__ __forceinline__ long tile_index(const TileGeo& g, const TileStream& d, int i, int& cl) {
+  const int hw = d.th * d.tw;
+  cl = (int)d.by_hw((unsigned)i);
+  const int pix = i - cl * hw;
+  const int r = (int)d.by_tw((unsigned)pix), q = pix - r * d.tw;
+  return (((long)d.b * g.oh + d.i0 + r) * g.ow + d.j0 + q) * g.N + d.grp * g.cpg + cl;
+}
+
+template <int WAVES>
+__global__ void __launch_bounds__(W * WAVES) encode_tiled_kernel(
+    const float* __restrict__ y, TileGeo g, const int* __restrict__ cum, int K,
+    unsigned short* __restrict__ scratch, long cap, unsigned* __restrict__ lengths,
+    int* __restrict__ status) {
+  extern __shared__ int sc[];
+  const int NS = 2 * K + 2, TS = NS + 1;
+  for (int i = threadIdx.x; i < g.N * TS; i += W * WAVES) sc[i] = cum[i];
+  __syncthreads();   // the only barrier: from here every wave is on its own
+  const int lane = threadIdx.x & (W - 1);
+  const int s = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (s >= g.ns) return;
+  const TileStream d = tile_stream(g, s);
+  unsigned short* out = scratch + (long)s * cap;
+  long ptr = cap;
+  unsigned x = kL;
+  int bad = 0;
+  const int nsym = g.cpg * d.th * d.tw;
+  const int nblk = (nsym + W - 1) / W;
+  for (int blk = nblk - 1; blk >= 0; --blk) {
+    const int i = blk * W + lane;
+    const bool act = i < nsym;
+    int sym = 0, pay = -1;
+    const int* cc = sc;
+    if (act) {
+      int cl;
+      const long e = tile_index(g, d, i, cl);
+      const float v = y[e];
+      cc = sc + (d.grp * g.cpg + cl) * TS;
+      const float r = rintf(v);
+      if (!(r == v)) { bad |= ST_NONINT; sym = K; }   // NaN / non-integer
+      else if (fabsf(v) > 32767.f) { bad |= ST_RANGE; sym = K; }
+      else {
+        const int iv = (int)v;
+        sym = (iv >= -K && iv <= K) ? iv + K : NS - 1;
+        if (sym == NS - 1) pay = iv + 32768;
+      }
+    }
+    // sub-round B: escape payloads (uniform, freq 1: always one word out)
+    {
+      const bool need = pay >= 0;
+      const int2 rc = lane_rank(need, lane);
+      if (need) {
+        out[ptr - rc.y + rc.x] = (unsigned short)(x & 0xffffu);
+        x = ((x >> 16) << 16) + (unsigned)pay;
+      }
+      ptr -= rc.y;
+    }
+    // sub-round A: the symbols
+    {
+      const unsigned start = (unsigned)cc[sym], f = (unsigned)(cc[sym + 1] - cc[sym]);
+      const bool need = act && x >= (f << 16);
+      const int2 rc = lane_rank(need, lane);
+      if (need) {
+        out[ptr - rc.y + rc.x] = (unsigned short)(x & 0xffffu);
+        x >>= 16;
+      }
+      ptr -= rc.y;
+      if (act) x = ((x / f) << 16) + (x % f) + start;
+    }
+  }
+  ptr -= 2 * W;
+  out[ptr + 2 * lane] = (unsigned short)(x >> 16);
+  out[ptr + 2 * lane + 1] = (unsigned short)(x & 0xffffu);
+  if (lane == 0) lengths[s] = (unsigned)(cap - ptr);
+  bad = wave_or(bad);
+  if (lane == 0 && bad) atomicOr(status, bad);
+}
+
+template <int WAVES>
+__global__ void __launch_bounds__(W * WAVES) decode_tiled_kernel(
+    const unsigned short* __restrict__ words, const long* __restrict__ offsets, long total,
+    TileGeo g, const int* __restrict__ cum, int K, float* __restrict__ y,
+    int* __restrict__ status) {
+  extern __shared__ int sc[];
+  const int NS = 2 * K + 2, TS = NS + 1;
+  for (int i = threadIdx.x; i < g.N * TS; i += W * WAVES) sc[i] = cum[i];
+  __syncthreads();   // the only barrier: from here every wave is on its own
+  const int lane = threadIdx.x & (W - 1);
+  const int s = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (s >= g.ns) return;
+  const TileStream d = tile_stream(g, s);
+  const long o0 = offsets[s], o1 = offsets[s + 1];
+  const long n = o1 - o0;
+  int bad = 0;
+  // the offsets come from a stream: never read outside the words, whatever they say
+  if (o0 < 0 || o1 > total || n < 2 * W) {
+    if (lane == 0) atomicOr(status, ST_OVERRUN);
+    return;
+  }
+  const unsigned short* in = words + o0;
+  unsigned x = ((unsigned)in[2 * lane] << 16) | in[2 * lane + 1];
+  long ptr = 2 * W;
+  auto word = [&](bool need, int& fail) -> unsigned {
+    const int2 rc = lane_rank(need, lane);
+    unsigned w = 0;
+    if (need) {
+      if (ptr + rc.x < n) w = in[ptr + rc.x];
+      else fail |= ST_OVERRUN;
+    }
+    ptr += rc.y;
+    return w;
+  };
+  const int nsym = g.cpg * d.th * d.tw;
+  const int nblk = (nsym + W - 1) / W;
+  for (int blk = 0; blk < nblk; ++blk) {
+    const int i = blk * W + lane;
+    const bool act = i < nsym;
+    int v = 0;
+    bool esc = false;
+    long e = 0;
+    if (act) {
+      int cl;
+      e = tile_index(g, d, i, cl);
+      const int* cc = sc + (d.grp * g.cpg + cl) * TS;
+      const unsigned slot = x & 0xffffu;
+      int lo = 0, hi = NS;   // cc[lo] ≤ slot < cc[hi]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned)cc[mid] <= slot) lo = mid; else hi = mid;
+      }
+      const unsigned start = (unsigned)cc[lo], f = (unsigned)(cc[lo + 1] - cc[lo]);
+      x = f * (x >> 16) + slot - start;
+      v = lo - K;
+      esc = lo == NS - 1;
+    }
+    {   // sub-round A: renormalise after the symbols
+      const bool need = act && x < kL;
+      const unsigned w = word(need, bad);
+      if (need) x = (x << 16) | w;
+    }
+    {   // sub-round B: escape payloads
+      unsigned u = 0;
+      if (esc) {
+        u = x & 0xffffu;
+        x >>= 16;
+      }
+      const unsigned w = word(esc, bad);
+      if (esc) {
+        x = (x << 16) | w;
+        v = (int)u - 32768;
+      }
+    }
+    if (act) y[e] = (float)v;
+  }
+  if (x != kL) bad |= ST_TRAIL;
+  if (lane == 0 && ptr != n) bad |= ST_TRAIL;
+  bad = wave_or(bad);
+  if (lane == 0 && bad) atomicOr(status, bad);
+}
+
+// Waves per workgroup when the caller leaves it open (§0k, profiles/tiled_ab.txt). The coder is
+// bound by one wave's chain of dependent steps, not by throughput: while every stream can have a
+// workgroup of its own resident — the LDS holds ⌊160 KiB / tables⌋ of them per CU — one wave per
+// workgroup spreads the streams over the most CUs and is the faster by 0–9 %. With more streams
+// than that, one-wave workgroups queue behind the LDS limit while SIMDs idle, and four waves
+// sharing a staged table set are 1.3–1.7× faster.
+int tiled_waves(int ns, size_t shm) {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    cus = n;
+  }
+  const long resident = (long)cus * (long)((160 * 1024) / shm);
+  return ns <= resident ? 1 : 4;
+}
+
+// The geometry of a tiled launch from the caller's scalars, or false with the reason in `why`.
+bool tile_geo(int B, int h, int w, int N, int P, int log2_t, int r0, int c0, int nr, int nc,
+              TileGeo& g, const char*& why) {
+  why = "bad shape";
+  if (B <= 0 || h <= 0 || w <= 0 || N <= 0 || P <= 0 || N % P) return false;
+  why = "log2 of the tile edge is not 3..6";
+  if (log2_t < 3 || log2_t > 6) return false;
+  const int t = 1 << log2_t, th = (h + t - 1) / t, tw = (w + t - 1) / t;
+  why = "the tile rectangle is not inside the tile grid";
+  if (r0 < 0 || c0 < 0 || nr <= 0 || nc <= 0 || r0 > th - nr || c0 > tw - nc) return false;
+  why = "too many streams";
+  const long ns = (long)B * nr * nc * P;
+  if (ns > (1L << 24)) return false;
+  g.h = h; g.w = w; g.N = N; g.cpg = N / P; g.P = P; g.lg = log2_t;
+  g.r0 = r0; g.c0 = c0; g.nr = nr; g.nc = nc;
+  g.oh = (h < (r0 + nr) * t ? h : (r0 + nr) * t) - r0 * t;
+  g.ow = (w < (c0 + nc) * t ? w : (c0 + nc) * t) - c0 * t;
+  g.ns = (int)ns;
+  return true;
+}
+
 }  // namespace
 }  // namespace iclr17
 
@@ -616,6 +879,91 @@ int iclr17_rans_decode_map(const uint16_t* words, const int64_t* offsets, int B,
                      (const unsigned short*)words, (const long*)offsets, g, m, K, y_hat,
                      (int*)status);
   return check_launch("rans_decode_map");
+}
+
+long iclr17_rans_tiled_capacity(int N, int streams_per_tile, int log2_t) {
+  if (N <= 0 || streams_per_tile <= 0 || N % streams_per_tile || log2_t < 3 || log2_t > 6) return 0;
+  return 2L * W + 2L * (N / streams_per_tile) * (1L << (2 * log2_t));
+}
+
+int iclr17_rans_tiled_streams(int h, int w, int streams_per_tile, int log2_t) {
+  if (h <= 0 || w <= 0 || streams_per_tile <= 0 || log2_t < 3 || log2_t > 6) return 0;
+  const long t = 1L << log2_t;
+  const long n = ((h + t - 1) / t) * ((w + t - 1) / t) * streams_per_tile;
+  return n > (1L << 24) ? 0 : (int)n;
+}
+
+int iclr17_rans_encode_tiled(const float* y_hat, int B, int h, int w, int N, int streams_per_tile,
+                             int log2_t, const int32_t* cum, int K, int waves, uint16_t* scratch,
+                             long scratch_words, uint32_t* lengths, int32_t* status,
+                             void* stream) {
+  ICLR17_REQUIRE(y_hat && cum && scratch && lengths && status && K >= 1 && K <= 1024,
+                 ICLR17_EINVAL, "rans_encode_tiled: bad arguments");
+  TileGeo g;
+  const char* why;
+  const int t = log2_t >= 3 && log2_t <= 6 ? 1 << log2_t : 1;
+  ICLR17_REQUIRE(tile_geo(B, h, w, N, streams_per_tile, log2_t, 0, 0, (h + t - 1) / t,
+                          (w + t - 1) / t, g, why),
+                 ICLR17_EINVAL, "rans_encode_tiled: %s", why);
+  const size_t shm = (size_t)N * (2 * K + 3) * sizeof(int);
+  ICLR17_REQUIRE(shm <= 64 * 1024, ICLR17_EINVAL,
+                 "rans_encode_tiled: tables of %zu bytes exceed LDS", shm);
+  const long cap = iclr17_rans_tiled_capacity(N, streams_per_tile, log2_t);
+  ICLR17_REQUIRE(scratch_words >= cap * g.ns, ICLR17_EINVAL,
+                 "rans_encode_tiled: scratch of %ld words < %ld", scratch_words, cap * g.ns);
+  if (!waves) waves = tiled_waves(g.ns, shm);
+#define ICLR17_ENC_TILED(WV)                                                                     \
+  hipLaunchKernelGGL(encode_tiled_kernel<WV>, dim3((g.ns + WV - 1) / WV), dim3(W * WV), shm,     \
+                     (hipStream_t)stream, y_hat, g, (const int*)cum, K,                          \
+                     (unsigned short*)scratch, cap, (unsigned*)lengths, (int*)status)
+  switch (waves) {
+    case 1: ICLR17_ENC_TILED(1); break;
+    case 2: ICLR17_ENC_TILED(2); break;
+    case 4: ICLR17_ENC_TILED(4); break;
+    case 8: ICLR17_ENC_TILED(8); break;
+    case 16: ICLR17_ENC_TILED(16); break;
+    default:
+      ICLR17_REQUIRE(false, ICLR17_EINVAL,
+                     "rans_encode_tiled: %d waves per workgroup (0, 1, 2, 4, 8, 16)", waves);
+  }
+#undef ICLR17_ENC_TILED
+  return check_launch("rans_encode_tiled");
+}
+
+int iclr17_rans_decode_tiled(const uint16_t* words, long total_words, const int64_t* offsets,
+                             int B, int h, int w, int N, int streams_per_tile, int log2_t, int r0,
+                             int c0, int nr, int nc, const int32_t* cum, int K, int waves,
+                             float* y_hat, long y_elems, int32_t* status, void* stream) {
+  ICLR17_REQUIRE(words && offsets && cum && y_hat && status && total_words >= 0 && K >= 1 &&
+                     K <= 1024,
+                 ICLR17_EINVAL, "rans_decode_tiled: bad arguments");
+  TileGeo g;
+  const char* why;
+  ICLR17_REQUIRE(tile_geo(B, h, w, N, streams_per_tile, log2_t, r0, c0, nr, nc, g, why),
+                 ICLR17_EINVAL, "rans_decode_tiled: %s", why);
+  const size_t shm = (size_t)N * (2 * K + 3) * sizeof(int);
+  ICLR17_REQUIRE(shm <= 64 * 1024, ICLR17_EINVAL,
+                 "rans_decode_tiled: tables of %zu bytes exceed LDS", shm);
+  const long need = (long)B * g.oh * g.ow * N;
+  ICLR17_REQUIRE(y_elems >= need, ICLR17_EINVAL,
+                 "rans_decode_tiled: output of %ld elements < %ld", y_elems, need);
+  if (!waves) waves = tiled_waves(g.ns, shm);
+#define ICLR17_DEC_TILED(WV)                                                                     \
+  hipLaunchKernelGGL(decode_tiled_kernel<WV>, dim3((g.ns + WV - 1) / WV), dim3(W * WV), shm,     \
+                     (hipStream_t)stream, (const unsigned short*)words, (const long*)offsets,    \
+                     total_words, g, (const int*)cum, K, y_hat, (int*)status)
+  switch (waves) {
+    case 1: ICLR17_DEC_TILED(1); break;
+    case 2: ICLR17_DEC_TILED(2); break;
+    case 4: ICLR17_DEC_TILED(4); break;
+    case 8: ICLR17_DEC_TILED(8); break;
+    case 16: ICLR17_DEC_TILED(16); break;
+    default:
+      ICLR17_REQUIRE(false, ICLR17_EINVAL,
+                     "rans_decode_tiled: %d waves per workgroup (0, 1, 2, 4, 8, 16)", waves);
+  }
+#undef ICLR17_DEC_TILED
+  return check_launch("rans_decode_tiled");
 }
 
 }  // extern "C"

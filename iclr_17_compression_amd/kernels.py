@@ -1480,6 +1480,99 @@ def rans_decode_map(words: Tensor, offsets: Tensor, cum: Tensor, slots, block: i
     return y
 
 
+# ------------------------------------------------------------ tiled streams (csrc/rans.hip, §0k)
+TILES = (8, 16, 32, 64)        # tile edges t of the tiled coder, in latent positions
+TILE_WAVES = (1, 2, 4, 8, 16)  # waves per workgroup of the tiled kernels (one stream each)
+
+
+def tile_grid(h: int, w: int, tile: int) -> Tuple[int, int]:
+    """(th, tw) = (⌈h/t⌉, ⌈w/t⌉): the tiles of an h×w latent."""
+    if isinstance(tile, bool) or not isinstance(tile, (int, np.integer)) or tile not in TILES:
+        raise Iclr17Error(f"iclr17: tiled coder: the tile edge {tile!r} is not one of {TILES}")
+    if h < 1 or w < 1:
+        raise Iclr17Error(f"iclr17: tiled coder: a latent of {h}x{w} positions")
+    return -(-h // tile), -(-w // tile)
+
+
+def _tiled_args(what: str, cum, N: int, K: int, P: int, tile: int, h: int, w: int, waves):
+    """The scalar arguments of a tiled launch checked on the host → (th, tw, log2 t, waves)."""
+    th, tw = tile_grid(h, w, tile)
+    if isinstance(P, bool) or not isinstance(P, (int, np.integer)) or P < 1 or N % P:
+        raise Iclr17Error(f"iclr17: {what}: N={N} not divisible into {P!r} streams per tile")
+    if (not isinstance(cum, torch.Tensor) or cum.device.type != "cuda" or cum.dtype != torch.int32
+            or tuple(cum.shape) != (N, 2 * K + 3)):
+        raise Iclr17Error(f"iclr17: {what}: the tables must be an int32 GPU tensor [{N}, {2 * K + 3}]")
+    if waves is not None and (isinstance(waves, bool) or waves not in TILE_WAVES):
+        raise Iclr17Error(f"iclr17: {what}: {waves!r} waves per workgroup (one of {TILE_WAVES})")
+    return th, tw, TILES.index(tile) + 3, int(waves or 0)
+
+
+def rans_encode_tiled(y_hat: Tensor, cum: Tensor, tile: int, K: int = ENTROPY_K,
+                      streams_per_tile: int = 1, waves: Optional[int] = None):
+    """ŷ NHWC [B,h,w,N] → (words, offsets int64 [B·th·tw·P + 1]) with a stream per (image, tile
+    row, tile column, channel group) of ``tile``×``tile`` latent positions (``tile_grid``), each
+    the words ``rans_encode`` gives the tile as a latent of its own. ``waves``: waves per
+    workgroup (None: the measured default); every choice gives the same words."""
+    _check(y_hat, "latent", 4)
+    B, h, w, N = y_hat.shape
+    P = streams_per_tile
+    th, tw, lg, wv = _tiled_args("rans_encode_tiled", cum, N, K, P, tile, h, w, waves)
+    cap = query("iclr17_rans_tiled_capacity", N, P, lg)
+    ns = B * th * tw * P
+    dev = y_hat.device
+    scratch = torch.empty(ns * cap, device=dev, dtype=torch.int16)
+    lengths = torch.empty(ns, device=dev, dtype=torch.int32)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    st = _stream(y_hat)
+    call("iclr17_rans_encode_tiled", _p(y_hat.contiguous()), B, h, w, N, P, lg, _p(cum.contiguous()),
+         K, wv, _p(scratch), scratch.numel(), _p(lengths), _p(status), st)
+    offsets = torch.empty(ns + 1, device=dev, dtype=torch.int64)
+    call("iclr17_rans_offsets", _p(lengths), ns, _p(offsets), st)
+    total = int(offsets[-1].item())
+    words = torch.empty(max(total, 1), device=dev, dtype=torch.int16)
+    call("iclr17_rans_pack", _p(scratch), cap, _p(offsets), ns, _p(words), st)
+    _rans_status(status, "rans_encode_tiled")
+    return words[:total], offsets
+
+
+def rans_decode_tiled(words: Tensor, offsets: Tensor, cum: Tensor, B: int, h: int, w: int, N: int,
+                      tile: int, K: int = ENTROPY_K, streams_per_tile: int = 1,
+                      rect: Optional[Tuple[int, int, int, int]] = None,
+                      waves: Optional[int] = None) -> Tensor:
+    """Inverse of ``rans_encode_tiled`` → ŷ NHWC fp32 [B,h,w,N]. With ``rect`` = (r0, c0, r1, c1),
+    a half-open rectangle of tiles, ``words`` / ``offsets`` hold the B·(r1−r0)·(c1−c0)·P streams
+    of those tiles alone, in stream order, and the result is the window they cover:
+    [B, min(h, r1·t) − r0·t, min(w, c1·t) − c0·t, N]."""
+    P = streams_per_tile
+    th, tw, lg, wv = _tiled_args("rans_decode_tiled", cum, N, K, P, tile, h, w, waves)
+    r0, c0, r1, c1 = (0, 0, th, tw) if rect is None else (int(v) for v in rect)
+    if not (0 <= r0 < r1 <= th and 0 <= c0 < c1 <= tw):
+        raise Iclr17Error(f"iclr17: rans_decode_tiled: the tile rectangle {(r0, c0, r1, c1)} is not "
+                          f"inside the {th}x{tw} tiles")
+    if B < 1:
+        raise Iclr17Error(f"iclr17: rans_decode_tiled: B={B}")
+    ns = B * (r1 - r0) * (c1 - c0) * P
+    dev = cum.device
+    if (not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64
+            or offsets.numel() != ns + 1):
+        raise Iclr17Error(f"iclr17: rans_decode_tiled: offsets do not match the {ns} streams of the "
+                          "tile rectangle")
+    if not isinstance(words, torch.Tensor) or words.dtype != torch.int16 or words.dim() != 1:
+        raise Iclr17Error("iclr17: rans_decode_tiled: words must be a 1-D int16 tensor")
+    if words.device != dev or offsets.device != dev:
+        raise Iclr17Error("iclr17: rans_decode_tiled: words, offsets and tables on different devices")
+    oh, ow = min(h, r1 * tile) - r0 * tile, min(w, c1 * tile) - c0 * tile
+    y = torch.empty(B, oh, ow, N, device=dev, dtype=torch.float32)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    total = words.numel()
+    words = words.contiguous() if total else torch.zeros(1, device=dev, dtype=torch.int16)
+    call("iclr17_rans_decode_tiled", _p(words), total, _p(offsets.contiguous()), B, h, w, N, P, lg,
+         r0, c0, r1 - r0, c1 - c0, _p(cum.contiguous()), K, wv, _p(y), y.numel(), _p(status),
+         _stream(y))
+    _rans_status(status, "rans_decode_tiled")
+    return y
+
+
 # ------------------------------------------------------------ stepped training (csrc/steptrain.hip)
 def _step_args(t: Tensor, steps_dev: Tensor, rate_packed: Tensor, what: str):
     """An fp32 NHWC latent-shaped tensor, the [B] fp32 step sizes and the UNscaled pack, checked."""

@@ -334,7 +334,8 @@ class ImageCompressor(nn.Module):
     def compress_latents(self, y: torch.Tensor, step: Optional[int],
                          streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                          K: int = kernels.ENTROPY_K, step_map=None,
-                         block: int = 4, rdo=None, rdo_weights=None) -> Dict[str, object]:
+                         block: int = 4, rdo=None, rdo_weights=None,
+                         tile: Optional[int] = None) -> Dict[str, object]:
         """``compress`` from the latent of ``latents`` at ladder step ``step``: ŷ = rint(y/Δ)
         (kernels.quantise_step), then rANS with the step's tables. Returns ``compress``'s dict and
         "y_hat" (NHWC). With ``step_map`` (ladder indices per block, integers [B, mh, mw] for
@@ -345,8 +346,15 @@ class ImageCompressor(nn.Module):
         With ``rdo`` (λ ≥ 0, finite; ``rdo_weights``: [N] channel weights, default
         ``synthesis_gains``) the levels are rate–distortion optimised (kernels.quantise_rdo,
         DESIGN.md §0j) and coded with the step's same tables; the dict gains "est_bits", the
-        model's estimate of ŷ per image (float64 [B] on the device). Not with ``step_map``."""
+        model's estimate of ŷ per image (float64 [B] on the device). Not with ``step_map``.
+
+        With ``tile`` (8, 16, 32 or 64) the same ŷ is coded with a stream per tile of
+        ``tile``×``tile`` latent positions and channel group (kernels.rans_encode_tiled, DESIGN.md
+        §0k): a string then holds th·tw·P word counts, in (tile row, tile column, group) order,
+        and the words. Not with ``step_map``."""
         from . import codec
+        if tile is not None and step_map is not None:
+            raise kernels.Iclr17Error(codec.TILE_WITH_MAP)
         if rdo is not None:
             if step_map is not None:
                 raise kernels.Iclr17Error(codec.RDO_WITH_MAP)
@@ -354,13 +362,13 @@ class ImageCompressor(nn.Module):
             y_hat, _, est = kernels.quantise_rdo(y, self.bitEstimator.packed(),
                                                  codec.step_size(step), lam)
             enc = self._entropy_code(y_hat, self.bitEstimator.entropy_tables(K, step=step),
-                                     streams_per_image, K)
+                                     streams_per_image, K, tile=tile)
             enc["est_bits"] = est
             return enc
         if step_map is None:
             y_hat, _ = kernels.quantise_step(y, codec.step_size(step))
             return self._entropy_code(y_hat, self.bitEstimator.entropy_tables(K, step=step),
-                                      streams_per_image, K)
+                                      streams_per_image, K, tile=tile)
         if step is not None:
             raise kernels.Iclr17Error("iclr17: compress_latents: step and step_map given together")
         tables, slots = self._map_tables(step_map, K)
@@ -368,9 +376,14 @@ class ImageCompressor(nn.Module):
                                              [codec.step_size(s) for s in range(codec.STEPS)])
         return self._entropy_code(y_hat, tables, streams_per_image, K, slots, block)
 
-    def _entropy_code(self, y_hat, tables, P, K, slots=None, block=None):
+    def _entropy_code(self, y_hat, tables, P, K, slots=None, block=None, tile=None):
         B, h, w, N = y_hat.shape
-        if slots is None:
+        S = P   # streams per image
+        if tile is not None:
+            th, tw = kernels.tile_grid(h, w, tile)
+            S = th * tw * P
+            words, offsets = kernels.rans_encode_tiled(y_hat, tables, tile, K, P)
+        elif slots is None:
             words, offsets = kernels.rans_encode(y_hat, tables, K, P)
         else:
             words, offsets = kernels.rans_encode_map(y_hat, tables, slots, block, K, P)
@@ -378,7 +391,7 @@ class ImageCompressor(nn.Module):
         wv = words.cpu().numpy().view("<u2")
         strings = []
         for b in range(B):
-            o = off[b * P:(b + 1) * P + 1]
+            o = off[b * S:(b + 1) * S + 1]
             strings.append(np.diff(o).astype("<u4").tobytes() + wv[o[0]:o[-1]].tobytes())
         return {"strings": strings, "shape": (h, w), "streams_per_image": P, "K": K,
                 "y_hat": y_hat}
@@ -386,11 +399,12 @@ class ImageCompressor(nn.Module):
     # ------------------------------------------------------------- entropy coding (§8 f4)
     @torch.no_grad()
     def compress(self, x: torch.Tensor, streams_per_image: int = kernels.STREAMS_PER_IMAGE,
-                 K: int = kernels.ENTROPY_K) -> Dict[str, object]:
+                 K: int = kernels.ENTROPY_K, tile: Optional[int] = None) -> Dict[str, object]:
         """Encode images to byte strings: the analysis transform, rounding, then rANS over the
         factorised BitEstimator (the model the reference uses only to estimate bpp). Per image:
         P little-endian uint32 stream word counts, then the stream words (uint16 LE).
-        Returns {"strings": [bytes] * B, "shape": (h, w), "streams_per_image": P, "K": K}."""
+        Returns {"strings": [bytes] * B, "shape": (h, w), "streams_per_image": P, "K": K}.
+        With ``tile`` the same ŷ in tiled streams, as ``compress_latents(tile=)`` lays them out."""
         mode = kernels.precision()
         y_hat = self.encode_latents(x, mode=mode)["y_hat"]
         if mode == "h3" and kernels.h3_range_overflowed(x.device):
@@ -399,23 +413,32 @@ class ImageCompressor(nn.Module):
             # the stream sizes below synchronise anyway.
             with kernels.precision_scope("x6"):
                 y_hat = self.encode_latents(x)["y_hat"]
-        enc = self._entropy_code(y_hat, self.bitEstimator.entropy_tables(K), streams_per_image, K)
+        enc = self._entropy_code(y_hat, self.bitEstimator.entropy_tables(K), streams_per_image, K,
+                                 tile=tile)
         del enc["y_hat"]
         return enc
 
     @torch.no_grad()
     def decompress(self, strings, shape, streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                    K: int = kernels.ENTROPY_K, device=None, step: Optional[int] = None,
-                   step_map=None, block: int = 4) -> Dict[str, torch.Tensor]:
+                   step_map=None, block: int = 4,
+                   tile: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """Inverse of ``compress``: byte strings → {"y_hat": NCHW latents, "x_hat": the clipped
         reconstruction} (bit-identical latents; the synthesis as in ``forward``). With ``step``
         the inverse of ``compress_latents`` at that ladder step: the step's tables decode ŷ, and
         the synthesis runs on Δ·ŷ as a general (non-integer) latent. With ``step_map`` /
-        ``block`` the inverse of ``compress_latents(step_map=…)``."""
+        ``block`` the inverse of ``compress_latents(step_map=…)``; with ``tile`` the inverse of
+        ``compress`` / ``compress_latents`` with that tile edge."""
         if step is not None and step_map is not None:
             raise kernels.Iclr17Error("iclr17: decompress: step and step_map given together")
         P, N = streams_per_image, self.out_channel_N
         h, w = shape
+        if tile is not None:
+            if step_map is not None:
+                from . import codec
+                raise kernels.Iclr17Error(codec.TILE_WITH_MAP)
+            th, tw = kernels.tile_grid(h, w, tile)
+            P = th * tw * streams_per_image   # streams per image
         device = device or next(self.parameters()).device
         counts, payload = [], []
         for sbytes in strings:
@@ -431,7 +454,11 @@ class ImageCompressor(nn.Module):
         off = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.int64)
         words = torch.from_numpy(np.concatenate(payload).view(np.int16).copy()).to(device)
         offsets = torch.from_numpy(off).to(device)
-        if step_map is None:
+        if tile is not None:
+            y_hat = kernels.rans_decode_tiled(words, offsets,
+                                              self.bitEstimator.entropy_tables(K, step=step),
+                                              B, h, w, N, tile, K, streams_per_image)
+        elif step_map is None:
             y_hat = kernels.rans_decode(words, offsets,
                                         self.bitEstimator.entropy_tables(K, step=step),
                                         B, h, w, N, K, P)
@@ -461,7 +488,8 @@ class ImageCompressor(nn.Module):
                         streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                         K: int = kernels.ENTROPY_K, step: Optional[int] = None,
                         max_bytes=None, bpp=None, stats: Optional[dict] = None,
-                        step_offsets=None, block: int = 4, rdo=None, rdo_weights=None):
+                        step_offsets=None, block: int = 4, rdo=None, rdo_weights=None,
+                        tile: Optional[int] = None):
         """8-bit images of any sizes ≥ 1×1 (a sequence of uint8 HWC RGB arrays, numpy or torch) →
         one self-describing blob per image, in input order: codec.py's 28-byte header (true size,
         N, P, K, weights fingerprint) + the image's ``compress`` string. Images are batched by
@@ -488,20 +516,28 @@ class ImageCompressor(nn.Module):
         level is the cheapest of rint(y/Δ), its neighbour toward zero and zero under
         bits + λ·g_c·Δ²·error², with ``rdo_weights`` [N] as g (default ``synthesis_gains``). It goes
         with ``step`` or a budget and alone means the unit step; the blobs are ordinary I17Q ones
-        and record nothing of it. With ``step_offsets`` it raises (per-block RDO is not built)."""
+        and record nothing of it. With ``step_offsets`` it raises (per-block RDO is not built).
+
+        ``tile`` (8, 16, 32 or 64 latent positions, 16 pixels each; None: today's streams) codes
+        the same latents with an independent stream per tile and channel group (codec.py, "Tiled
+        streams"): many waves code one large image, and ``decompress_region`` decodes a pixel box
+        from the tiles it needs alone. It goes with ``step``, a budget (the tile overhead
+        counted) and ``rdo``; alone it codes ``compress``'s own ŷ. These blobs carry the magic
+        I17T, a ladder index (8 when no rate option is given) and the tile edge. With
+        ``step_offsets`` it raises (tiled step maps are not built)."""
         from . import codec
         return codec.compress_images(self, images, max_batch, streams_per_image, K, step=step,
                                      max_bytes=max_bytes, bpp=bpp, stats=stats,
                                      step_offsets=step_offsets, block=block, rdo=rdo,
-                                     rdo_weights=rdo_weights)
+                                     rdo_weights=rdo_weights, tile=tile)
 
     @torch.no_grad()
     def decompress_images(self, blobs, max_batch: int = 64):
         """Inverse of ``compress_images``: blobs → uint8 HWC numpy arrays of the true sizes, in
         input order (``decompress`` per canvas batch, then kernels.image_egress: round-half-even of
-        the clipped reconstruction·255, cropped). Plain (I17C), stepped (I17Q) and mapped (I17M)
-        blobs may be mixed; a batch holds blobs of one canvas, P, K and step (mapped ones: of one
-        block edge). Raises Iclr17Error on a foreign or truncated blob, a corrupt step map,
+        the clipped reconstruction·255, cropped). Plain (I17C), stepped (I17Q), mapped (I17M) and
+        tiled (I17T) blobs may be mixed; a batch holds blobs of one canvas, P, K and step (mapped
+        ones: of one block edge; tiled ones: of one tile edge). Raises Iclr17Error on a foreign or truncated blob, a corrupt step map,
         another N or other weights (the header's fingerprint). Within one precision mode
         the bytes are reproducible and independent of the batch; between modes a pixel may differ
         by one 8-bit step."""
@@ -509,9 +545,20 @@ class ImageCompressor(nn.Module):
         return codec.decode_groups(self, list(blobs), max_batch)[0]
 
     @torch.no_grad()
+    def decompress_region(self, blob, box, stats: Optional[dict] = None):
+        """The pixels ``box`` = (x0, y0, x1, y1) (half-open, inside the image) of one blob → uint8
+        [y1 − y0, x1 − x0, 3], byte for byte ``decompress_images([blob])[0][y0:y1, x0:x1]``. Of a
+        tiled (I17T) blob only the streams of the tiles that cover the latent positions the box
+        depends on (codec.region_window) are decoded, and the synthesis runs on that rectangle of
+        the latent as an image of its own; any other blob is decoded whole. ``stats`` (a dict)
+        receives "streams_decoded" and "streams_total"."""
+        from . import codec
+        return codec.decode_region(self, blob, box, stats)
+
+    @torch.no_grad()
     def evaluate_images(self, images, want_msssim: bool = False, max_batch: int = 64,
                         step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
-                        block: int = 4, rdo=None, rdo_weights=None):
+                        block: int = 4, rdo=None, rdo_weights=None, tile: Optional[int] = None):
         """The real codec path per image, compress_images then decompress_images, measured on
         the 8-bit decoded image as codecs are reported: a dict per image with ``bytes``, ``bpp`` =
         8·len(blob)/(H·W) (header included, true pixel count), ``sse_u8`` (int), ``psnr_u8`` =
@@ -520,11 +567,12 @@ class ImageCompressor(nn.Module):
         small for 5 levels) and ``step`` (the blob's ladder step; None for a plain blob).
         ``step`` / ``max_bytes`` / ``bpp`` / ``step_offsets`` / ``block`` / ``rdo`` /
         ``rdo_weights`` as in ``compress_images``; a mapped blob's row has its base index as
-        ``step`` and also ``step_map`` and ``block``. Precision as ``decompress_images``."""
+        ``step`` and also ``step_map`` and ``block``; with ``tile`` a row has the blob's ladder
+        index as ``step`` and also ``tile``. Precision as ``decompress_images``."""
         from . import codec
         return codec.evaluate_images(self, images, want_msssim, max_batch, step=step,
                                      max_bytes=max_bytes, bpp=bpp, step_offsets=step_offsets,
-                                     block=block, rdo=rdo, rdo_weights=rdo_weights)
+                                     block=block, rdo=rdo, rdo_weights=rdo_weights, tile=tile)
 
     @torch.no_grad()
     def evaluate(self, x: torch.Tensor, want_y: bool = False,

@@ -367,6 +367,39 @@ int iclr17_rans_decode_map(const uint16_t* words, const int64_t* offsets, int B,
                            const uint8_t* slots, int log2_g, int window, float* y_hat,
                            int32_t* status, void* stream);
 
+/* --------------------------------------------------------------- tiled streams (csrc/rans.hip)
+ * The entropy coder with a stream per spatial tile of the latent: one large image
+ * is coded by many waves, and a decoder can read a rectangle of tiles alone. The h×w latent is cut
+ * into tiles of t×t positions, t = 2^log2_t with log2_t = 3..6, ⌈h/t⌉×⌈w/t⌉ of them, ragged at the
+ * bottom and right. One stream per (image, tile row, tile column, channel group), in that order;
+ * within a stream the symbols run in (channel, row in tile, column in tile) order. Everything
+ * else — lanes, blocks, escapes, word order, tables, status bits — is the plain entries': a tile's
+ * words are what iclr17_rans_encode writes for the tile as a latent of its own. `waves`: waves
+ * per workgroup (1, 2, 4, 8, 16; one stream each, sharing one staged table set), 0 the default;
+ * every choice gives the same words. Offsets and pack are iclr17_rans_offsets / iclr17_rans_pack
+ * with the capacity below. */
+/* Words of per-stream scratch: 128 + 2·(N/P)·t² (0: bad arguments). */
+long iclr17_rans_tiled_capacity(int N, int streams_per_tile, int log2_t);
+/* Streams per image: ⌈h/t⌉·⌈w/t⌉·P (0: bad arguments). */
+int iclr17_rans_tiled_streams(int h, int w, int streams_per_tile, int log2_t);
+/* ŷ NHWC [B][h][w][N] → stream s's words at the END of its scratch slot s·capacity, its word
+ * count in lengths[s], s = ((b·⌈h/t⌉ + tile row)·⌈w/t⌉ + tile column)·P + group. status as
+ * iclr17_rans_encode's. */
+int iclr17_rans_encode_tiled(const float* y_hat, int B, int h, int w, int N, int streams_per_tile,
+                             int log2_t, const int32_t* cum, int K, int waves, uint16_t* scratch,
+                             long scratch_words, uint32_t* lengths, int32_t* status,
+                             void* stream);
+/* Decodes the streams of the nr×nc tiles from tile (r0, c0) of B images of an h×w latent into
+ * y_hat NHWC [B][oh][ow][N], the window those tiles cover: oh = min(h, (r0 + nr)·t) − r0·t, ow
+ * likewise (r0 = c0 = 0 with the whole grid: the whole latent). words / offsets hold these
+ * B·nr·nc·P streams alone, in the order above; total_words is the length of words, and a stream
+ * whose offsets leave it sets status 4 and is not read. y_elems: the elements y_hat holds
+ * (≥ B·oh·ow·N). status as iclr17_rans_decode's. */
+int iclr17_rans_decode_tiled(const uint16_t* words, long total_words, const int64_t* offsets,
+                             int B, int h, int w, int N, int streams_per_tile, int log2_t, int r0,
+                             int c0, int nr, int nc, const int32_t* cum, int K, int waves,
+                             float* y_hat, long y_elems, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------ stepped training (csrc/steptrain.hip)
  * The quantiser / rate part of a training step whose images each have a ladder step of their own
  * (DESIGN.md §0h): the coder's convention above with the rounding replaced by noise. Per image b
