@@ -98,6 +98,19 @@ built. The blob:
 It always carries a ladder index: a call with ``tile`` and no rate option writes index 8 and codes
 ``compress``'s own ŷ. ``decompress_images`` takes the four kinds mixed.
 
+Quality targets. ``compress_images(..., psnr=T)`` is the opposite request: at
+least T dB, as small as the ladder allows. An index *passes* for an image when the integer SSE of
+its 8-bit decode is ≤ ``sse_limit(H, W, T)`` = ⌊255²·3·H·W·10^(−T/10)⌋; ``search_quality`` brackets the
+boundary with at most 8 probes per image, and the image is coded at the index L it ends on: L
+passed, and it is 31 or index L + 1 was measured and failed. The SSE is not assumed monotone along
+the ladder. A probe (``quality_probe``) quantises every unfinished image of a canvas batch at its
+own index, runs the synthesis and sums the squared 8-bit error on the device: no entropy coding,
+no pixel transfer. ``estimate=True`` orders the probes by ``distortion_sweep``'s prediction and never
+decides; the default bisects (measured: guiding saves no probes). The blobs are those of ``step=`` at the index found, byte for byte (I17Q, with ``tile``
+I17T): encoder-side only. A target index 0 misses raises; ``psnr`` with another rate option, ``rdo``
+or ``step_offsets`` raises (the last two: not built). No claim is made about the rate–distortion
+trade away from Δ = 1.
+
 Region decode. ``decompress_region(blob, box)`` returns the pixels of ``box`` = (x0, y0, x1, y1)
 (half-open, inside the image), byte for byte the crop of the full decode, from the tiles it needs
 alone. The synthesis is deconv 5×5/s2/p2, IGDN, deconv 5×5/s2/p2, IGDN, deconv 9×9/s4/p4; IGDN is
@@ -109,13 +122,13 @@ streams are decoded into a compact latent, which is dequantised and synthesised 
 its own, and ``image_egress`` runs on the crop.
 
     python -m iclr_17_compression_amd.codec encode IN.png OUT.i17c --weights CKPT [--N 192]
-                                            [--step S | --max-bytes B | --bpp R]
+                                            [--step S | --max-bytes B | --bpp R | --psnr T]
                                             [--roi X0,Y0,X1,Y1,OFF ...] [--block G] [--rdo L]
                                             [--tile T]
     python -m iclr_17_compression_amd.codec decode IN.i17c OUT.png --weights CKPT
                                             [--region X0,Y0,X1,Y1]
     python -m iclr_17_compression_amd.codec eval IMG... --weights CKPT [--ms-ssim] [--steps 4,8,12]
-                                            [--rdo L]
+                                            [--rdo L] [--psnr T]
 """
 from __future__ import annotations
 
@@ -224,6 +237,112 @@ def encode_to_budget(chosen: Sequence[int], budgets: Sequence[Optional[int]], en
                     again.append(k)
         todo = sorted(again)
     return blobs, reencodes
+
+
+# ------------------------------------------------------------------------------ quality targets
+MAX_PROBES = 8    # per image: 6 bisect the 33 outcomes, 2 more are the guided probes'
+
+# one image of a quality search: its name in messages, the target in dB, its size and sse_limit
+QualityTarget = namedtuple("QualityTarget", "label psnr H W limit")
+# search_quality's answer, one entry per image: the ladder index, the probes spent, the SSE
+# measured at the index, and the guided search's first guess (None: none was made)
+QualityResult = namedtuple("QualityResult", "indices probes sse guesses")
+
+
+def psnr_value(psnr) -> float:
+    """A PSNR target in dB checked on the host: a real number, not a bool, finite and > 0."""
+    if isinstance(psnr, bool) or not isinstance(psnr, (int, float, np.integer, np.floating)):
+        raise Iclr17Error(f"iclr17: codec: psnr must be a real number (got {psnr!r})")
+    t = float(psnr)
+    if not (math.isfinite(t) and t > 0.0):
+        raise Iclr17Error(f"iclr17: codec: psnr must be finite and > 0 (got {psnr!r})")
+    return t
+
+
+def sse_limit(H: int, W: int, psnr) -> int:
+    """The largest integer SSE of an 8-bit H×W RGB image that still reaches ``psnr`` dB:
+    ⌊255²·3·H·W·10^(−psnr/10)⌋, evaluated in float64. A ladder index *passes* when the integer SSE
+    of its 8-bit decode is ≤ this; nothing is decided on a rounded dB value."""
+    t = psnr_value(psnr)
+    if H < 1 or W < 1:
+        raise Iclr17Error(f"iclr17: codec: image size {H}x{W} must be at least 1x1")
+    return int(math.floor(255.0 ** 2 * 3.0 * float(H) * float(W) * 10.0 ** (-t / 10.0)))
+
+
+def _psnr_of(sse: int, H: int, W: int) -> float:
+    return 10.0 * math.log10(255.0 ** 2 * 3 * H * W / sse) if sse else math.inf
+
+
+def _guided_guess(seed, limit: int, sse0: int) -> int:
+    """The coarsest index the calibrated prediction passes, −1 when none: the prediction is
+    base + seed[s] with base = max(0, SSE(UNIT_STEP) − seed[UNIT_STEP])."""
+    base = max(0.0, float(sse0) - float(seed[UNIT_STEP]))
+    ok = [s for s in range(STEPS) if base + float(seed[s]) <= limit]
+    return max(ok) if ok else -1
+
+
+def search_quality(probe, n: int, seeds=None, targets=None) -> QualityResult:
+    """The search of a quality target for ``n`` images (a pure host function: the measuring is
+    ``probe``). ``targets``: one ``QualityTarget`` per image. Per image the bracket L < F holds an
+    index that passed (L, −1 at first: virtual) and one that failed (F, 32 at first: virtual).
+    Every round calls ``probe(members, indices)`` once for all unfinished images (ascending
+    positions), one index per image strictly inside its bracket, gets their integer SSEs back and
+    moves L (SSE ≤ limit) or F. An image is done at F == L + 1: L is its answer, and L == −1
+    raises Iclr17Error with the PSNR reached at index 0. Nothing assumes the SSE monotone along the
+    ladder: the answer passed, and it is index 31 or its coarser neighbour was measured failing.
+
+    The probe index is the bracket's midpoint ⌊(L + F)/2⌋: 6 probes at most. With ``seeds[k]`` (32
+    predicted SSE contributions of the quantiser, 255²·``distortion_sweep``'s row; None: plain
+    bisection) image k first probes UNIT_STEP, then the coarsest index that the prediction
+    calibrated on that probe passes (``_guided_guess``, moved inside the bracket), then that
+    index's neighbour on the side of the boundary, then bisects: ``MAX_PROBES`` = 8 at most. An
+    image's sequence depends on its own seed, limit and measurements alone."""
+    if targets is None or len(targets) != n or (seeds is not None and len(seeds) != n):
+        raise Iclr17Error(f"iclr17: codec: search_quality takes one target (and seed) per image "
+                          f"for {n} images")
+    lo, hi = [-1] * n, [STEPS] * n
+    seen: List[Dict[int, int]] = [{} for _ in range(n)]
+    guesses: List[Optional[int]] = [None] * n
+    last: List[Optional[int]] = [None] * n      # the guided probes' previous index
+
+    def next_index(k: int) -> int:
+        L, F = lo[k], hi[k]
+        seed = None if seeds is None else seeds[k]
+        if seed is not None:
+            if not seen[k]:
+                return UNIT_STEP
+            if len(seen[k]) == 1:
+                g = guesses[k] = _guided_guess(seed, targets[k].limit, seen[k][UNIT_STEP])
+                return min(max(g, L + 1), F - 1)
+            if len(seen[k]) == 2 and last[k] is not None:
+                c = last[k] + 1 if lo[k] == last[k] else last[k] - 1
+                if L < c < F:
+                    return c
+        return (L + F) // 2
+
+    todo = list(range(n))
+    while todo:
+        indices = [next_index(k) for k in todo]
+        sses = probe(list(todo), list(indices))
+        if len(sses) != len(todo):
+            raise Iclr17Error("iclr17: codec: search_quality: the probe returned "
+                              f"{len(sses)} sums for {len(todo)} images")
+        for k, s, e in zip(todo, indices, sses):
+            if not lo[k] < s < hi[k] or len(seen[k]) >= MAX_PROBES:
+                raise Iclr17Error("iclr17: codec: search_quality: probe outside its bracket or cap")
+            seen[k][s] = int(e)
+            last[k] = s
+            if int(e) <= targets[k].limit:
+                lo[k] = s
+            else:
+                hi[k] = s
+        todo = [k for k in todo if hi[k] > lo[k] + 1]
+    for k, t in enumerate(targets):
+        if lo[k] < 0:
+            raise Iclr17Error(f"iclr17: codec: {t.label} cannot reach {t.psnr:g} dB: the finest step "
+                              f"(index 0) gives {_psnr_of(seen[k][0], t.H, t.W):.4f} dB")
+    return QualityResult(list(lo), [len(v) for v in seen], [seen[k][lo[k]] for k in range(n)],
+                         guesses)
 
 
 def blob_overhead(P: int) -> int:
@@ -582,10 +701,18 @@ def rdo_value(rdo) -> float:
     return lam
 
 
+PSNR_WITH_RDO = ("iclr17: codec: psnr with rdo: a quality target over rate–distortion optimised "
+                 "levels is not built")
+PSNR_WITH_MAP = ("iclr17: codec: psnr with step_offsets / a step map: a quality target over "
+                 "per-block steps is not built")
+
+
 def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None, rdo=None,
-                 tile=None):
+                 tile=None, psnr=None):
     """The rate options of ``compress_images`` for ``n`` images, checked on the host before any
-    device use → None (the plain path), ("step", index) or ("budget", per-image values, is_bpp).
+    device use → None (the plain path), ("step", index), ("budget", per-image values, is_bpp) or,
+    for ``psnr`` (a quality target in dB, a scalar or one value per image; not with another rate
+    option, ``rdo`` or ``step_offsets``; with ``tile``), ("quality", per-image values).
     At most one option; a budget is a scalar or one value per image. ``step_offsets`` goes with
     any one of them, the option then giving the base index; alone it means the unit step. So does
     ``rdo`` (``rdo_value`` checks it); ``rdo`` with ``step_offsets`` raises. ``tile`` (the tile
@@ -602,10 +729,24 @@ def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None,
         rdo_value(rdo)
         if step_offsets is not None:
             raise Iclr17Error(RDO_WITH_MAP)
-    given = [k for k, v in (("step", step), ("max_bytes", max_bytes), ("bpp", bpp)) if v is not None]
+    given = [k for k, v in (("step", step), ("max_bytes", max_bytes), ("bpp", bpp), ("psnr", psnr))
+             if v is not None]
     if len(given) > 1:
         raise Iclr17Error(f"iclr17: codec: {' and '.join(given)} given together (at most one of "
-                          "step, max_bytes, bpp)")
+                          f"step, max_bytes, bpp{'' if psnr is None else ', psnr'})")
+    if psnr is not None:
+        if isinstance(psnr, (list, tuple)):     # element by element: an array would turn a bool
+            per = list(psnr)                    # among floats into 1.0
+        else:
+            per = [psnr] * n if np.ndim(psnr) == 0 else list(np.asarray(psnr).reshape(-1))
+        if len(per) != n:
+            raise Iclr17Error(f"iclr17: codec: psnr has {len(per)} values for {n} images")
+        per = [psnr_value(v.item() if isinstance(v, np.generic) else v) for v in per]
+        if rdo is not None:
+            raise Iclr17Error(PSNR_WITH_RDO)
+        if step_offsets is not None:
+            raise Iclr17Error(PSNR_WITH_MAP)
+        return "quality", per
     if not given:
         return None if step_offsets is None and rdo is None else ("step", UNIT_STEP)
     if step is not None:
@@ -620,14 +761,67 @@ def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None,
     return "budget", per, bpp is not None
 
 
+# Plain bisection: measured on trained weights the guided order does not lower the mean probe count
+# (DESIGN.md §0l), so ``estimate=True`` is an option and not the default.
+DEFAULT_ESTIMATE = False
+
+
+def quality_seeds(net, y) -> np.ndarray:
+    """``search_quality``'s seeds of a latent batch: 255²·``net.distortion_sweep`` at the 32 ladder
+    indices, float64 [B, 32] on the host — the SSE in 8-bit units that the linearised synthesis
+    predicts the quantiser alone adds."""
+    return 255.0 ** 2 * net.distortion_sweep(y, latent=True).cpu().numpy()
+
+
+def quality_probe(net, y, packed, offsets, shapes):
+    """``search_quality``'s probe of one canvas batch: ``y`` its NHWC latent, ``packed`` /
+    ``offsets`` / ``shapes`` the uploaded originals as ``upload_packed`` returns them. A call
+    quantises every member at its own index (kernels.quantise_steps), runs the synthesis of the
+    current precision mode as ``decompress`` does and sums the squared 8-bit error on the device
+    (kernels.image_sse): no entropy coding, no 8-bit pixels, and 8·members + 8 bytes come back.
+    The sums are those of the real decode at that index. Raises as ``quantise_step`` and
+    ``image_egress`` do (in h3: ``H3_RANGE_MESSAGE``)."""
+    from . import chain
+    device = y.device
+    B = y.shape[0]
+    Hc, Wc = canvas(*shapes[0])
+    desc = kernels._image_desc("image_sse", packed.numel(), offsets, shapes, (Hc, Wc)).to(device)
+    ladder = torch.tensor([step_size(s) for s in range(STEPS)], dtype=torch.float32, device=device)
+
+    def probe(members, indices):
+        pick = torch.tensor(members, device=device)
+        whole = len(members) == B
+        sel = y if whole else y[pick]
+        steps_dev = ladder[torch.tensor(indices, device=device)]
+        _, y_deq, qstatus = kernels.quantise_steps_device(sel, steps_dev, want_hat=False)
+        m = chain.MODES[kernels.precision()]
+        clipped, _, _ = m.synthesis(net.Decoder, y_deq, m.latent_operand(y_deq), None, False, False,
+                                    None, False)
+        buf, _, _, spare = kernels.image_sse_device(clipped, None, None, packed,
+                                                    desc if whole else desc[pick].contiguous())
+        spare.copy_(qstatus)
+        host = buf.cpu()
+        n = len(members)
+        words = host[8 * n:].view(torch.int32)
+        kernels._step_status(words[1:2], "quantise_steps")
+        if int(words[0]):
+            if kernels.precision() == "h3":
+                raise Iclr17Error(kernels.H3_RANGE_MESSAGE)
+            raise Iclr17Error("iclr17: image_sse: non-finite reconstruction")
+        return [int(v) for v in host[:8 * n].view(torch.int64)]
+
+    return probe
+
+
 def compress_images(net, images, max_batch: int = 64,
                     streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                     K: int = kernels.ENTROPY_K, step: Optional[int] = None, max_bytes=None,
                     bpp=None, stats: Optional[dict] = None, step_offsets=None,
                     block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None,
-                    tile: Optional[int] = None) -> List[bytes]:
+                    tile: Optional[int] = None, psnr=None, estimate: bool = DEFAULT_ESTIMATE
+                    ) -> List[bytes]:
     imgs = [as_u8_hwc(im) for im in images]
-    request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets, rdo, tile)
+    request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets, rdo, tile, psnr)
     how = {} if rdo is None else {"rdo": rdo, "rdo_weights": rdo_weights}
     per_image = None
     if step_offsets is not None:
@@ -640,6 +834,7 @@ def compress_images(net, images, max_batch: int = 64,
         for i, (im, v) in enumerate(zip(imgs, request[1])):
             budgets[i] = int(math.floor(float(v) * im.shape[0] * im.shape[1] / 8)) if request[2] else int(v)
     reencodes = [0] * len(imgs)
+    probes, sses = [0] * len(imgs), [None] * len(imgs)
     for idx in group_by_canvas([im.shape[:2] for im in imgs], max_batch):
         group = [imgs[i] for i in idx]
         packed, offsets, shapes = upload_packed(group, device)
@@ -664,6 +859,14 @@ def compress_images(net, images, max_batch: int = 64,
             overhead = tiled_blob_overhead(P, *shapes[0], tile)   # one canvas: one tile grid
         if request[0] == "step":
             chosen = [request[1]] * len(idx)
+        elif request[0] == "quality":
+            targets = [QualityTarget(f"image {i} ({H}x{W})", request[1][i], H, W,
+                                     sse_limit(H, W, request[1][i])) for i, (H, W) in zip(idx, shapes)]
+            found = search_quality(quality_probe(net, y, packed, offsets, shapes), len(idx),
+                                   quality_seeds(net, y) if estimate else None, targets)
+            chosen = found.indices
+            for k, i in enumerate(idx):
+                probes[i], sses[i] = found.probes[k], found.sse[k]
         else:
             est = (net.rate_sweep(y, latent=True, **how) if offs is None
                    else net.rate_sweep_offsets(y, offs, block)).cpu().numpy()
@@ -696,6 +899,8 @@ def compress_images(net, images, max_batch: int = 64,
             blobs[i], reencodes[i] = blob, n
     if stats is not None:
         stats["reencodes"] = reencodes
+        if request is not None and request[0] == "quality":
+            stats["probes"], stats["sse"] = probes, sses
     return blobs
 
 
@@ -800,11 +1005,12 @@ def decode_region(net, blob, box, stats: Optional[dict] = None) -> np.ndarray:
 def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
                     step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
                     block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None,
-                    tile: Optional[int] = None) -> List[dict]:
+                    tile: Optional[int] = None, psnr=None,
+                    estimate: bool = DEFAULT_ESTIMATE) -> List[dict]:
     imgs = [as_u8_hwc(im) for im in images]
     blobs = compress_images(net, imgs, max_batch=max_batch, step=step, max_bytes=max_bytes, bpp=bpp,
                             step_offsets=step_offsets, block=block, rdo=rdo, rdo_weights=rdo_weights,
-                            tile=tile)
+                            tile=tile, psnr=psnr, estimate=estimate)
     recons, sses = decode_groups(net, blobs, max_batch, refs=imgs)
     device = next(net.parameters()).device
     res = []
@@ -870,7 +1076,8 @@ def _region(text: str) -> Tuple[int, int, int, int]:
     return box
 
 
-def main(argv: Optional[Sequence[str]] = None) -> int:
+def build_parser() -> argparse.ArgumentParser:
+    """The command line's parser (no device use)."""
     common = argparse.ArgumentParser(add_help=False)
     common.add_argument("--weights", required=True, help="checkpoint (model.load_model)")
     common.add_argument("--N", type=int, default=192, help="channel count of the checkpoint")
@@ -885,6 +1092,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     rate.add_argument("--step", type=int, default=None, help="ladder index 0..31 (8: the unit step)")
     rate.add_argument("--max-bytes", type=int, default=None, help="byte budget of the output file")
     rate.add_argument("--bpp", type=float, default=None, help="budget in bits per pixel of the file")
+    rate.add_argument("--psnr", type=float, default=None, metavar="T",
+                      help="quality target in dB: the coarsest ladder index found whose 8-bit "
+                           "decode reaches T (not with --rdo or --roi)")
     enc.add_argument("--roi", action="append", default=None, metavar="X0,Y0,X1,Y1,OFF",
                      help="a pixel box whose blocks get the ladder offset OFF (negative: finer); "
                           "repeatable, the finest offset wins where boxes overlap")
@@ -910,7 +1120,19 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                                                   "and step, and a mean per step")
     ev.add_argument("--rdo", type=float, default=None, metavar="L",
                     help="rate-distortion optimised quantisation with lambda L >= 0")
-    args = ap.parse_args(argv)
+    ev.add_argument("--psnr", type=float, default=None, metavar="T",
+                    help="quality target in dB per image (not with --steps or --rdo)")
+    return ap
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    args = build_parser().parse_args(argv)
+    if getattr(args, "psnr", None) is not None:   # before the device is touched
+        rate_request(1, step=getattr(args, "step", None), rdo=args.rdo, psnr=args.psnr,
+                     step_offsets=[None] if getattr(args, "roi", None) else None)
+        if getattr(args, "steps", None):
+            raise Iclr17Error("iclr17: codec: step and psnr given together (at most one of step, "
+                              "max_bytes, bpp, psnr)")
     net = _model(args)
     with kernels.precision_scope(args.precision or kernels.precision()):
         if args.cmd == "encode":
@@ -919,7 +1141,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 roi = {"step_offsets": [roi_offsets(*image.shape[:2], _boxes(args.roi), args.block)],
                        "block": args.block}
             blob = net.compress_images([image], step=args.step, max_bytes=args.max_bytes,
-                                       bpp=args.bpp, rdo=args.rdo, tile=args.tile, **roi)[0]
+                                       bpp=args.bpp, rdo=args.rdo, tile=args.tile,
+                                       psnr=args.psnr, **roi)[0]
             with open(args.output, "wb") as f:
                 f.write(blob)
         elif args.cmd == "decode":
@@ -936,14 +1159,17 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             steps = [int(t) for t in args.steps.split(",")] if args.steps else [None]
             for step in steps:
                 rows = net.evaluate_images(imgs, want_msssim=args.ms_ssim, step=step,
-                                           rdo=args.rdo)
+                                           rdo=args.rdo, psnr=args.psnr)
                 tag = {} if step is None else {"step": step}
+                if args.psnr is not None:
+                    tag["psnr"] = args.psnr
                 if args.rdo is not None:
                     tag["rdo"] = args.rdo
                 for p, im, r in zip(args.images, imgs, rows):
                     print(json.dumps({"name": p, **tag, "H": im.shape[0], "W": im.shape[1],
                                       "bytes": r["bytes"], "bpp": r["bpp"], "psnr_u8": r["psnr_u8"],
-                                      "ms_ssim": r.get("ms_ssim")}))
+                                      "ms_ssim": r.get("ms_ssim"),
+                                      **({} if args.psnr is None else {"index": r["step"]})}))
                 ms = [r["ms_ssim"] for r in rows if r.get("ms_ssim") is not None]
                 print(json.dumps({"name": "mean", **tag, "images": len(rows),
                                   "bpp": float(np.mean([r["bpp"] for r in rows])),

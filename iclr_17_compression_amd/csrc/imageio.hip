@@ -4,6 +4,7 @@
 //           the image at the top left of the Hc×Wc canvas, bottom and right edges replicated)
 //   egress: dst_b[i][j][c] = (uint8) rintf(clamp(recon[b,c,i,j], 0, 1) · 255) for the image's own
 //           H_b×W_b region, optionally Σ (dst − ref)² per image (int64) and a non-finite status
+//   sse:    the egress's sums and status alone, no pixel written (the probe of a quality target)
 // The reference has no such step (train.py feeds fp32 crops); tests/test_gpu_image_io.py holds the
 // contract as torch expressions.
 //
@@ -102,7 +103,8 @@ __global__ void __launch_bounds__(64 * kRows) image_ingest_kernel(
   for (int c = 0; c < 3; ++c) *(f4*)(o + c * plane) = v[c];
 }
 
-template <bool REF>
+// WRITE = false is image_sse: the same pixels and the same sums, dst never touched.
+template <bool REF, bool WRITE = true>
 __global__ void __launch_bounds__(64 * kRows) image_egress_kernel(
     const float* __restrict__ recon, const long* __restrict__ desc, int Hc, int Wc,
     unsigned char* __restrict__ dst, const unsigned char* __restrict__ ref,
@@ -161,7 +163,7 @@ __global__ void __launch_bounds__(64 * kRows) image_egress_kernel(
         }
       }
     }
-    unstage_bytes(dst + seg, 3 * ncols, pix[wave], lane);
+    if constexpr (WRITE) unstage_bytes(dst + seg, 3 * ncols, pix[wave], lane);
   }
   if (__any(bad) && lane == 0) atomicOr(status, 1);
   if constexpr (REF) {
@@ -226,6 +228,24 @@ int iclr17_image_egress_u8(const float* recon, const int64_t* desc, int B, int H
                        (const long*)desc, Hc, Wc, (unsigned char*)dst, (const unsigned char*)nullptr,
                        (unsigned long long*)nullptr, (int*)status);
   return check_launch("image_egress");
+}
+
+int iclr17_image_sse_u8(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
+                        const uint8_t* ref, int64_t* sse, int32_t* status, void* stream) {
+  ICLR17_REQUIRE(recon && desc && ref && sse && status, ICLR17_EINVAL, "image_sse: null pointer");
+  if (int rc = check_canvas("image_sse", B, Hc, Wc)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+  if (e == hipSuccess) e = hipMemsetAsync(sse, 0, (size_t)B * sizeof(int64_t), st);
+  if (e != hipSuccess) {
+    set_error(ICLR17_ELAUNCH, "image_sse: %s", hipGetErrorString(e));
+    return ICLR17_ELAUNCH;
+  }
+  const dim3 grid((Wc + kCols - 1) / kCols, Hc / kRows, B);
+  hipLaunchKernelGGL((image_egress_kernel<true, false>), grid, dim3(64 * kRows), 0, st, recon,
+                     (const long*)desc, Hc, Wc, (unsigned char*)nullptr,
+                     (const unsigned char*)ref, (unsigned long long*)sse, (int*)status);
+  return check_launch("image_sse");
 }
 
 }  // extern "C"

@@ -1271,6 +1271,78 @@ def rate_sweep(y: Tensor, rate_packed: Tensor, steps: Sequence[float]) -> Tensor
     return bits
 
 
+# ----------------------------------------------------------- quality targets (csrc/quality.hip)
+def _steps_dev(y: Tensor, steps_dev: Tensor, what: str) -> Tensor:
+    """The [B] fp32 step sizes of a batch ``y`` on its device, each finite and > 0 (checked here:
+    the library sees device memory)."""
+    _check(y, "latent")
+    _check(steps_dev, "step sizes", 1)
+    if y.dim() < 1 or steps_dev.numel() != y.shape[0] or steps_dev.device != y.device:
+        raise Iclr17Error(f"iclr17: {what}: {steps_dev.numel()} step sizes for a batch of "
+                          f"{y.shape[0] if y.dim() else 0} on the latent's device")
+    if y.numel() == 0:
+        raise Iclr17Error(f"iclr17: {what}: empty latent")
+    if not bool((torch.isfinite(steps_dev) & (steps_dev > 0)).all()):
+        raise Iclr17Error(f"iclr17: {what}: a step is not finite and positive")
+    return steps_dev.contiguous()
+
+
+def quantise_steps_device(y: Tensor, steps_dev: Tensor, want_hat: bool = True,
+                          status: Optional[Tensor] = None):
+    """``quantise_steps`` without the status read: → (ŷ | None, Δ_b·ŷ, status int32 [1] on the
+    device, ``quantise_step``'s bits). ``status`` (zeroed by the caller) is used when given."""
+    steps_dev = _steps_dev(y, steps_dev, "quantise_steps")
+    y = y.contiguous()
+    B = y.shape[0]
+    y_hat = torch.empty_like(y) if want_hat else None
+    y_deq = torch.empty_like(y)
+    if status is None:
+        status = torch.zeros(1, device=y.device, dtype=torch.int32)
+    call("iclr17_quantise_steps", _p(y), B, y.numel() // B, _p(steps_dev), _p(y_hat), _p(y_deq),
+         _p(status), _stream(y))
+    return y_hat, y_deq, status
+
+
+def quantise_steps(y: Tensor, steps_dev: Tensor, want_hat: bool = True):
+    """``quantise_step`` with a step per image: y fp32 [B, …] and steps_dev fp32 [B] on the device
+    (each finite and > 0) → (ŷ = rint(y/Δ_b) or None without ``want_hat``, Δ_b·ŷ); per image bit
+    for bit ``quantise_step(y[b], Δ_b)``. Raises as it does on a NaN and on |ŷ| > 32767."""
+    y_hat, y_deq, status = quantise_steps_device(y, steps_dev, want_hat)
+    _step_status(status, "quantise_steps")
+    return y_hat, y_deq
+
+
+def distortion_sweep(y: Tensor, weights: Tensor, steps: Sequence[float]) -> Tensor:
+    """y fp32 NHWC [B,h,w,N], channel weights (fp32 [N] on the device, finite and ≥ 0) and 1..32
+    step sizes → float64 [B, S]: E[b][s] = Σ weights[c]·e², e = fma(Δ_s, rint(v/Δ_s), −v), the
+    weighted squared quantisation error of each image at each step from one read of y. Bitwise
+    reproducible and independent of the batch."""
+    B, h, w, N, weights = _channel_weights(y, weights, "distortion_sweep", "weights")
+    ds = [_step_value(s, "distortion_sweep") for s in steps]
+    S = len(ds)
+    if not 1 <= S <= SWEEP_MAX_STEPS:
+        raise Iclr17Error(f"iclr17: distortion_sweep: {S} steps (1..{SWEEP_MAX_STEPS})")
+    T = query("iclr17_rate_sweep_partials", h, w, N)
+    partial = torch.empty(B * S * max(T, 1), device=y.device, dtype=torch.float64)
+    out = torch.empty(B, S, device=y.device, dtype=torch.float64)
+    arr = (ctypes.c_float * S)(*ds)
+    call("iclr17_distortion_sweep", _p(y.contiguous()), B, h, w, N, _p(weights),
+         ctypes.cast(arr, ctypes.c_void_p), S, _p(partial), _p(out), _stream(y))
+    return out
+
+
+def _channel_weights(y: Tensor, lam: Tensor, what: str, name: str):
+    _check(y, "latent", 4)
+    B, h, w, N = y.shape
+    if not isinstance(lam, torch.Tensor) or lam.dtype != torch.float32 or lam.device != y.device \
+            or tuple(lam.shape) != (N,):
+        raise Iclr17Error(f"iclr17: {what}: {name} must be an fp32 tensor of shape [{N}] on the "
+                          "latent's device")
+    if not bool((torch.isfinite(lam) & (lam >= 0)).all()):
+        raise Iclr17Error(f"iclr17: {what}: {name} must be finite and >= 0")
+    return B, h, w, N, lam.contiguous()
+
+
 # ------------------------------------- rate–distortion optimised quantisation (csrc/rdoq.hip)
 def _rdo_args(y: Tensor, rate_packed: Tensor, lam: Tensor, what: str):
     _check(y, "latent", 4)
@@ -1735,6 +1807,46 @@ def image_egress(recon: Tensor, offsets, shapes, ref: Optional[Tensor] = None):
             raise Iclr17Error(H3_RANGE_MESSAGE)
         raise Iclr17Error("iclr17: image_egress: non-finite reconstruction")
     return host[8 * B + 8:], (host[:8 * B].view(torch.int64) if sse is not None else None)
+
+
+def image_sse_device(recon: Tensor, offsets, shapes, ref: Tensor, desc: Optional[Tensor] = None):
+    """``image_sse`` without the transfer: → (buffer, sse int64 [B], status int32 [1], spare int32
+    [1]), views of the one uint8 ``buffer`` of 8·B + 8 bytes on the device; ``spare`` is zeroed
+    for a caller's own status word (a probe puts the quantiser's there), so one copy of the buffer
+    brings everything to the host. ``desc``: the checked descriptors of an earlier call with the
+    same offsets, shapes and canvas, already on the device."""
+    _check(recon, "reconstruction", 4)
+    B, C, Hc, Wc = recon.shape
+    if C != 3:
+        raise Iclr17Error(f"iclr17: image_sse takes a [B,3,Hc,Wc] reconstruction (got {C} channels)")
+    _check_u8(ref, "reference bytes")
+    if desc is None:
+        desc = _image_desc("image_sse", ref.numel(), offsets, shapes, (Hc, Wc)).to(recon.device)
+    if tuple(desc.shape) != (B, 4):
+        raise Iclr17Error(f"iclr17: image_sse: {desc.shape[0]} images for a batch of {B}")
+    ref = _check_u8_gpu(ref, "reference bytes")
+    buf = torch.zeros(8 * B + 8, device=recon.device, dtype=torch.uint8)
+    sse = buf[:8 * B].view(torch.int64)
+    status = buf[8 * B:8 * B + 4].view(torch.int32)
+    spare = buf[8 * B + 4:].view(torch.int32)
+    call("iclr17_image_sse_u8", _p(recon.contiguous()), _p(desc), B, Hc, Wc, _p(ref), _p(sse),
+         _p(status), _stream(recon))
+    return buf, sse, status, spare
+
+
+def image_sse(recon: Tensor, offsets, shapes, ref: Tensor):
+    """``image_egress(recon, offsets, shapes, ref)``'s sums alone: the per-image Σ (dst − ref)² of
+    the 8-bit image that ``image_egress`` would write (int64 [B] on the HOST, exact), without
+    writing or moving a pixel. Raises as ``image_egress`` does on a non-finite value inside an
+    image."""
+    buf, _, _, _ = image_sse_device(recon, offsets, shapes, ref)
+    host = buf.cpu()
+    B = recon.shape[0]
+    if int(host[8 * B:8 * B + 4].view(torch.int32).item()):
+        if precision() == "h3":
+            raise Iclr17Error(H3_RANGE_MESSAGE)
+        raise Iclr17Error("iclr17: image_sse: non-finite reconstruction")
+    return host[:8 * B].view(torch.int64)
 
 
 # ------------------------------------------------------------------------------ modules

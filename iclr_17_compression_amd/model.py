@@ -253,16 +253,58 @@ class ImageCompressor(nn.Module):
         cache = self.__dict__.setdefault("_codec_cache", PackCache())
 
         def build() -> torch.Tensor:
+            g = self.synthesis_gains_raw()
+            return (g / g.mean()).contiguous()
+
+        return cache.get("synthesis_gains", [sd[k] for k in keys], build)
+
+    @torch.no_grad()
+    def synthesis_gains_raw(self) -> torch.Tensor:
+        """``synthesis_gains`` before its division by the mean: fp32 [N] on the device, g_c in
+        squared pixel units (of the [0, 1] range) per unit squared latent error, the default
+        weights of ``distortion_sweep``. Cached until a parameter changes."""
+        sd = self.state_dict()
+        keys = sorted(sd)
+        cache = self.__dict__.setdefault("_codec_cache", PackCache())
+
+        def build() -> torch.Tensor:
             N = self.out_channel_N
             dev = next(self.parameters()).device
             probe = torch.zeros(N + 1, N, 8, 8, device=dev, dtype=torch.float32)
             probe[torch.arange(N), torch.arange(N), 4, 4] = 1.0
             with kernels.precision_scope("x6"):
                 out = self.Decoder(probe)
-            g = ((out[:N] - out[N:]) ** 2).sum(dim=(1, 2, 3))
-            return (g / g.mean()).contiguous()
+            return ((out[:N] - out[N:]) ** 2).sum(dim=(1, 2, 3)).contiguous()
 
-        return cache.get("synthesis_gains", [sd[k] for k in keys], build)
+        return cache.get("synthesis_gains_raw", [sd[k] for k in keys], build)
+
+    @torch.no_grad()
+    def distortion_sweep(self, x_or_y: torch.Tensor, steps=range(32), weights=None,
+                         latent: Optional[bool] = None) -> torch.Tensor:
+        """The weighted squared quantisation error of every image's latent at every ladder step of
+        ``steps`` (codec.step_size indices, at most 32): float64 [B, S] on the device, E[b][s] =
+        Σ w_c·(Δ_s·rint(y/Δ_s) − y)², from one analysis pass and one read of y
+        (kernels.distortion_sweep). The argument as ``rate_sweep``'s; ``weights``: [N] channel
+        weights, finite and ≥ 0, default ``synthesis_gains_raw`` — E is then the linearised
+        synthesis's prediction of the squared pixel error a step adds (it orders
+        the probes of a quality target and decides nothing)."""
+        from . import codec
+        kernels._check(x_or_y, "image or latent", 4)
+        if latent is None:
+            latent = x_or_y.shape[1] != 3
+        y = x_or_y if latent else self.latents(x_or_y)
+        N = self.out_channel_N
+        if y.shape[3] != N:
+            raise kernels.Iclr17Error(f"iclr17: distortion_sweep: the latent has {y.shape[3]} "
+                                      f"channels, the model {N}")
+        if weights is None:
+            g = self.synthesis_gains_raw()
+        else:
+            g = torch.as_tensor(weights, dtype=torch.float32).to(y.device)
+            if tuple(g.shape) != (N,):
+                raise kernels.Iclr17Error(f"iclr17: distortion_sweep: weights must have shape "
+                                          f"[{N}] (got {tuple(g.shape)})")
+        return kernels.distortion_sweep(y, g.contiguous(), [codec.step_size(s) for s in steps])
 
     def _rdo_lam(self, rdo, rdo_weights, what: str) -> torch.Tensor:
         """lam[c] = rdo · weight_c for kernels.quantise_rdo / rate_sweep_rdo: fp32 [N] on the
@@ -489,7 +531,7 @@ class ImageCompressor(nn.Module):
                         K: int = kernels.ENTROPY_K, step: Optional[int] = None,
                         max_bytes=None, bpp=None, stats: Optional[dict] = None,
                         step_offsets=None, block: int = 4, rdo=None, rdo_weights=None,
-                        tile: Optional[int] = None):
+                        tile: Optional[int] = None, psnr=None, estimate: Optional[bool] = None):
         """8-bit images of any sizes ≥ 1×1 (a sequence of uint8 HWC RGB arrays, numpy or torch) →
         one self-describing blob per image, in input order: codec.py's 28-byte header (true size,
         N, P, K, weights fingerprint) + the image's ``compress`` string. Images are batched by
@@ -524,12 +566,24 @@ class ImageCompressor(nn.Module):
         from the tiles it needs alone. It goes with ``step``, a budget (the tile overhead
         counted) and ``rdo``; alone it codes ``compress``'s own ŷ. These blobs carry the magic
         I17T, a ladder index (8 when no rate option is given) and the tile edge. With
-        ``step_offsets`` it raises (tiled step maps are not built)."""
+        ``step_offsets`` it raises (tiled step maps are not built).
+
+        ``psnr`` (dB, finite and > 0; a scalar or one value per image) is a quality target, the
+        fourth rate option (codec.py, "Quality targets"): each image is coded at the coarsest
+        ladder index found whose 8-bit decode reaches the target, decided on the integer SSE
+        against codec.sse_limit; the index passed, and it is 31 or its coarser neighbour was
+        measured and failed. At most 8 probes per image, each a quantise–synthesis–SSE pass on
+        the device without entropy coding; ``estimate=True`` orders them by
+        ``distortion_sweep``'s prediction, False bisects (None: codec.DEFAULT_ESTIMATE, which is
+        bisection). The blobs are byte for byte those of ``step=`` at the index found (I17Q, or I17T with ``tile``); ``stats`` receives
+        "probes" and "sse" (the SSE at the index) per image. A target above what index 0 reaches
+        raises; with ``rdo`` or ``step_offsets`` it raises (not built)."""
         from . import codec
         return codec.compress_images(self, images, max_batch, streams_per_image, K, step=step,
                                      max_bytes=max_bytes, bpp=bpp, stats=stats,
                                      step_offsets=step_offsets, block=block, rdo=rdo,
-                                     rdo_weights=rdo_weights, tile=tile)
+                                     rdo_weights=rdo_weights, tile=tile, psnr=psnr,
+                                     estimate=codec.DEFAULT_ESTIMATE if estimate is None else estimate)
 
     @torch.no_grad()
     def decompress_images(self, blobs, max_batch: int = 64):
@@ -558,7 +612,8 @@ class ImageCompressor(nn.Module):
     @torch.no_grad()
     def evaluate_images(self, images, want_msssim: bool = False, max_batch: int = 64,
                         step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
-                        block: int = 4, rdo=None, rdo_weights=None, tile: Optional[int] = None):
+                        block: int = 4, rdo=None, rdo_weights=None, tile: Optional[int] = None,
+                        psnr=None, estimate: Optional[bool] = None):
         """The real codec path per image, compress_images then decompress_images, measured on
         the 8-bit decoded image as codecs are reported: a dict per image with ``bytes``, ``bpp`` =
         8·len(blob)/(H·W) (header included, true pixel count), ``sse_u8`` (int), ``psnr_u8`` =
@@ -568,11 +623,14 @@ class ImageCompressor(nn.Module):
         ``step`` / ``max_bytes`` / ``bpp`` / ``step_offsets`` / ``block`` / ``rdo`` /
         ``rdo_weights`` as in ``compress_images``; a mapped blob's row has its base index as
         ``step`` and also ``step_map`` and ``block``; with ``tile`` a row has the blob's ladder
-        index as ``step`` and also ``tile``. Precision as ``decompress_images``."""
+        index as ``step`` and also ``tile``. ``psnr`` / ``estimate`` as in ``compress_images``: the
+        row's ``step`` is the index found. Precision as ``decompress_images``."""
         from . import codec
         return codec.evaluate_images(self, images, want_msssim, max_batch, step=step,
                                      max_bytes=max_bytes, bpp=bpp, step_offsets=step_offsets,
-                                     block=block, rdo=rdo, rdo_weights=rdo_weights, tile=tile)
+                                     block=block, rdo=rdo, rdo_weights=rdo_weights, tile=tile,
+                                     psnr=psnr,
+                                     estimate=codec.DEFAULT_ESTIMATE if estimate is None else estimate)
 
     @torch.no_grad()
     def evaluate(self, x: torch.Tensor, want_y: bool = False,

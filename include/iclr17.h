@@ -300,6 +300,26 @@ int iclr17_rate_sweep_partials(int h, int w, int N);
 int iclr17_rate_sweep(const float* y, int B, int h, int w, int N, const float* rate_packed,
                       const float* steps, int S, double* partial, double* bits, void* stream);
 
+/* ------------------------------------------------------------ quality targets (csrc/quality.hip)
+ * DESIGN.md §0l. */
+/* iclr17_quantise_step with a step per image: y holds B images of per_image elements each, and
+ * element i of image b gives y_hat = rintf(y / steps_dev[b]) and y_deq = steps_dev[b] · y_hat,
+ * per image bit for bit what iclr17_quantise_step writes. steps_dev: device fp32 [B], each finite
+ * and > 0 (the caller checks: the library sees device memory). y_hat may be NULL (not written).
+ * status as there (caller-zeroed). */
+int iclr17_quantise_steps(const float* y, int B, int64_t per_image, const float* steps_dev,
+                          float* y_hat, float* y_deq, int32_t* status, void* stream);
+/* The distortion half of iclr17_rate_sweep: out[b][s] = Σ weights[c] · e² over image b of y (fp32
+ * NHWC [B][h][w][N]) with e = fmaf(steps[s], rintf(v / steps[s]), −v), S ≤ 32 steps from one read
+ * of y. weights: device fp32 [N], each finite and ≥ 0 (the caller checks); steps is a host array,
+ * copied at the call. rate_sweep's chunks and thread map, fp32 per thread and wave, float64 across
+ * waves and chunks in a fixed order, no atomics: bitwise reproducible and independent of the
+ * batch. partial: B · S · iclr17_rate_sweep_partials(h, w, N) doubles of scratch; out: [B][S]
+ * doubles. */
+int iclr17_distortion_sweep(const float* y, int B, int h, int w, int N, const float* weights,
+                            const float* steps, int S, double* partial, double* out,
+                            void* stream);
+
 /* ----------------------------------------- rate–distortion optimised quantisation (csrc/rdoq.hip)
  * An encoder-side choice of the level; the stream and the decoder are unchanged.
  * Per element of channel c at step Δ: t = y/Δ (IEEE fp32 divide), r = rintf(t), candidates r,
@@ -503,6 +523,11 @@ int iclr17_image_ingest_u8(const uint8_t* src, const int64_t* desc, int B, int H
 int iclr17_image_egress_u8(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
                            uint8_t* dst, const uint8_t* ref, int64_t* sse, int32_t* status,
                            void* stream);
+/* iclr17_image_egress_u8's sse and status alone (the probe of a quality target):
+ * the same pixels rintf(clamp·255) compared with ref over each image's own H_b×W_b, the same exact
+ * int64 sums and status bit; no 8-bit pixel is written. ref is required. */
+int iclr17_image_sse_u8(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
+                        const uint8_t* ref, int64_t* sse, int32_t* status, void* stream);
 
 /* train.py:106-112: element-wise gradient clamp to ±grad_clip (≤ 0: none; written back to the
  * gradient) fused with one torch.optim.Adam step (no weight decay, no amsgrad) over n_tensors
