@@ -9,15 +9,29 @@
 // frequencies (each ≥ 1, summing to 2^16).
 //
 // Coder: interleaved rANS, 32-bit states in [2^16, 2^32), 16-bit renormalisation words, 16-bit
-// probability precision. Streams: each image's channels are cut into P contiguous groups, one
-// stream per (image, group), symbols in (channel, row, column) order. One wave codes a stream:
-// lane l owns symbols l, l + 64, … with its own state; a block's renormalisation words are
-// ordered by lane (ballot + prefix count), so the stream stays one word sequence. The encoder
-// writes back to front into its own scratch slot; the offsets scan and the pack kernel then
-// concatenate the streams. The CDF tables are staged in LDS.
+// probability precision. One wave codes a stream: lane l owns symbols l, l + 64, … with its own
+// state; a block's renormalisation words are ordered by lane (ballot + prefix count), so the
+// stream stays one word sequence. The encoder writes back to front into its own scratch slot;
+// the offsets scan and the pack kernel then concatenate the streams.
 //
-// encode_map_kernel / decode_map_kernel are the same coder with a table set per block of latent
-// positions: see "step maps" below.
+// The file has one coder and three layouts.
+//   Body: encode_stream / decode_stream code one stream with one wave. They hold every rule of
+//     the stream format: the classification and escape rule, the order of the sub-rounds, the
+//     word placement, the 64 leading states and the status bits. Nothing else in the file does.
+//   Layout: a small struct that tells the body what a stream is made of: nsym(), the symbol
+//     count, at(i, e), the table row of symbol i and its element e of the latent tensor, and
+//     idle(), any readable row, for the lanes past the end of the encoder's last block; a
+//     layout with kWindow also has walk_down(blk) / walk_up(blk), which the body calls before a
+//     block so the layout can restage its LDS window. Row is a const int* into LDS or a TabRow.
+//       PlainLayout  a stream per (image, channel group), symbols in (channel, row, column)
+//                    order, every channel's table in LDS;
+//       MapLayout    the same streams with a table set per block of latent positions
+//                    (DESIGN.md §0i), the tables in an LDS window or in global memory;
+//       TileLayout   a stream per (image, tile, channel group).
+//   Shell: the six kernels stage tables where their layout does, find their stream, build the
+//     layout and call the body.
+#include <type_traits>
+
 #include "common.h"
 
 namespace iclr17 {
@@ -75,9 +89,10 @@ __device__ __forceinline__ long sym_index(const StreamGeo& g, int b, int grp, in
 // status bits
 enum : int { ST_NONINT = 1, ST_RANGE = 2, ST_OVERRUN = 4, ST_TRAIL = 8 };
 
-// every channel's table into LDS (N·(2K + 3) ints)
+// every channel's table into LDS (N·(2K + 3) ints), by a workgroup of T threads
+template <int T = W>
 __device__ __forceinline__ void load_tables(const int* __restrict__ cum, int n, int* sc) {
-  for (int i = threadIdx.x; i < n; i += W) sc[i] = cum[i];
+  for (int i = threadIdx.x; i < n; i += T) sc[i] = cum[i];
   __syncthreads();
 }
 
@@ -93,36 +108,34 @@ __device__ __forceinline__ int2 lane_rank(bool need, int lane) {
   return make_int2(__popcll(m & ((1ull << lane) - 1ull)), __popcll(m));
 }
 
-// One wave per stream; lane l codes symbols l, l + 64, … with its own state. Blocks of 64
-// symbols are encoded last to first; inside a block the escape payloads go first, then the
-// symbols (the decoder's reverse). Renormalisation words of a (block, sub-round) are placed
-// back to front as a group, lane order ascending, so the decoder reading forward hands each
-// lane its own word. The 64 final states (high word first) lead the stream.
-__global__ void __launch_bounds__(W) encode_kernel(const float* __restrict__ y, StreamGeo g,
-                                                   const int* __restrict__ cum, int K,
-                                                   unsigned short* __restrict__ scratch, long cap,
-                                                   unsigned* __restrict__ lengths,
-                                                   int* __restrict__ status) {
-  extern __shared__ int sc[];
-  const int NS = 2 * K + 2, TS = NS + 1;
-  load_tables(cum, g.N * TS, sc);
-  const int s = blockIdx.x, lane = threadIdx.x;
-  const int b = s / g.P, grp = s - b * g.P;
+// ----------------------------------------------------------------------------- the body
+// Encodes stream s of layout `lay` with the calling wave. Blocks of 64 symbols are encoded last
+// to first; inside a block the escape payloads go first, then the symbols (the decoder's
+// reverse). Renormalisation words of a (block, sub-round) are placed back to front as a group,
+// lane order ascending, so the decoder reading forward hands each lane its own word. The 64
+// final states (high word first) lead the stream.
+template <class L>
+__device__ __forceinline__ void encode_stream(L& lay, int s, int lane, const float* __restrict__ y,
+                                              int K, unsigned short* __restrict__ scratch, long cap,
+                                              unsigned* __restrict__ lengths,
+                                              int* __restrict__ status) {
+  const int NS = 2 * K + 2;
   unsigned short* out = scratch + (long)s * cap;
   long ptr = cap;
   unsigned x = kL;
   int bad = 0;
-  const int nsym = g.cpg * g.HW;
+  const int nsym = lay.nsym();
   const int nblk = (nsym + W - 1) / W;
   for (int blk = nblk - 1; blk >= 0; --blk) {
+    if constexpr (L::kWindow) lay.walk_down(blk);
     const int i = blk * W + lane;
     const bool act = i < nsym;
     int sym = 0, pay = -1;
-    const int* cc = sc;
+    typename L::Row cc = lay.idle();   // an idle lane reads a row it never codes
     if (act) {
-      const long e = sym_index(g, b, grp, i);
+      long e;
+      cc = lay.at(i, e);
       const float v = y[e];
-      cc = sc + (grp * g.cpg + i / g.HW) * TS;
       const float r = rintf(v);
       if (!(r == v)) { bad |= ST_NONINT; sym = K; }   // NaN / non-integer
       else if (fabsf(v) > 32767.f) { bad |= ST_RANGE; sym = K; }
@@ -144,7 +157,7 @@ __global__ void __launch_bounds__(W) encode_kernel(const float* __restrict__ y, 
     }
     // sub-round A: the symbols
     {
-      const unsigned start = (unsigned)cc[sym], f = (unsigned)(cc[sym + 1] - cc[sym]);
+      const unsigned start = (unsigned)cc[sym], f = (unsigned)cc[sym + 1] - start;
       const bool need = act && x >= (f << 16);
       const int2 rc = lane_rank(need, lane);
       if (need) {
@@ -161,6 +174,112 @@ __global__ void __launch_bounds__(W) encode_kernel(const float* __restrict__ y, 
   if (lane == 0) lengths[s] = (unsigned)(cap - ptr);
   bad = wave_or(bad);
   if (lane == 0 && bad) atomicOr(status, bad);
+}
+
+// Decodes the n words at `in` as a stream of layout `lay` with the calling wave. A stream too
+// short for its states makes the whole wave leave, so no barrier of the layout follows.
+template <class L>
+__device__ __forceinline__ void decode_stream(L& lay, int lane, const unsigned short* __restrict__ in,
+                                              long n, int K, float* __restrict__ y,
+                                              int* __restrict__ status) {
+  const int NS = 2 * K + 2;
+  int bad = 0;
+  if (n < 2 * W) {
+    if (lane == 0) atomicOr(status, ST_OVERRUN);
+    return;
+  }
+  unsigned x = ((unsigned)in[2 * lane] << 16) | in[2 * lane + 1];
+  long ptr = 2 * W;
+  auto word = [&](bool need, int& fail) -> unsigned {
+    const int2 rc = lane_rank(need, lane);
+    unsigned w = 0;
+    if (need) {
+      if (ptr + rc.x < n) w = in[ptr + rc.x];
+      else fail |= ST_OVERRUN;
+    }
+    ptr += rc.y;
+    return w;
+  };
+  const int nsym = lay.nsym();
+  const int nblk = (nsym + W - 1) / W;
+  for (int blk = 0; blk < nblk; ++blk) {
+    if constexpr (L::kWindow) lay.walk_up(blk);
+    const int i = blk * W + lane;
+    const bool act = i < nsym;
+    int v = 0;
+    bool esc = false;
+    long e = 0;
+    if (act) {
+      const typename L::Row cc = lay.at(i, e);
+      const unsigned slot = x & 0xffffu;
+      int lo = 0, hi = NS;   // cc[lo] ≤ slot < cc[hi]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned)cc[mid] <= slot) lo = mid; else hi = mid;
+      }
+      const unsigned start = (unsigned)cc[lo], f = (unsigned)cc[lo + 1] - start;
+      x = f * (x >> 16) + slot - start;
+      v = lo - K;
+      esc = lo == NS - 1;
+    }
+    // Sub-round A renormalises after the symbols, sub-round B takes the escape payloads. Where a
+    // lane's words lie follows from the ranks alone, so both loads go out before either is used:
+    // one memory wait per block, not two (profiles/rans_coder_refactor_ab.txt).
+    const bool need = act && x < kL;
+    const unsigned wa = word(need, bad), wb = word(esc, bad);
+    if (need) x = (x << 16) | wa;
+    if (esc) {
+      v = (int)(x & 0xffffu) - 32768;
+      x = (x & 0xffff0000u) | wb;
+    }
+    if (act) y[e] = (float)v;
+  }
+  if (x != kL) bad |= ST_TRAIL;
+  if (lane == 0 && ptr != n) bad |= ST_TRAIL;
+  bad = wave_or(bad);
+  if (lane == 0 && bad) atomicOr(status, bad);
+}
+
+// ----------------------------------------------------------------------------- plain streams
+// Each image's channels are cut into P contiguous groups, one stream per (image, group), symbols
+// in (channel, row, column) order; one wave per workgroup, workgroup s codes stream s.
+struct PlainLayout {
+  using Row = const int*;
+  static constexpr bool kWindow = false;
+  const StreamGeo& g;
+  const int* sc;   // every channel's table, in LDS
+  int TS, b, grp;
+  __device__ __forceinline__ PlainLayout(const StreamGeo& geo, const int* tables, int K, int s)
+      : g(geo), sc(tables), TS(2 * K + 3), b(s / geo.P), grp(s - b * geo.P) {}
+  __device__ __forceinline__ int nsym() const { return g.cpg * g.HW; }
+  __device__ __forceinline__ Row idle() const { return sc; }
+  __device__ __forceinline__ Row at(int i, long& e) const {
+    e = sym_index(g, b, grp, i);
+    return sc + (grp * g.cpg + i / g.HW) * TS;
+  }
+};
+
+__global__ void __launch_bounds__(W) encode_kernel(const float* __restrict__ y, StreamGeo g,
+                                                   const int* __restrict__ cum, int K,
+                                                   unsigned short* __restrict__ scratch, long cap,
+                                                   unsigned* __restrict__ lengths,
+                                                   int* __restrict__ status) {
+  extern __shared__ int sc[];
+  load_tables(cum, g.N * (2 * K + 3), sc);
+  const int s = blockIdx.x;
+  PlainLayout lay(g, sc, K, s);
+  encode_stream(lay, s, threadIdx.x, y, K, scratch, cap, lengths, status);
+}
+
+__global__ void __launch_bounds__(W) decode_kernel(const unsigned short* __restrict__ words,
+                                                   const long* __restrict__ offsets, StreamGeo g,
+                                                   const int* __restrict__ cum, int K,
+                                                   float* __restrict__ y, int* __restrict__ status) {
+  extern __shared__ int sc[];
+  load_tables(cum, g.N * (2 * K + 3), sc);
+  const int s = blockIdx.x;
+  PlainLayout lay(g, sc, K, s);
+  decode_stream(lay, threadIdx.x, words + offsets[s], offsets[s + 1] - offsets[s], K, y, status);
 }
 
 // offsets[0] = 0, offsets[i + 1] = offsets[i] + lengths[i]   (one workgroup; n ≤ a few 10^5)
@@ -201,84 +320,10 @@ __global__ void __launch_bounds__(256) pack_kernel(const unsigned short* __restr
   for (long i = threadIdx.x; i < n; i += 256) words[o + i] = src[i];
 }
 
-__global__ void __launch_bounds__(W) decode_kernel(const unsigned short* __restrict__ words,
-                                                   const long* __restrict__ offsets, StreamGeo g,
-                                                   const int* __restrict__ cum, int K,
-                                                   float* __restrict__ y, int* __restrict__ status) {
-  extern __shared__ int sc[];
-  const int NS = 2 * K + 2, TS = NS + 1;
-  load_tables(cum, g.N * TS, sc);
-  const int s = blockIdx.x, lane = threadIdx.x;
-  const int b = s / g.P, grp = s - b * g.P;
-  const unsigned short* in = words + offsets[s];
-  const long n = offsets[s + 1] - offsets[s];
-  int bad = 0;
-  if (n < 2 * W) {
-    if (lane == 0) atomicOr(status, ST_OVERRUN);
-    return;
-  }
-  unsigned x = ((unsigned)in[2 * lane] << 16) | in[2 * lane + 1];
-  long ptr = 2 * W;
-  auto word = [&](bool need, int& fail) -> unsigned {
-    const int2 rc = lane_rank(need, lane);
-    unsigned w = 0;
-    if (need) {
-      if (ptr + rc.x < n) w = in[ptr + rc.x];
-      else fail |= ST_OVERRUN;
-    }
-    ptr += rc.y;
-    return w;
-  };
-  const int nsym = g.cpg * g.HW;
-  const int nblk = (nsym + W - 1) / W;
-  for (int blk = 0; blk < nblk; ++blk) {
-    const int i = blk * W + lane;
-    const bool act = i < nsym;
-    int v = 0;
-    bool esc = false;
-    if (act) {
-      const int* cc = sc + (grp * g.cpg + i / g.HW) * TS;
-      const unsigned slot = x & 0xffffu;
-      int lo = 0, hi = NS;   // cc[lo] ≤ slot < cc[hi]
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((unsigned)cc[mid] <= slot) lo = mid; else hi = mid;
-      }
-      const unsigned start = (unsigned)cc[lo], f = (unsigned)(cc[lo + 1] - cc[lo]);
-      x = f * (x >> 16) + slot - start;
-      v = lo - K;
-      esc = lo == NS - 1;
-    }
-    {   // sub-round A: renormalise after the symbols
-      const bool need = act && x < kL;
-      const unsigned w = word(need, bad);
-      if (need) x = (x << 16) | w;
-    }
-    {   // sub-round B: escape payloads
-      unsigned u = 0;
-      if (esc) {
-        u = x & 0xffffu;
-        x >>= 16;
-      }
-      const unsigned w = word(esc, bad);
-      if (esc) {
-        x = (x << 16) | w;
-        v = (int)u - 32768;
-      }
-    }
-    if (act) y[sym_index(g, b, grp, i)] = (float)v;
-  }
-  if (x != kL) bad |= ST_TRAIL;
-  if (lane == 0 && ptr != n) bad |= ST_TRAIL;
-  bad = wave_or(bad);
-  if (lane == 0 && bad) atomicOr(status, bad);
-}
-
 // ----------------------------------------------------------------------------- step maps (§0i)
-// The same coder with a table row per symbol: the symbol of channel c at latent position (i, j)
-// of image b is coded with row slot·N + c of the stacked tables cum[S][N][2K + 3], slot =
-// slots[b][i >> lg][j >> lg]. Stream layout, symbol order, lane ownership, word order and escapes
-// are encode_kernel's and decode_kernel's.
+// MapLayout: PlainLayout's streams with a table row per symbol: the symbol of channel c at latent
+// position (i, j) of image b is coded with row slot·N + c of the stacked tables
+// cum[S][N][2K + 3], slot = slots[b][i >> lg][j >> lg].
 //
 // S·N tables do not fit the LDS (32 steps × 192 channels × 67 ints = 1.6 MB), and a stream walks
 // its channels in order, so the LDS holds a WINDOW: the rows of wc consecutive channels for all S
@@ -333,78 +378,56 @@ __device__ __forceinline__ TabRow map_row(const MapTab& m, const StreamGeo& g, i
   return t;
 }
 
+struct MapLayout {
+  using Row = TabRow;
+  static constexpr bool kWindow = true;
+  const StreamGeo& g;
+  const MapTab& m;
+  int* sc;   // the window, in LDS
+  int TS, b, grp;
+  Window win;
+  __device__ __forceinline__ MapLayout(const StreamGeo& geo, const MapTab& tab, int* window, int K,
+                                       int s)
+      : g(geo), m(tab), sc(window), TS(2 * K + 3), b(s / geo.P), grp(s - b * geo.P) {}
+  __device__ __forceinline__ int nsym() const { return g.cpg * g.HW; }
+  __device__ __forceinline__ Row idle() const { return {sc, m.cum, false}; }
+  __device__ __forceinline__ Row at(int i, long& e) const {
+    e = sym_index(g, b, grp, i);
+    return map_row(m, g, TS, win, sc, b, grp, i);
+  }
+  // the encoder walks down: restage once the block's last channel is below the window
+  __device__ __forceinline__ void walk_down(int blk) {
+    if (m.wc == 0) return;
+    const int last = blk * W + W - 1 < nsym() ? blk * W + W - 1 : nsym() - 1;
+    const int chi = grp * g.cpg + last / g.HW;
+    if (win.n == 0 || chi < win.c0) {
+      win.c0 = chi - m.wc + 1 > grp * g.cpg ? chi - m.wc + 1 : grp * g.cpg;
+      win.n = chi - win.c0 + 1;
+      stage_window(m, g.N, TS, win.c0, win.n, sc);
+    }
+  }
+  // the decoder walks up: restage once the block's first channel is above the window
+  __device__ __forceinline__ void walk_up(int blk) {
+    if (m.wc == 0) return;
+    const int clo = grp * g.cpg + blk * W / g.HW;
+    if (win.n == 0 || clo >= win.c0 + win.n) {
+      const int end = (grp + 1) * g.cpg;
+      win.c0 = clo;
+      win.n = end - clo < m.wc ? end - clo : m.wc;
+      stage_window(m, g.N, TS, win.c0, win.n, sc);
+    }
+  }
+};
+
 __global__ void __launch_bounds__(W) encode_map_kernel(const float* __restrict__ y, StreamGeo g,
                                                        MapTab m, int K,
                                                        unsigned short* __restrict__ scratch,
                                                        long cap, unsigned* __restrict__ lengths,
                                                        int* __restrict__ status) {
   extern __shared__ int sc[];
-  const int NS = 2 * K + 2, TS = NS + 1;
-  const int s = blockIdx.x, lane = threadIdx.x;
-  const int b = s / g.P, grp = s - b * g.P;
-  unsigned short* out = scratch + (long)s * cap;
-  long ptr = cap;
-  unsigned x = kL;
-  int bad = 0;
-  const int nsym = g.cpg * g.HW;
-  const int nblk = (nsym + W - 1) / W;
-  Window win;
-  for (int blk = nblk - 1; blk >= 0; --blk) {
-    if (m.wc > 0) {   // the encoder walks down: restage once the block's last channel is below
-      const int last = blk * W + W - 1 < nsym ? blk * W + W - 1 : nsym - 1;
-      const int chi = grp * g.cpg + last / g.HW;
-      if (win.n == 0 || chi < win.c0) {
-        const int c0 = chi - m.wc + 1 > grp * g.cpg ? chi - m.wc + 1 : grp * g.cpg;
-        win.c0 = c0;
-        win.n = chi - c0 + 1;
-        stage_window(m, g.N, TS, win.c0, win.n, sc);
-      }
-    }
-    const int i = blk * W + lane;
-    const bool act = i < nsym;
-    int sym = 0, pay = -1;
-    TabRow cc = map_row(m, g, TS, win, sc, b, grp, act ? i : 0);
-    if (act) {
-      const long e = sym_index(g, b, grp, i);
-      const float v = y[e];
-      const float r = rintf(v);
-      if (!(r == v)) { bad |= ST_NONINT; sym = K; }   // NaN / non-integer
-      else if (fabsf(v) > 32767.f) { bad |= ST_RANGE; sym = K; }
-      else {
-        const int iv = (int)v;
-        sym = (iv >= -K && iv <= K) ? iv + K : NS - 1;
-        if (sym == NS - 1) pay = iv + 32768;
-      }
-    }
-    // sub-round B: escape payloads (uniform, freq 1: always one word out)
-    {
-      const bool need = pay >= 0;
-      const int2 rc = lane_rank(need, lane);
-      if (need) {
-        out[ptr - rc.y + rc.x] = (unsigned short)(x & 0xffffu);
-        x = ((x >> 16) << 16) + (unsigned)pay;
-      }
-      ptr -= rc.y;
-    }
-    // sub-round A: the symbols
-    {
-      const unsigned start = (unsigned)cc[sym], f = (unsigned)cc[sym + 1] - start;
-      const bool need = act && x >= (f << 16);
-      const int2 rc = lane_rank(need, lane);
-      if (need) {
-        out[ptr - rc.y + rc.x] = (unsigned short)(x & 0xffffu);
-        x >>= 16;
-      }
-      ptr -= rc.y;
-      if (act) x = ((x / f) << 16) + (x % f) + start;
-    }
-  }
-  ptr -= 2 * W;
-  out[ptr + 2 * lane] = (unsigned short)(x >> 16);
-  out[ptr + 2 * lane + 1] = (unsigned short)(x & 0xffffu);
-  if (lane == 0) lengths[s] = (unsigned)(cap - ptr);
-  bad = wave_or(bad);
-  if (lane == 0 && bad) atomicOr(status, bad);
+  const int s = blockIdx.x;
+  MapLayout lay(g, m, sc, K, s);
+  encode_stream(lay, s, threadIdx.x, y, K, scratch, cap, lengths, status);
 }
 
 __global__ void __launch_bounds__(W) decode_map_kernel(const unsigned short* __restrict__ words,
@@ -413,81 +436,9 @@ __global__ void __launch_bounds__(W) decode_map_kernel(const unsigned short* __r
                                                        float* __restrict__ y,
                                                        int* __restrict__ status) {
   extern __shared__ int sc[];
-  const int NS = 2 * K + 2, TS = NS + 1;
-  const int s = blockIdx.x, lane = threadIdx.x;
-  const int b = s / g.P, grp = s - b * g.P;
-  const unsigned short* in = words + offsets[s];
-  const long n = offsets[s + 1] - offsets[s];
-  int bad = 0;
-  if (n < 2 * W) {   // the whole workgroup (one wave) leaves: no barrier follows
-    if (lane == 0) atomicOr(status, ST_OVERRUN);
-    return;
-  }
-  unsigned x = ((unsigned)in[2 * lane] << 16) | in[2 * lane + 1];
-  long ptr = 2 * W;
-  auto word = [&](bool need, int& fail) -> unsigned {
-    const int2 rc = lane_rank(need, lane);
-    unsigned w = 0;
-    if (need) {
-      if (ptr + rc.x < n) w = in[ptr + rc.x];
-      else fail |= ST_OVERRUN;
-    }
-    ptr += rc.y;
-    return w;
-  };
-  const int nsym = g.cpg * g.HW;
-  const int nblk = (nsym + W - 1) / W;
-  Window win;
-  for (int blk = 0; blk < nblk; ++blk) {
-    if (m.wc > 0) {   // the decoder walks up: restage once the block's first channel is above
-      const int clo = grp * g.cpg + blk * W / g.HW;
-      if (win.n == 0 || clo >= win.c0 + win.n) {
-        const int end = (grp + 1) * g.cpg;
-        win.c0 = clo;
-        win.n = end - clo < m.wc ? end - clo : m.wc;
-        stage_window(m, g.N, TS, win.c0, win.n, sc);
-      }
-    }
-    const int i = blk * W + lane;
-    const bool act = i < nsym;
-    int v = 0;
-    bool esc = false;
-    if (act) {
-      const TabRow cc = map_row(m, g, TS, win, sc, b, grp, i);
-      const unsigned slot = x & 0xffffu;
-      int lo = 0, hi = NS;   // cc[lo] ≤ slot < cc[hi]
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((unsigned)cc[mid] <= slot) lo = mid; else hi = mid;
-      }
-      const unsigned start = (unsigned)cc[lo], f = (unsigned)cc[lo + 1] - start;
-      x = f * (x >> 16) + slot - start;
-      v = lo - K;
-      esc = lo == NS - 1;
-    }
-    {   // sub-round A: renormalise after the symbols
-      const bool need = act && x < kL;
-      const unsigned w = word(need, bad);
-      if (need) x = (x << 16) | w;
-    }
-    {   // sub-round B: escape payloads
-      unsigned u = 0;
-      if (esc) {
-        u = x & 0xffffu;
-        x >>= 16;
-      }
-      const unsigned w = word(esc, bad);
-      if (esc) {
-        x = (x << 16) | w;
-        v = (int)u - 32768;
-      }
-    }
-    if (act) y[sym_index(g, b, grp, i)] = (float)v;
-  }
-  if (x != kL) bad |= ST_TRAIL;
-  if (lane == 0 && ptr != n) bad |= ST_TRAIL;
-  bad = wave_or(bad);
-  if (lane == 0 && bad) atomicOr(status, bad);
+  const int s = blockIdx.x;
+  MapLayout lay(g, m, sc, K, s);
+  decode_stream(lay, threadIdx.x, words + offsets[s], offsets[s + 1] - offsets[s], K, y, status);
 }
 
 // The window of a map launch: as many channels as the S slots' rows allow in 64 KiB of LDS, at
@@ -500,11 +451,11 @@ int map_window(int S, int K, int cpg, int window) {
 }
 
 // ----------------------------------------------------------------------------- tiles (§0k)
-// The same coder with a stream per spatial tile: the h×w latent is cut into tiles of t×t
-// positions (t = 2^lg; ragged at the bottom and right), one stream per (image, tile row, tile
-// column, channel group) in that order, symbols in (channel, row in tile, column in tile) order.
-// Lane ownership, block order, escapes, word groups and status bits are encode_kernel's and
-// decode_kernel's, so a tile's words are the oracle's encode_stream of its sequence.
+// TileLayout: a stream per spatial tile: the h×w latent is cut into tiles of t×t positions
+// (t = 2^lg; ragged at the bottom and right), one stream per (image, tile row, tile column,
+// channel group) in that order, symbols in (channel, row in tile, column in tile) order, every
+// channel's table in LDS. The body codes it, so a tile's words are the oracle's encode_stream of
+// its sequence.
 //
 // A launch codes the streams of a rectangle of tiles, nr×nc from tile (r0, c0), against a tensor
 // [B][oh][ow][N] whose origin is the rectangle's first position: the whole grid and the whole
@@ -512,7 +463,9 @@ int map_window(int S, int K, int cpg, int window) {
 // Every stream's place follows from its index and this geometry, which the host has checked; no
 // address comes from device memory.
 //
-// WAVES waves share one workgroup and one staged table set, one stream each.
+// WAVES waves share one workgroup and one staged table set, one stream each. Staging ends in the
+// kernels' only barrier: after it the waves run independently and those without a stream have
+// returned, which is why this layout has no per-block hook.
 struct TileGeo {
   int h, w, N, cpg, P;   // the latent, its channels, channels per group, groups
   int lg;                // log2 of the tile edge
@@ -539,8 +492,8 @@ struct Divisor {
 
 struct TileStream {
   int b, grp;
-  int i0, j0;    // the tile's origin in the tensor
-  int th, tw;    // its extent
+  long e0;       // the element of the tile's origin and the group's first channel in the tensor
+  int th, tw;    // the tile's extent
   Divisor by_hw, by_tw;
 };
 
@@ -553,8 +506,7 @@ __device__ __forceinline__ TileStream tile_stream(const TileGeo& g, int s) {
   const int tr = q % g.nr;
   d.b = q / g.nr;
   const int t = 1 << g.lg;
-  d.i0 = tr * t;
-  d.j0 = tc * t;
+  d.e0 = (((long)d.b * g.oh + tr * t) * g.ow + tc * t) * g.N + d.grp * g.cpg;
   d.th = min(t, g.h - (g.r0 + tr) * t);
   d.tw = min(t, g.w - (g.c0 + tc) * t);
   d.by_hw.set((unsigned)(d.th * d.tw), (unsigned long long)g.cpg * d.th * d.tw + W);
@@ -568,8 +520,26 @@ __device__ __forceinline__ long tile_index(const TileGeo& g, const TileStream& d
   cl = (int)d.by_hw((unsigned)i);
   const int pix = i - cl * hw;
   const int r = (int)d.by_tw((unsigned)pix), q = pix - r * d.tw;
-  return (((long)d.b * g.oh + d.i0 + r) * g.ow + d.j0 + q) * g.N + d.grp * g.cpg + cl;
+  return d.e0 + ((long)r * g.ow + q) * g.N + cl;
 }
+
+struct TileLayout {
+  using Row = const int*;
+  static constexpr bool kWindow = false;
+  const TileGeo& g;
+  const int* sc;   // every channel's table, in LDS
+  int TS;
+  TileStream d;
+  __device__ __forceinline__ TileLayout(const TileGeo& geo, const int* tables, int K, int s)
+      : g(geo), sc(tables), TS(2 * K + 3), d(tile_stream(geo, s)) {}
+  __device__ __forceinline__ int nsym() const { return g.cpg * d.th * d.tw; }
+  __device__ __forceinline__ Row idle() const { return sc; }
+  __device__ __forceinline__ Row at(int i, long& e) const {
+    int cl;
+    e = tile_index(g, d, i, cl);
+    return sc + (d.grp * g.cpg + cl) * TS;
+  }
+};
 
 template <int WAVES>
 __global__ void __launch_bounds__(W * WAVES) encode_tiled_kernel(
@@ -577,67 +547,11 @@ __global__ void __launch_bounds__(W * WAVES) encode_tiled_kernel(
     unsigned short* __restrict__ scratch, long cap, unsigned* __restrict__ lengths,
     int* __restrict__ status) {
   extern __shared__ int sc[];
-  const int NS = 2 * K + 2, TS = NS + 1;
-  for (int i = threadIdx.x; i < g.N * TS; i += W * WAVES) sc[i] = cum[i];
-  __syncthreads();   // the only barrier: from here every wave is on its own
-  const int lane = threadIdx.x & (W - 1);
+  load_tables<W * WAVES>(cum, g.N * (2 * K + 3), sc);   // the only barrier
   const int s = blockIdx.x * WAVES + (threadIdx.x >> 6);
   if (s >= g.ns) return;
-  const TileStream d = tile_stream(g, s);
-  unsigned short* out = scratch + (long)s * cap;
-  long ptr = cap;
-  unsigned x = kL;
-  int bad = 0;
-  const int nsym = g.cpg * d.th * d.tw;
-  const int nblk = (nsym + W - 1) / W;
-  for (int blk = nblk - 1; blk >= 0; --blk) {
-    const int i = blk * W + lane;
-    const bool act = i < nsym;
-    int sym = 0, pay = -1;
-    const int* cc = sc;
-    if (act) {
-      int cl;
-      const long e = tile_index(g, d, i, cl);
-      const float v = y[e];
-      cc = sc + (d.grp * g.cpg + cl) * TS;
-      const float r = rintf(v);
-      if (!(r == v)) { bad |= ST_NONINT; sym = K; }   // NaN / non-integer
-      else if (fabsf(v) > 32767.f) { bad |= ST_RANGE; sym = K; }
-      else {
-        const int iv = (int)v;
-        sym = (iv >= -K && iv <= K) ? iv + K : NS - 1;
-        if (sym == NS - 1) pay = iv + 32768;
-      }
-    }
-    // sub-round B: escape payloads (uniform, freq 1: always one word out)
-    {
-      const bool need = pay >= 0;
-      const int2 rc = lane_rank(need, lane);
-      if (need) {
-        out[ptr - rc.y + rc.x] = (unsigned short)(x & 0xffffu);
-        x = ((x >> 16) << 16) + (unsigned)pay;
-      }
-      ptr -= rc.y;
-    }
-    // sub-round A: the symbols
-    {
-      const unsigned start = (unsigned)cc[sym], f = (unsigned)(cc[sym + 1] - cc[sym]);
-      const bool need = act && x >= (f << 16);
-      const int2 rc = lane_rank(need, lane);
-      if (need) {
-        out[ptr - rc.y + rc.x] = (unsigned short)(x & 0xffffu);
-        x >>= 16;
-      }
-      ptr -= rc.y;
-      if (act) x = ((x / f) << 16) + (x % f) + start;
-    }
-  }
-  ptr -= 2 * W;
-  out[ptr + 2 * lane] = (unsigned short)(x >> 16);
-  out[ptr + 2 * lane + 1] = (unsigned short)(x & 0xffffu);
-  if (lane == 0) lengths[s] = (unsigned)(cap - ptr);
-  bad = wave_or(bad);
-  if (lane == 0 && bad) atomicOr(status, bad);
+  TileLayout lay(g, sc, K, s);
+  encode_stream(lay, s, threadIdx.x & (W - 1), y, K, scratch, cap, lengths, status);
 }
 
 template <int WAVES>
@@ -646,80 +560,17 @@ __global__ void __launch_bounds__(W * WAVES) decode_tiled_kernel(
     TileGeo g, const int* __restrict__ cum, int K, float* __restrict__ y,
     int* __restrict__ status) {
   extern __shared__ int sc[];
-  const int NS = 2 * K + 2, TS = NS + 1;
-  for (int i = threadIdx.x; i < g.N * TS; i += W * WAVES) sc[i] = cum[i];
-  __syncthreads();   // the only barrier: from here every wave is on its own
-  const int lane = threadIdx.x & (W - 1);
-  const int s = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  load_tables<W * WAVES>(cum, g.N * (2 * K + 3), sc);   // the only barrier
+  const int s = blockIdx.x * WAVES + (threadIdx.x >> 6), lane = threadIdx.x & (W - 1);
   if (s >= g.ns) return;
-  const TileStream d = tile_stream(g, s);
   const long o0 = offsets[s], o1 = offsets[s + 1];
-  const long n = o1 - o0;
-  int bad = 0;
   // the offsets come from a stream: never read outside the words, whatever they say
-  if (o0 < 0 || o1 > total || n < 2 * W) {
+  if (o0 < 0 || o1 > total) {
     if (lane == 0) atomicOr(status, ST_OVERRUN);
     return;
   }
-  const unsigned short* in = words + o0;
-  unsigned x = ((unsigned)in[2 * lane] << 16) | in[2 * lane + 1];
-  long ptr = 2 * W;
-  auto word = [&](bool need, int& fail) -> unsigned {
-    const int2 rc = lane_rank(need, lane);
-    unsigned w = 0;
-    if (need) {
-      if (ptr + rc.x < n) w = in[ptr + rc.x];
-      else fail |= ST_OVERRUN;
-    }
-    ptr += rc.y;
-    return w;
-  };
-  const int nsym = g.cpg * d.th * d.tw;
-  const int nblk = (nsym + W - 1) / W;
-  for (int blk = 0; blk < nblk; ++blk) {
-    const int i = blk * W + lane;
-    const bool act = i < nsym;
-    int v = 0;
-    bool esc = false;
-    long e = 0;
-    if (act) {
-      int cl;
-      e = tile_index(g, d, i, cl);
-      const int* cc = sc + (d.grp * g.cpg + cl) * TS;
-      const unsigned slot = x & 0xffffu;
-      int lo = 0, hi = NS;   // cc[lo] ≤ slot < cc[hi]
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((unsigned)cc[mid] <= slot) lo = mid; else hi = mid;
-      }
-      const unsigned start = (unsigned)cc[lo], f = (unsigned)(cc[lo + 1] - cc[lo]);
-      x = f * (x >> 16) + slot - start;
-      v = lo - K;
-      esc = lo == NS - 1;
-    }
-    {   // sub-round A: renormalise after the symbols
-      const bool need = act && x < kL;
-      const unsigned w = word(need, bad);
-      if (need) x = (x << 16) | w;
-    }
-    {   // sub-round B: escape payloads
-      unsigned u = 0;
-      if (esc) {
-        u = x & 0xffffu;
-        x >>= 16;
-      }
-      const unsigned w = word(esc, bad);
-      if (esc) {
-        x = (x << 16) | w;
-        v = (int)u - 32768;
-      }
-    }
-    if (act) y[e] = (float)v;
-  }
-  if (x != kL) bad |= ST_TRAIL;
-  if (lane == 0 && ptr != n) bad |= ST_TRAIL;
-  bad = wave_or(bad);
-  if (lane == 0 && bad) atomicOr(status, bad);
+  TileLayout lay(g, sc, K, s);
+  decode_stream(lay, lane, words + o0, o1 - o0, K, y, status);
 }
 
 // Waves per workgroup when the caller leaves it open (§0k, profiles/tiled_ab.txt). The coder is
@@ -762,6 +613,42 @@ bool tile_geo(int B, int h, int w, int N, int P, int log2_t, int r0, int c0, int
   return true;
 }
 
+// The bytes of N channels' tables, which a launch that stages them all must fit in the LDS.
+int table_bytes(const char* what, int N, int K, size_t& shm) {
+  shm = (size_t)N * (2 * K + 3) * sizeof(int);
+  ICLR17_REQUIRE(shm <= 64 * 1024, ICLR17_EINVAL, "%s: tables of %zu bytes exceed LDS", what, shm);
+  return 0;
+}
+
+// The geometry, tables and dynamic LDS of a mapped launch from the caller's (checked) scalars.
+struct MapLaunch {
+  StreamGeo g;
+  MapTab m;
+  size_t shm;
+};
+
+MapLaunch map_launch(int h, int w, int N, int P, const int32_t* cum, int S, int K,
+                     const uint8_t* slots, int log2_g, int window) {
+  const StreamGeo g{h * w, N, N / P, P};
+  const int gb = 1 << log2_g, mh = (h + gb - 1) / gb, mw = (w + gb - 1) / gb;
+  const MapTab m{(const int*)cum, (const unsigned char*)slots, S, w, mw, mh * mw, log2_g,
+                 map_window(S, K, g.cpg, window)};
+  return {g, m, (size_t)S * m.wc * (2 * K + 3) * sizeof(int)};
+}
+
+// launch(integral_constant<int, waves>) for a supported number of waves per workgroup
+template <class F>
+bool with_waves(int waves, F&& launch) {
+  switch (waves) {
+    case 1: launch(std::integral_constant<int, 1>{}); return true;
+    case 2: launch(std::integral_constant<int, 2>{}); return true;
+    case 4: launch(std::integral_constant<int, 4>{}); return true;
+    case 8: launch(std::integral_constant<int, 8>{}); return true;
+    case 16: launch(std::integral_constant<int, 16>{}); return true;
+    default: return false;
+  }
+}
+
 }  // namespace
 }  // namespace iclr17
 
@@ -789,8 +676,8 @@ int iclr17_rans_encode(const float* y_hat, int B, int h, int w, int N, int strea
   const long cap = iclr17_rans_capacity(h, w, N, streams_per_image);
   ICLR17_REQUIRE(y_hat && cum && scratch && lengths && status && B > 0 && cap > 0 && K >= 1,
                  ICLR17_EINVAL, "rans_encode: bad arguments");
-  const size_t shm = (size_t)N * (2 * K + 3) * sizeof(int);
-  ICLR17_REQUIRE(shm <= 64 * 1024, ICLR17_EINVAL, "rans_encode: tables of %zu bytes exceed LDS", shm);
+  size_t shm;
+  if (const int rc = table_bytes("rans_encode", N, K, shm)) return rc;
   const int ns = B * streams_per_image;
   ICLR17_REQUIRE(scratch_words >= cap * ns, ICLR17_EINVAL,
                  "rans_encode: scratch of %ld words < %ld", scratch_words, cap * ns);
@@ -824,8 +711,8 @@ int iclr17_rans_decode(const uint16_t* words, const int64_t* offsets, int B, int
   ICLR17_REQUIRE(words && offsets && cum && y_hat && status && B > 0 && h > 0 && w > 0 &&
                      N > 0 && streams_per_image > 0 && N % streams_per_image == 0 && K >= 1,
                  ICLR17_EINVAL, "rans_decode: bad arguments");
-  const size_t shm = (size_t)N * (2 * K + 3) * sizeof(int);
-  ICLR17_REQUIRE(shm <= 64 * 1024, ICLR17_EINVAL, "rans_decode: tables of %zu bytes exceed LDS", shm);
+  size_t shm;
+  if (const int rc = table_bytes("rans_decode", N, K, shm)) return rc;
   const int ns = B * streams_per_image;
   StreamGeo g{h * w, N, N / streams_per_image, streams_per_image};
   hipLaunchKernelGGL(decode_kernel, dim3(ns), dim3(W), shm, (hipStream_t)stream,
@@ -848,13 +735,9 @@ int iclr17_rans_encode_map(const float* y_hat, int B, int h, int w, int N, int s
   const int ns = B * streams_per_image;
   ICLR17_REQUIRE(scratch_words >= cap * ns, ICLR17_EINVAL,
                  "rans_encode_map: scratch of %ld words < %ld", scratch_words, cap * ns);
-  StreamGeo g{h * w, N, N / streams_per_image, streams_per_image};
-  const int gb = 1 << log2_g, mh = (h + gb - 1) / gb, mw = (w + gb - 1) / gb;
-  MapTab m{(const int*)cum, (const unsigned char*)slots, S, w, mw, mh * mw, log2_g,
-           map_window(S, K, g.cpg, window)};
-  const size_t shm = (size_t)S * m.wc * (2 * K + 3) * sizeof(int);
-  hipLaunchKernelGGL(encode_map_kernel, dim3(ns), dim3(W), shm, (hipStream_t)stream, y_hat, g, m,
-                     K, (unsigned short*)scratch, cap, (unsigned*)lengths, (int*)status);
+  const MapLaunch l = map_launch(h, w, N, streams_per_image, cum, S, K, slots, log2_g, window);
+  hipLaunchKernelGGL(encode_map_kernel, dim3(ns), dim3(W), l.shm, (hipStream_t)stream, y_hat, l.g,
+                     l.m, K, (unsigned short*)scratch, cap, (unsigned*)lengths, (int*)status);
   return check_launch("rans_encode_map");
 }
 
@@ -870,13 +753,9 @@ int iclr17_rans_decode_map(const uint16_t* words, const int64_t* offsets, int B,
   ICLR17_REQUIRE(log2_g >= 0 && log2_g <= 4, ICLR17_EINVAL,
                  "rans_decode_map: log2 of the block edge is %d (0..4)", log2_g);
   const int ns = B * streams_per_image;
-  StreamGeo g{h * w, N, N / streams_per_image, streams_per_image};
-  const int gb = 1 << log2_g, mh = (h + gb - 1) / gb, mw = (w + gb - 1) / gb;
-  MapTab m{(const int*)cum, (const unsigned char*)slots, S, w, mw, mh * mw, log2_g,
-           map_window(S, K, g.cpg, window)};
-  const size_t shm = (size_t)S * m.wc * (2 * K + 3) * sizeof(int);
-  hipLaunchKernelGGL(decode_map_kernel, dim3(ns), dim3(W), shm, (hipStream_t)stream,
-                     (const unsigned short*)words, (const long*)offsets, g, m, K, y_hat,
+  const MapLaunch l = map_launch(h, w, N, streams_per_image, cum, S, K, slots, log2_g, window);
+  hipLaunchKernelGGL(decode_map_kernel, dim3(ns), dim3(W), l.shm, (hipStream_t)stream,
+                     (const unsigned short*)words, (const long*)offsets, l.g, l.m, K, y_hat,
                      (int*)status);
   return check_launch("rans_decode_map");
 }
@@ -905,28 +784,20 @@ int iclr17_rans_encode_tiled(const float* y_hat, int B, int h, int w, int N, int
   ICLR17_REQUIRE(tile_geo(B, h, w, N, streams_per_tile, log2_t, 0, 0, (h + t - 1) / t,
                           (w + t - 1) / t, g, why),
                  ICLR17_EINVAL, "rans_encode_tiled: %s", why);
-  const size_t shm = (size_t)N * (2 * K + 3) * sizeof(int);
-  ICLR17_REQUIRE(shm <= 64 * 1024, ICLR17_EINVAL,
-                 "rans_encode_tiled: tables of %zu bytes exceed LDS", shm);
+  size_t shm;
+  if (const int rc = table_bytes("rans_encode_tiled", N, K, shm)) return rc;
   const long cap = iclr17_rans_tiled_capacity(N, streams_per_tile, log2_t);
   ICLR17_REQUIRE(scratch_words >= cap * g.ns, ICLR17_EINVAL,
                  "rans_encode_tiled: scratch of %ld words < %ld", scratch_words, cap * g.ns);
   if (!waves) waves = tiled_waves(g.ns, shm);
-#define ICLR17_ENC_TILED(WV)                                                                     \
-  hipLaunchKernelGGL(encode_tiled_kernel<WV>, dim3((g.ns + WV - 1) / WV), dim3(W * WV), shm,     \
-                     (hipStream_t)stream, y_hat, g, (const int*)cum, K,                          \
-                     (unsigned short*)scratch, cap, (unsigned*)lengths, (int*)status)
-  switch (waves) {
-    case 1: ICLR17_ENC_TILED(1); break;
-    case 2: ICLR17_ENC_TILED(2); break;
-    case 4: ICLR17_ENC_TILED(4); break;
-    case 8: ICLR17_ENC_TILED(8); break;
-    case 16: ICLR17_ENC_TILED(16); break;
-    default:
-      ICLR17_REQUIRE(false, ICLR17_EINVAL,
-                     "rans_encode_tiled: %d waves per workgroup (0, 1, 2, 4, 8, 16)", waves);
-  }
-#undef ICLR17_ENC_TILED
+  const bool ok = with_waves(waves, [&](auto wv) {
+    constexpr int WV = decltype(wv)::value;
+    hipLaunchKernelGGL(encode_tiled_kernel<WV>, dim3((g.ns + WV - 1) / WV), dim3(W * WV), shm,
+                       (hipStream_t)stream, y_hat, g, (const int*)cum, K, (unsigned short*)scratch,
+                       cap, (unsigned*)lengths, (int*)status);
+  });
+  ICLR17_REQUIRE(ok, ICLR17_EINVAL,
+                 "rans_encode_tiled: %d waves per workgroup (0, 1, 2, 4, 8, 16)", waves);
   return check_launch("rans_encode_tiled");
 }
 
@@ -941,28 +812,20 @@ int iclr17_rans_decode_tiled(const uint16_t* words, long total_words, const int6
   const char* why;
   ICLR17_REQUIRE(tile_geo(B, h, w, N, streams_per_tile, log2_t, r0, c0, nr, nc, g, why),
                  ICLR17_EINVAL, "rans_decode_tiled: %s", why);
-  const size_t shm = (size_t)N * (2 * K + 3) * sizeof(int);
-  ICLR17_REQUIRE(shm <= 64 * 1024, ICLR17_EINVAL,
-                 "rans_decode_tiled: tables of %zu bytes exceed LDS", shm);
+  size_t shm;
+  if (const int rc = table_bytes("rans_decode_tiled", N, K, shm)) return rc;
   const long need = (long)B * g.oh * g.ow * N;
   ICLR17_REQUIRE(y_elems >= need, ICLR17_EINVAL,
                  "rans_decode_tiled: output of %ld elements < %ld", y_elems, need);
   if (!waves) waves = tiled_waves(g.ns, shm);
-#define ICLR17_DEC_TILED(WV)                                                                     \
-  hipLaunchKernelGGL(decode_tiled_kernel<WV>, dim3((g.ns + WV - 1) / WV), dim3(W * WV), shm,     \
-                     (hipStream_t)stream, (const unsigned short*)words, (const long*)offsets,    \
-                     total_words, g, (const int*)cum, K, y_hat, (int*)status)
-  switch (waves) {
-    case 1: ICLR17_DEC_TILED(1); break;
-    case 2: ICLR17_DEC_TILED(2); break;
-    case 4: ICLR17_DEC_TILED(4); break;
-    case 8: ICLR17_DEC_TILED(8); break;
-    case 16: ICLR17_DEC_TILED(16); break;
-    default:
-      ICLR17_REQUIRE(false, ICLR17_EINVAL,
-                     "rans_decode_tiled: %d waves per workgroup (0, 1, 2, 4, 8, 16)", waves);
-  }
-#undef ICLR17_DEC_TILED
+  const bool ok = with_waves(waves, [&](auto wv) {
+    constexpr int WV = decltype(wv)::value;
+    hipLaunchKernelGGL(decode_tiled_kernel<WV>, dim3((g.ns + WV - 1) / WV), dim3(W * WV), shm,
+                       (hipStream_t)stream, (const unsigned short*)words, (const long*)offsets,
+                       total_words, g, (const int*)cum, K, y_hat, (int*)status);
+  });
+  ICLR17_REQUIRE(ok, ICLR17_EINVAL,
+                 "rans_decode_tiled: %d waves per workgroup (0, 1, 2, 4, 8, 16)", waves);
   return check_launch("rans_decode_tiled");
 }
 

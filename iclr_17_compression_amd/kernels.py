@@ -1134,6 +1134,28 @@ def _rans_status(status: Tensor, what: str) -> None:
         raise Iclr17Error(f"iclr17: {what}: " + "; ".join(why))
 
 
+def _rans_encode_tail(launch, ns: int, cap: int, dev, st, what: str):
+    """What every encoder does around its launch: ``launch(scratch, lengths, status)`` codes ns
+    streams into slots of cap words; offsets, pack and the status check → (words, offsets)."""
+    scratch = torch.empty(ns * cap, device=dev, dtype=torch.int16)
+    lengths = torch.empty(ns, device=dev, dtype=torch.int32)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    launch(scratch, lengths, status)
+    offsets = torch.empty(ns + 1, device=dev, dtype=torch.int64)
+    call("iclr17_rans_offsets", _p(lengths), ns, _p(offsets), st)
+    total = int(offsets[-1].item())
+    words = torch.empty(max(total, 1), device=dev, dtype=torch.int16)
+    call("iclr17_rans_pack", _p(scratch), cap, _p(offsets), ns, _p(words), st)
+    _rans_status(status, what)
+    return words[:total], offsets
+
+
+def _rans_decode_args(words: Tensor, dev):
+    """(words contiguous, or a 1-element dummy for an empty tensor; a zeroed status word)."""
+    words = words.contiguous() if words.numel() else torch.zeros(1, device=dev, dtype=torch.int16)
+    return words, torch.zeros(1, device=dev, dtype=torch.int32)
+
+
 def rans_encode(y_hat: Tensor, cum: Tensor, K: int = ENTROPY_K,
                 streams_per_image: int = STREAMS_PER_IMAGE):
     """ŷ NHWC [B,h,w,N] → (words int16 [T] (uint16 bit patterns), offsets int64 [B·P + 1]);
@@ -1144,20 +1166,12 @@ def rans_encode(y_hat: Tensor, cum: Tensor, K: int = ENTROPY_K,
     cap = query("iclr17_rans_capacity", h, w, N, P)
     if cap <= 0:
         raise Iclr17Error(f"iclr17: rans_encode: N={N} not divisible into {P} streams")
-    dev = y_hat.device
-    scratch = torch.empty(B * P * cap, device=dev, dtype=torch.int16)
-    lengths = torch.empty(B * P, device=dev, dtype=torch.int32)
-    status = torch.zeros(1, device=dev, dtype=torch.int32)
     st = _stream(y_hat)
-    call("iclr17_rans_encode", _p(y_hat.contiguous()), B, h, w, N, P, _p(cum), K, _p(scratch),
-         scratch.numel(), _p(lengths), _p(status), st)
-    offsets = torch.empty(B * P + 1, device=dev, dtype=torch.int64)
-    call("iclr17_rans_offsets", _p(lengths), B * P, _p(offsets), st)
-    total = int(offsets[-1].item())
-    words = torch.empty(max(total, 1), device=dev, dtype=torch.int16)
-    call("iclr17_rans_pack", _p(scratch), cap, _p(offsets), B * P, _p(words), st)
-    _rans_status(status, "rans_encode")
-    return words[:total], offsets
+
+    def launch(scratch, lengths, status):
+        call("iclr17_rans_encode", _p(y_hat.contiguous()), B, h, w, N, P, _p(cum), K, _p(scratch),
+             scratch.numel(), _p(lengths), _p(status), st)
+    return _rans_encode_tail(launch, B * P, cap, y_hat.device, st, "rans_encode")
 
 
 def rans_decode(words: Tensor, offsets: Tensor, cum: Tensor, B: int, h: int, w: int, N: int,
@@ -1168,8 +1182,7 @@ def rans_decode(words: Tensor, offsets: Tensor, cum: Tensor, B: int, h: int, w: 
         raise Iclr17Error("iclr17: rans_decode: offsets do not match B x streams_per_image")
     dev = cum.device
     y = torch.empty(B, h, w, N, device=dev, dtype=torch.float32)
-    status = torch.zeros(1, device=dev, dtype=torch.int32)
-    words = words.contiguous() if words.numel() else torch.zeros(1, device=dev, dtype=torch.int16)
+    words, status = _rans_decode_args(words, dev)
     call("iclr17_rans_decode", _p(words), _p(offsets.contiguous()), B, h, w, N, P, _p(cum), K,
          _p(y), _p(status), _stream(y))
     _rans_status(status, "rans_decode")
@@ -1513,21 +1526,13 @@ def rans_encode_map(y_hat: Tensor, cum: Tensor, slots, block: int, K: int = ENTR
     cap = query("iclr17_rans_capacity", h, w, N, P)
     if cap <= 0:
         raise Iclr17Error(f"iclr17: rans_encode_map: N={N} not divisible into {P} streams")
-    dev = y_hat.device
-    scratch = torch.empty(B * P * cap, device=dev, dtype=torch.int16)
-    lengths = torch.empty(B * P, device=dev, dtype=torch.int32)
-    status = torch.zeros(1, device=dev, dtype=torch.int32)
     st = _stream(y_hat)
-    call("iclr17_rans_encode_map", _p(y_hat.contiguous()), B, h, w, N, P, _p(cum.contiguous()), S, K,
-         _p(sl), MAP_BLOCKS.index(block), int(bool(window)),
-         _p(scratch), scratch.numel(), _p(lengths), _p(status), st)
-    offsets = torch.empty(B * P + 1, device=dev, dtype=torch.int64)
-    call("iclr17_rans_offsets", _p(lengths), B * P, _p(offsets), st)
-    total = int(offsets[-1].item())
-    words = torch.empty(max(total, 1), device=dev, dtype=torch.int16)
-    call("iclr17_rans_pack", _p(scratch), cap, _p(offsets), B * P, _p(words), st)
-    _rans_status(status, "rans_encode_map")
-    return words[:total], offsets
+
+    def launch(scratch, lengths, status):
+        call("iclr17_rans_encode_map", _p(y_hat.contiguous()), B, h, w, N, P, _p(cum.contiguous()),
+             S, K, _p(sl), MAP_BLOCKS.index(block), int(bool(window)),
+             _p(scratch), scratch.numel(), _p(lengths), _p(status), st)
+    return _rans_encode_tail(launch, B * P, cap, y_hat.device, st, "rans_encode_map")
 
 
 def rans_decode_map(words: Tensor, offsets: Tensor, cum: Tensor, slots, block: int, B: int, h: int,
@@ -1542,8 +1547,7 @@ def rans_decode_map(words: Tensor, offsets: Tensor, cum: Tensor, slots, block: i
     dev = cum.device
     sl = _map_on(dev, slots, "rans_decode_map", "slots", B, h, w, block, 0, S - 1, np.uint8)
     y = torch.empty(B, h, w, N, device=dev, dtype=torch.float32)
-    status = torch.zeros(1, device=dev, dtype=torch.int32)
-    words = words.contiguous() if words.numel() else torch.zeros(1, device=dev, dtype=torch.int16)
+    words, status = _rans_decode_args(words, dev)
     call("iclr17_rans_decode_map", _p(words), _p(offsets.contiguous()), B, h, w, N, P,
          _p(cum.contiguous()), S, K, _p(sl), MAP_BLOCKS.index(block),
          int(S <= RANS_MAP_DECODE_WINDOW_SETS if window is None else bool(window)), _p(y),
@@ -1590,21 +1594,12 @@ def rans_encode_tiled(y_hat: Tensor, cum: Tensor, tile: int, K: int = ENTROPY_K,
     P = streams_per_tile
     th, tw, lg, wv = _tiled_args("rans_encode_tiled", cum, N, K, P, tile, h, w, waves)
     cap = query("iclr17_rans_tiled_capacity", N, P, lg)
-    ns = B * th * tw * P
-    dev = y_hat.device
-    scratch = torch.empty(ns * cap, device=dev, dtype=torch.int16)
-    lengths = torch.empty(ns, device=dev, dtype=torch.int32)
-    status = torch.zeros(1, device=dev, dtype=torch.int32)
     st = _stream(y_hat)
-    call("iclr17_rans_encode_tiled", _p(y_hat.contiguous()), B, h, w, N, P, lg, _p(cum.contiguous()),
-         K, wv, _p(scratch), scratch.numel(), _p(lengths), _p(status), st)
-    offsets = torch.empty(ns + 1, device=dev, dtype=torch.int64)
-    call("iclr17_rans_offsets", _p(lengths), ns, _p(offsets), st)
-    total = int(offsets[-1].item())
-    words = torch.empty(max(total, 1), device=dev, dtype=torch.int16)
-    call("iclr17_rans_pack", _p(scratch), cap, _p(offsets), ns, _p(words), st)
-    _rans_status(status, "rans_encode_tiled")
-    return words[:total], offsets
+
+    def launch(scratch, lengths, status):
+        call("iclr17_rans_encode_tiled", _p(y_hat.contiguous()), B, h, w, N, P, lg,
+             _p(cum.contiguous()), K, wv, _p(scratch), scratch.numel(), _p(lengths), _p(status), st)
+    return _rans_encode_tail(launch, B * th * tw * P, cap, y_hat.device, st, "rans_encode_tiled")
 
 
 def rans_decode_tiled(words: Tensor, offsets: Tensor, cum: Tensor, B: int, h: int, w: int, N: int,
@@ -1635,9 +1630,8 @@ def rans_decode_tiled(words: Tensor, offsets: Tensor, cum: Tensor, B: int, h: in
         raise Iclr17Error("iclr17: rans_decode_tiled: words, offsets and tables on different devices")
     oh, ow = min(h, r1 * tile) - r0 * tile, min(w, c1 * tile) - c0 * tile
     y = torch.empty(B, oh, ow, N, device=dev, dtype=torch.float32)
-    status = torch.zeros(1, device=dev, dtype=torch.int32)
     total = words.numel()
-    words = words.contiguous() if total else torch.zeros(1, device=dev, dtype=torch.int16)
+    words, status = _rans_decode_args(words, dev)
     call("iclr17_rans_decode_tiled", _p(words), total, _p(offsets.contiguous()), B, h, w, N, P, lg,
          r0, c0, r1 - r0, c1 - c0, _p(cum.contiguous()), K, wv, _p(y), y.numel(), _p(status),
          _stream(y))

@@ -56,6 +56,40 @@ def test_bitstream_matches_oracle(device, N, P):
     assert torch.equal(back, y_hat)
 
 
+@pytest.mark.parametrize("k", [4, K])
+def test_three_layouts_give_the_same_words(device, k):
+    """One coder body, three layouts: where the layouts describe the same streams — a latent that
+    fits one tile, a map whose table sets are all the same — the tiled and the mapped coder give
+    the plain coder's words and offsets, and every decoder returns ŷ from them. 252 symbols per
+    stream: a ragged last block of 60, a block of 64 spanning four channels; at k = 4 most
+    blocks hold escapes."""
+    B, h, w, N, P = 2, 3, 7, 192, 16
+    y_np = np.rint(np.random.default_rng(1717).laplace(0.0, 3.0, (B, h, w, N))).astype(np.float32)
+    y_np[0, 0, 0, :2] = [k + 1.0, -k - 1.0]
+    y_np[0, 0, 0, 3] = -32767.0
+    y_np[1, 2, 5, N - 1] = 32767.0
+    y = torch.from_numpy(y_np).to(device)
+    cum = net_for(N, 1, device).bitEstimator.entropy_tables(k)
+    cum2 = torch.stack([cum, cum])
+    slots = np.random.default_rng(1718).integers(0, 2, (B, h, w)).astype(np.uint8)
+
+    words, offsets = kernels.rans_encode(y, cum, k, P)
+    w_t, o_t = kernels.rans_encode_tiled(y, cum, 8, k, P)
+    assert torch.equal(o_t, offsets) and torch.equal(w_t, words)
+    for window in (True, False):
+        w_m, o_m = kernels.rans_encode_map(y, cum2, slots, 1, k, P, window=window)
+        assert torch.equal(o_m, offsets) and torch.equal(w_m, words), window
+
+    assert torch.equal(kernels.rans_decode(words, offsets, cum, B, h, w, N, k, P), y)
+    for window in (True, False):
+        back = kernels.rans_decode_map(words, offsets, cum2, slots, 1, B, h, w, N, k, P,
+                                       window=window)
+        assert torch.equal(back, y), window
+    for waves in (1, 4):
+        back = kernels.rans_decode_tiled(words, offsets, cum, B, h, w, N, 8, k, P, waves=waves)
+        assert torch.equal(back, y), waves
+
+
 def test_round_trip_full_size(device):
     """B=16 of 256² (C3-sized latents) plus wide-range values: decode(encode(ŷ)) == ŷ."""
     N = 192
