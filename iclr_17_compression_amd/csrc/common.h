@@ -159,7 +159,7 @@ __device__ __forceinline__ float element_bits(float z, const float* __restrict__
 
 // bitparm_cdf with the parameters of one channel in registers and row 0 given separately (the
 // step pack's row 0): the same separate fp32 ops in the same order. Shared by the
-// rate sweeps of ratectl.hip and stepmap.hip.
+// rate sweeps of ratectl.hip.
 __device__ __forceinline__ float cdf_regs(float v, float sp0, const float (&p)[kRateRows]) {
 #pragma unroll
   for (int k = 0; k < 3; ++k) {

@@ -13,19 +13,17 @@
 //                         partials in the [T][11][C] slots iclr17_rate_param_grad reads
 //   grad_recon_images     grad_recon with the MSE weight per image
 //
-// The forward's partials are rate_bits' own on z (the same 4096-element chunks, the same thread →
-// element map, fp32 per thread and wave, float64 across the waves), laid out [B][chunks] for
-// iclr17_reduce_partials; the backward's rows are written by the thread that owns the channel. No
-// atomics anywhere: bitwise reproducible.
+// The forward's partials are rate_bits' own on z (ladder.h's chunks and its tail of one sum: the
+// same thread → element map, fp32 per thread and wave, float64 across the waves), laid out
+// [B][chunks] for iclr17_reduce_partials; the backward's rows are written by the thread that owns
+// the channel. No atomics anywhere: bitwise reproducible.
 #include <math.h>
 
-#include "common.h"
+#include "ladder.h"
 
 namespace iclr17 {
 namespace {
 
-constexpr int kStepChunk = 4096;     // latents per bit partial: aux.hip's kRateChunk
-constexpr int kStepThreads = 256;
 constexpr int kStepBwdPixels = 16;   // pixels per workgroup (and per partial row) of the backward
 constexpr size_t kStepLdsMax = 64 * 1024;
 
@@ -39,43 +37,33 @@ __device__ __forceinline__ void stage_step_pack(const float* __restrict__ rp, in
 
 // One workgroup per (image, 4096-element chunk of its NHWC latent). noise is NCHW, as
 // ImageCompressor._latent_noise draws it and conv3's noise quantiser reads it.
-__global__ void __launch_bounds__(kStepThreads) step_noise_rate_kernel(
+__global__ void __launch_bounds__(kThreads) step_noise_rate_kernel(
     const float* __restrict__ y, const float* __restrict__ noise, int C, int HW,
     const float* __restrict__ steps, const float* __restrict__ rp, float* __restrict__ z_out,
     float* __restrict__ y_deq, double* __restrict__ partial, int chunks) {
   extern __shared__ float sp[];   // [11][C]
-  __shared__ float red[4];
-  const int b = blockIdx.x / chunks, ch = blockIdx.x % chunks;
-  const float d = steps[b];
-  stage_step_pack(rp, C, d, sp);
   const long per_image = (long)C * HW;
-  const long lo = (long)ch * kStepChunk;
-  const long hi = lo + kStepChunk < per_image ? lo + kStepChunk : per_image;
+  const Chunk k = sweep_chunk(chunks, per_image);
+  const float d = steps[k.b];
+  stage_step_pack(rp, C, d, sp);
   float s = 0.f;
-  for (long j = lo + threadIdx.x; j < hi; j += kStepThreads) {
+  for (long j = k.lo + threadIdx.x; j < k.hi; j += kThreads) {
     const int c = (int)(j % C);
     const long p = j / C;
-    const long i = (long)b * per_image + j;
-    const float z = y[i] / d + noise[(long)b * per_image + (long)c * HW + p];
+    const long i = (long)k.b * per_image + j;
+    const float z = y[i] / d + noise[(long)k.b * per_image + (long)c * HW + p];
     z_out[i] = z;
     y_deq[i] = d * z;
     s += element_bits(z, sp, C, c);
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int w = 0; w < 4; ++w) t += (double)red[w];
-    partial[(long)b * chunks + ch] = t;
-  }
+  chunk_sum_store(s, k, chunks, partial);
 }
 
 // One workgroup per (image, block of 16 pixels). Thread t owns the channels t, t + blockDim, …:
 // for each it walks the block's pixels (a wave reads 64 consecutive channels of one pixel) with
 // the channel's 11 accumulators in registers and stores them itself: rate_partial[row][k][c],
 // row = b · blocks + block, slot 0 times Δ_b (∂/∂softplus(h1) = Δ · ∂/∂(softplus(h1)·Δ)).
-__global__ void __launch_bounds__(kStepThreads) step_noise_rate_bwd_kernel(
+__global__ void __launch_bounds__(kThreads) step_noise_rate_bwd_kernel(
     const float* __restrict__ z, const float* __restrict__ g_deq, int C, int HW,
     const float* __restrict__ steps, const float* __restrict__ rp, const float* __restrict__ g_bits,
     float* __restrict__ g_y, float* __restrict__ rate_partial, int blocks) {
@@ -122,8 +110,8 @@ __global__ void grad_recon_images_kernel(const float* __restrict__ recon,
 }
 
 int check_step_shape(const char* what, int B, int h, int w, int N, size_t* shm) {
-  ICLR17_REQUIRE(B > 0 && h > 0 && w > 0 && N > 0, ICLR17_EINVAL,
-                 "%s: bad shape B=%d h=%d w=%d N=%d", what, B, h, w, N);
+  const int rc = check_latent(what, B, h, w, N);
+  if (rc) return rc;
   *shm = (size_t)kRateRows * N * sizeof(float);
   ICLR17_REQUIRE(*shm <= kStepLdsMax - 64, ICLR17_EUNSUPPORTED, "%s: N=%d needs %zu bytes of LDS",
                  what, N, *shm);
@@ -151,7 +139,7 @@ int iclr17_step_noise_rate(const float* y, const float* noise, int B, int h, int
   const long blocks = (long)B * chunks;
   ICLR17_REQUIRE(blocks < (1L << 31), ICLR17_EUNSUPPORTED, "step_noise_rate: %ld workgroups",
                  blocks);
-  hipLaunchKernelGGL(step_noise_rate_kernel, dim3((unsigned)blocks), dim3(kStepThreads), shm,
+  hipLaunchKernelGGL(step_noise_rate_kernel, dim3((unsigned)blocks), dim3(kThreads), shm,
                      (hipStream_t)stream, y, noise, N, h * w, steps_dev, rate_packed, z, y_deq,
                      bits_partial, chunks);
   return check_launch("step_noise_rate");
@@ -176,7 +164,7 @@ int iclr17_step_noise_rate_bwd(const float* z, const float* g_deq, int B, int h,
   ICLR17_REQUIRE(blocks < (1L << 31), ICLR17_EUNSUPPORTED, "step_noise_rate_bwd: %ld workgroups",
                  blocks);
   // one thread per channel, whole waves, at most 256 (more channels: a thread owns several)
-  const int threads = N >= kStepThreads ? kStepThreads : (N + 63) / 64 * 64;
+  const int threads = N >= kThreads ? kThreads : (N + 63) / 64 * 64;
   hipLaunchKernelGGL(step_noise_rate_bwd_kernel, dim3((unsigned)blocks), dim3(threads), shm,
                      (hipStream_t)stream, z, g_deq, N, h * w, steps_dev, rate_packed, g_bits, g_y,
                      rate_partial, per);

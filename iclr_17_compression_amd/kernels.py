@@ -1220,9 +1220,7 @@ def _step_value(step: float, what: str) -> float:
 def pack_rate_step(rate_packed: Tensor, N: int, step: float) -> Tensor:
     """The step pack: ``rate_packed`` [11][N] with row 0 · step, so that F(step·u) is the packed
     model of u and every rate / entropy kernel codes ŷ = rint(y/step) unchanged."""
-    _check(rate_packed, "rate table")
-    if rate_packed.numel() != 11 * N:
-        raise Iclr17Error(f"iclr17: pack_rate_step: packed rate parameters are not [11][{N}]")
+    _rate_pack(rate_packed, N, "pack_rate_step")
     d = _step_value(step, "pack_rate_step")
     out = torch.empty_like(rate_packed)
     call("iclr17_pack_rate_step", _p(rate_packed), N, ctypes.c_float(d), _p(out),
@@ -1237,14 +1235,51 @@ def _step_status(status: Tensor, what: str) -> None:
         raise Iclr17Error(f"iclr17: {what}: " + "; ".join(why))
 
 
+def _quantiser_out(y: Tensor, want_hat: bool = True, status: Optional[Tensor] = None):
+    """What a quantiser wrapper passes: y contiguous, ŷ (None without ``want_hat``), Δ·ŷ and the
+    status word (a zeroed one unless given)."""
+    y = y.contiguous()
+    y_hat = torch.empty_like(y) if want_hat else None
+    if status is None:
+        status = torch.zeros(1, device=y.device, dtype=torch.int32)
+    return y, y_hat, torch.empty_like(y), status
+
+
+def _rate_pack(rate_packed: Tensor, N: int, what: str) -> None:
+    _check(rate_packed, "rate table")
+    if rate_packed.numel() != 11 * N:
+        raise Iclr17Error(f"iclr17: {what}: packed rate parameters are not [11][{N}]")
+
+
+def _steps_arg(steps: Sequence[float], what: str, ladder: bool = False):
+    """Step sizes as the fp32 array the library reads and their number: 1..32 of them, or with
+    ``ladder`` the 32 of a step ladder."""
+    ds = [_step_value(s, what) for s in steps]
+    S = len(ds)
+    if ladder and S != SWEEP_MAX_STEPS:
+        raise Iclr17Error(f"iclr17: {what}: {S} ladder steps ({SWEEP_MAX_STEPS})")
+    if not 1 <= S <= SWEEP_MAX_STEPS:
+        raise Iclr17Error(f"iclr17: {what}: {S} steps (1..{SWEEP_MAX_STEPS})")
+    return ctypes.cast((ctypes.c_float * S)(*ds), ctypes.c_void_p), S
+
+
+def _sweep_args(y: Tensor, steps: Sequence[float], what: str, ladder: bool = False,
+                partials: str = "iclr17_rate_sweep_partials"):
+    """A sweep's step array, S, its float64 partials [B·S·T] and its result [B, S], for y
+    [B,h,w,N] already checked."""
+    B, h, w, N = y.shape
+    arr, S = _steps_arg(steps, what, ladder)
+    T = query(partials, h, w, N)
+    partial = torch.empty(B * S * max(T, 1), device=y.device, dtype=torch.float64)
+    return arr, S, partial, torch.empty(B, S, device=y.device, dtype=torch.float64)
+
+
 def quantise_step(y: Tensor, step: float):
     """y (fp32, any shape) → (ŷ = rint(y/step), integer-valued fp32; step·ŷ), one pass. Raises on
     a NaN and on |ŷ| > 32767 (what the entropy coder cannot carry)."""
     _check(y, "latent")
     d = _step_value(step, "quantise_step")
-    y = y.contiguous()
-    y_hat, y_deq = torch.empty_like(y), torch.empty_like(y)
-    status = torch.zeros(1, device=y.device, dtype=torch.int32)
+    y, y_hat, y_deq, status = _quantiser_out(y)
     call("iclr17_quantise_step", _p(y), y.numel(), ctypes.c_float(d), _p(y_hat), _p(y_deq),
          _p(status), _stream(y))
     _step_status(status, "quantise_step")
@@ -1267,20 +1302,11 @@ def rate_sweep(y: Tensor, rate_packed: Tensor, steps: Sequence[float]) -> Tensor
     estimated bits of each image at each step, from one read of y; per step what
     ``rate_bits(quantise_step(y, Δ)[0] as NCHW-shaped, pack_rate_step(…, Δ))`` sums to."""
     _check(y, "latent", 4)
-    _check(rate_packed, "rate table")
     B, h, w, N = y.shape
-    if rate_packed.numel() != 11 * N:
-        raise Iclr17Error(f"iclr17: rate_sweep: packed rate parameters are not [11][{N}]")
-    ds = [_step_value(s, "rate_sweep") for s in steps]
-    S = len(ds)
-    if not 1 <= S <= SWEEP_MAX_STEPS:
-        raise Iclr17Error(f"iclr17: rate_sweep: {S} steps (1..{SWEEP_MAX_STEPS})")
-    T = query("iclr17_rate_sweep_partials", h, w, N)
-    partial = torch.empty(B * S * max(T, 1), device=y.device, dtype=torch.float64)
-    bits = torch.empty(B, S, device=y.device, dtype=torch.float64)
-    arr = (ctypes.c_float * S)(*ds)
-    call("iclr17_rate_sweep", _p(y.contiguous()), B, h, w, N, _p(rate_packed),
-         ctypes.cast(arr, ctypes.c_void_p), S, _p(partial), _p(bits), _stream(y))
+    _rate_pack(rate_packed, N, "rate_sweep")
+    arr, S, partial, bits = _sweep_args(y, steps, "rate_sweep")
+    call("iclr17_rate_sweep", _p(y.contiguous()), B, h, w, N, _p(rate_packed), arr, S,
+         _p(partial), _p(bits), _stream(y))
     return bits
 
 
@@ -1305,12 +1331,8 @@ def quantise_steps_device(y: Tensor, steps_dev: Tensor, want_hat: bool = True,
     """``quantise_steps`` without the status read: → (ŷ | None, Δ_b·ŷ, status int32 [1] on the
     device, ``quantise_step``'s bits). ``status`` (zeroed by the caller) is used when given."""
     steps_dev = _steps_dev(y, steps_dev, "quantise_steps")
-    y = y.contiguous()
+    y, y_hat, y_deq, status = _quantiser_out(y, want_hat, status)
     B = y.shape[0]
-    y_hat = torch.empty_like(y) if want_hat else None
-    y_deq = torch.empty_like(y)
-    if status is None:
-        status = torch.zeros(1, device=y.device, dtype=torch.int32)
     call("iclr17_quantise_steps", _p(y), B, y.numel() // B, _p(steps_dev), _p(y_hat), _p(y_deq),
          _p(status), _stream(y))
     return y_hat, y_deq, status
@@ -1331,16 +1353,9 @@ def distortion_sweep(y: Tensor, weights: Tensor, steps: Sequence[float]) -> Tens
     weighted squared quantisation error of each image at each step from one read of y. Bitwise
     reproducible and independent of the batch."""
     B, h, w, N, weights = _channel_weights(y, weights, "distortion_sweep", "weights")
-    ds = [_step_value(s, "distortion_sweep") for s in steps]
-    S = len(ds)
-    if not 1 <= S <= SWEEP_MAX_STEPS:
-        raise Iclr17Error(f"iclr17: distortion_sweep: {S} steps (1..{SWEEP_MAX_STEPS})")
-    T = query("iclr17_rate_sweep_partials", h, w, N)
-    partial = torch.empty(B * S * max(T, 1), device=y.device, dtype=torch.float64)
-    out = torch.empty(B, S, device=y.device, dtype=torch.float64)
-    arr = (ctypes.c_float * S)(*ds)
-    call("iclr17_distortion_sweep", _p(y.contiguous()), B, h, w, N, _p(weights),
-         ctypes.cast(arr, ctypes.c_void_p), S, _p(partial), _p(out), _stream(y))
+    arr, S, partial, out = _sweep_args(y, steps, "distortion_sweep")
+    call("iclr17_distortion_sweep", _p(y.contiguous()), B, h, w, N, _p(weights), arr, S,
+         _p(partial), _p(out), _stream(y))
     return out
 
 
@@ -1359,17 +1374,8 @@ def _channel_weights(y: Tensor, lam: Tensor, what: str, name: str):
 # ------------------------------------- rate–distortion optimised quantisation (csrc/rdoq.hip)
 def _rdo_args(y: Tensor, rate_packed: Tensor, lam: Tensor, what: str):
     _check(y, "latent", 4)
-    _check(rate_packed, "rate table")
-    B, h, w, N = y.shape
-    if rate_packed.numel() != 11 * N:
-        raise Iclr17Error(f"iclr17: {what}: packed rate parameters are not [11][{N}]")
-    if not isinstance(lam, torch.Tensor) or lam.dtype != torch.float32 or lam.device != y.device \
-            or tuple(lam.shape) != (N,):
-        raise Iclr17Error(f"iclr17: {what}: lam must be an fp32 tensor of shape [{N}] on the "
-                          "latent's device")
-    if not bool((torch.isfinite(lam) & (lam >= 0)).all()):
-        raise Iclr17Error(f"iclr17: {what}: lam must be finite and >= 0")
-    return B, h, w, N, lam.contiguous()
+    _rate_pack(rate_packed, y.shape[3], what)
+    return _channel_weights(y, lam, what, "lam")
 
 
 def quantise_rdo(y: Tensor, rate_packed: Tensor, step: float, lam: Tensor):
@@ -1380,12 +1386,10 @@ def quantise_rdo(y: Tensor, rate_packed: Tensor, step: float, lam: Tensor):
     ``quantise_step``."""
     B, h, w, N, lam = _rdo_args(y, rate_packed, lam, "quantise_rdo")
     d = _step_value(step, "quantise_rdo")
-    y = y.contiguous()
-    y_hat, y_deq = torch.empty_like(y), torch.empty_like(y)
+    y, y_hat, y_deq, status = _quantiser_out(y)
     T = query("iclr17_rate_sweep_rdo_partials", h, w, N)
     partial = torch.empty(B * max(T, 1), device=y.device, dtype=torch.float64)
     bits = torch.empty(B, device=y.device, dtype=torch.float64)
-    status = torch.zeros(1, device=y.device, dtype=torch.int32)
     call("iclr17_quantise_rdo", _p(y), B, h, w, N, _p(rate_packed), ctypes.c_float(d), _p(lam),
          _p(y_hat), _p(y_deq), _p(partial), _p(bits), _p(status), _stream(y))
     _step_status(status, "quantise_rdo")
@@ -1396,20 +1400,14 @@ def rate_sweep_rdo(y: Tensor, rate_packed: Tensor, steps: Sequence[float], lam: 
     """``rate_sweep`` with ``quantise_rdo``'s choice inside → float64 [B, S]: column s is
     ``quantise_rdo(y, rate_packed, steps[s], lam)``'s bits, every step from one read of y."""
     B, h, w, N, lam = _rdo_args(y, rate_packed, lam, "rate_sweep_rdo")
-    ds = [_step_value(s, "rate_sweep_rdo") for s in steps]
-    S = len(ds)
-    if not 1 <= S <= SWEEP_MAX_STEPS:
-        raise Iclr17Error(f"iclr17: rate_sweep_rdo: {S} steps (1..{SWEEP_MAX_STEPS})")
-    T = query("iclr17_rate_sweep_rdo_partials", h, w, N)
-    partial = torch.empty(B * S * max(T, 1), device=y.device, dtype=torch.float64)
-    bits = torch.empty(B, S, device=y.device, dtype=torch.float64)
-    arr = (ctypes.c_float * S)(*ds)
-    call("iclr17_rate_sweep_rdo", _p(y.contiguous()), B, h, w, N, _p(rate_packed),
-         ctypes.cast(arr, ctypes.c_void_p), S, _p(lam), _p(partial), _p(bits), _stream(y))
+    arr, S, partial, bits = _sweep_args(y, steps, "rate_sweep_rdo",
+                                        partials="iclr17_rate_sweep_rdo_partials")
+    call("iclr17_rate_sweep_rdo", _p(y.contiguous()), B, h, w, N, _p(rate_packed), arr, S,
+         _p(lam), _p(partial), _p(bits), _stream(y))
     return bits
 
 
-# ------------------------------------------------------- per-block steps (csrc/stepmap.hip, rans.hip)
+# ------------------------------------------- per-block steps (csrc/stepmap.hip, ratectl.hip, rans.hip)
 MAP_BLOCKS = (1, 2, 4, 8, 16)   # block edges g of a step map, in latent positions
 
 
@@ -1435,13 +1433,6 @@ def _map_on(device, m, what: str, name: str, B: int, h: int, w: int, block: int,
     return torch.from_numpy(np.ascontiguousarray(a.astype(dtype))).to(device)
 
 
-def _ladder_arg(steps: Sequence[float], what: str):
-    ds = [_step_value(s, what) for s in steps]
-    if len(ds) != SWEEP_MAX_STEPS:
-        raise Iclr17Error(f"iclr17: {what}: {len(ds)} ladder steps ({SWEEP_MAX_STEPS})")
-    return ctypes.cast((ctypes.c_float * SWEEP_MAX_STEPS)(*ds), ctypes.c_void_p)
-
-
 def quantise_step_map(y: Tensor, indices, block: int, steps: Sequence[float]):
     """y fp32 NHWC [B,h,w,N], ladder indices per block ([B, mh, mw], each 0..31; ``map_shape``)
     and the 32 ladder step sizes → (ŷ = rint(y/Δ), Δ·ŷ) with Δ = steps[index of the element's
@@ -1450,10 +1441,8 @@ def quantise_step_map(y: Tensor, indices, block: int, steps: Sequence[float]):
     B, h, w, N = y.shape
     idx = _map_on(y.device, indices, "quantise_step_map", "indices", B, h, w, block, 0,
                   SWEEP_MAX_STEPS - 1, np.uint8)
-    arr = _ladder_arg(steps, "quantise_step_map")
-    y = y.contiguous()
-    y_hat, y_deq = torch.empty_like(y), torch.empty_like(y)
-    status = torch.zeros(1, device=y.device, dtype=torch.int32)
+    arr, _ = _steps_arg(steps, "quantise_step_map", ladder=True)
+    y, y_hat, y_deq, status = _quantiser_out(y)
     call("iclr17_quantise_step_map", _p(y), B, h, w, N, _p(idx), MAP_BLOCKS.index(block), arr,
          _p(y_hat), _p(y_deq), _p(status), _stream(y))
     _step_status(status, "quantise_step_map")
@@ -1466,7 +1455,7 @@ def dequantise_step_map(y_hat: Tensor, indices, block: int, steps: Sequence[floa
     B, h, w, N = y_hat.shape
     idx = _map_on(y_hat.device, indices, "dequantise_step_map", "indices", B, h, w, block, 0,
                   SWEEP_MAX_STEPS - 1, np.uint8)
-    arr = _ladder_arg(steps, "dequantise_step_map")
+    arr, _ = _steps_arg(steps, "dequantise_step_map", ladder=True)
     y_hat = y_hat.contiguous()
     out = torch.empty_like(y_hat)
     call("iclr17_dequantise_step_map", _p(y_hat), B, h, w, N, _p(idx), MAP_BLOCKS.index(block), arr,
@@ -1480,16 +1469,11 @@ def rate_sweep_offsets(y: Tensor, rate_packed: Tensor, steps: Sequence[float], o
     −31..31) → float64 [B, 32]: row s sums every element at step clamp(s + offset, 0, 31). Zero
     offsets give ``rate_sweep(y, rate_packed, steps)`` bit for bit."""
     _check(y, "latent", 4)
-    _check(rate_packed, "rate table")
     B, h, w, N = y.shape
-    if rate_packed.numel() != 11 * N:
-        raise Iclr17Error(f"iclr17: rate_sweep_offsets: packed rate parameters are not [11][{N}]")
+    _rate_pack(rate_packed, N, "rate_sweep_offsets")
     off = _map_on(y.device, offsets, "rate_sweep_offsets", "offsets", B, h, w, block,
                   1 - SWEEP_MAX_STEPS, SWEEP_MAX_STEPS - 1, np.int8)
-    arr = _ladder_arg(steps, "rate_sweep_offsets")
-    T = query("iclr17_rate_sweep_partials", h, w, N)
-    partial = torch.empty(B * SWEEP_MAX_STEPS * max(T, 1), device=y.device, dtype=torch.float64)
-    bits = torch.empty(B, SWEEP_MAX_STEPS, device=y.device, dtype=torch.float64)
+    arr, _, partial, bits = _sweep_args(y, steps, "rate_sweep_offsets", ladder=True)
     call("iclr17_rate_sweep_offsets", _p(y.contiguous()), B, h, w, N, _p(rate_packed), arr, _p(off),
          MAP_BLOCKS.index(block), _p(partial), _p(bits), _stream(y))
     return bits

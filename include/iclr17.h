@@ -346,7 +346,7 @@ int iclr17_rate_sweep_rdo(const float* y, int B, int h, int w, int N, const floa
                           const float* steps, int S, const float* lam, double* partial,
                           double* bits, void* stream);
 
-/* ------------------------------------------------------ per-block steps (csrc/stepmap.hip, rans.hip)
+/* ------------------------------------------ per-block steps (csrc/stepmap.hip, ratectl.hip, rans.hip)
  * A quantiser step per block of latent positions: region-of-interest coding. A
  * block is g×g positions of the h×w latent, g = 2^log2_g with log2_g = 0..4; a map holds
  * mh×mw = ⌈h/g⌉×⌈w/g⌉ entries per image, row-major, position (i, j) reading entry

@@ -192,6 +192,65 @@ def test_quantise_is_exact(device):
         kernels.quantise_step(yd, 0.0)
 
 
+# ------------------------------------------------------------------ 3b. one body, three sources
+def test_step_sources_agree(device, nets):
+    """The quantiser has one body and three step sources (a scalar, a step per image, the ladder
+    at a block's index) and the rate sweep two (its steps, the ladder at a clamped offset): on one
+    input they give the same bits, and the same errors."""
+    big = tie_free((3, 5, 7, 128), 5, -60.0, 60.0)   # 13440 elements: the last workgroup is
+    one = tie_free((1, 1, 1, 128), 6, -9.0, 9.0)     # partial, the maps of 4 and 16 are ragged
+    for y_np, index in ((big, (0, 8, 31)), (one, (8,))):
+        y = torch.from_numpy(y_np).to(device)
+        B, h, w, _ = y.shape
+        deltas = torch.tensor([DELTAS[s] for s in index], device=device, dtype=torch.float32)
+        hat_b, deq_b = kernels.quantise_steps(y, deltas)
+        maps = {g: np.stack([np.full(kernels.map_shape(h, w, g), s, np.uint8) for s in index])
+                for g in (1, 4, 16)}
+        mapped = {g: kernels.quantise_step_map(y, maps[g], g, DELTAS) for g in maps}
+        for b, s in enumerate(index):
+            hat, deq = kernels.quantise_step(y[b], DELTAS[s])
+            for got_hat, got_deq in [(hat_b, deq_b)] + list(mapped.values()):
+                assert torch.equal(got_hat[b].view(torch.int32), hat.view(torch.int32)), (b, s)
+                assert torch.equal(got_deq[b].view(torch.int32), deq.view(torch.int32)), (b, s)
+            assert torch.equal(kernels.dequantise_step(hat, DELTAS[s]).view(torch.int32),
+                               deq.view(torch.int32))
+        for g in maps:
+            assert torch.equal(kernels.dequantise_step_map(hat_b, maps[g], g, DELTAS)
+                               .view(torch.int32), deq_b.view(torch.int32)), g
+
+    # the same refusal through every source: Δ = 0.25 as a scalar, per image and as ladder entry 5
+    y = torch.from_numpy(big).to(device)
+    ladder = list(DELTAS)
+    ladder[5] = 0.25
+    quarter = torch.full((3,), 0.25, device=device)
+    fives = np.full((3,) + kernels.map_shape(5, 7, 4), 5, np.uint8)
+    for value in (float("nan"), 8192.0):
+        bad = y.clone()
+        bad[2, 4, 6, 127] = value   # the last element
+        said = []
+        for name, run in (("quantise_step", lambda: kernels.quantise_step(bad, 0.25)),
+                          ("quantise_steps", lambda: kernels.quantise_steps(bad, quarter)),
+                          ("quantise_step_map",
+                           lambda: kernels.quantise_step_map(bad, fives, 4, ladder))):
+            with pytest.raises(kernels.Iclr17Error) as err:
+                run()
+            head = f"iclr17: {name}: "
+            assert str(err.value).startswith(head), str(err.value)
+            said.append(str(err.value)[len(head):])
+        assert said[0] and said.count(said[0]) == 3, said
+        assert ("NaN" if value != value else "> 32767") in said[0]
+
+    # one offset c for a whole image: row s of the offset sweep is row clamp(s + c) of rate_sweep
+    pack = nets(128).bitEstimator.packed()
+    rows = kernels.rate_sweep(y, pack, DELTAS)
+    for c in (-3, 5):
+        for g in (1, 4):
+            off = np.full((3,) + kernels.map_shape(5, 7, g), c, np.int8)
+            got = kernels.rate_sweep_offsets(y, pack, DELTAS, off, g)
+            want = rows[:, [min(max(s + c, 0), 31) for s in ALL_STEPS]]
+            assert torch.equal(got.view(torch.int64), want.view(torch.int64)), (c, g)
+
+
 def test_step_pack_and_its_cache(device, nets):
     net = make_net(128, device)   # its own: a parameter changes below
     be = net.bitEstimator
