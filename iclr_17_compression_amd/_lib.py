@@ -103,6 +103,8 @@ SIGNATURES = {
     "iclr17_quantise_steps": (_I, [_P, _I, _I64, _P, _P, _P, _P, _P]),
     "iclr17_distortion_sweep": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "iclr17_image_sse_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "iclr17_image_msssim_workspace_size": (_SZ, [_I, _I, _I]),
+    "iclr17_image_msssim_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _SZ, _P, _P, _P]),
     "iclr17_rate_sweep_rdo_partials": (_I, [_I, _I, _I]),
     "iclr17_quantise_rdo": (_I, [_P, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
     "iclr17_rate_sweep_rdo": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),

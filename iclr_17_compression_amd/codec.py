@@ -111,6 +111,16 @@ I17T): encoder-side only. A target index 0 misses raises; ``psnr`` with another 
 or ``step_offsets`` raises (the last two: not built). No claim is made about the rate–distortion
 trade away from Δ = 1.
 
+MS-SSIM targets. ``compress_images(..., msssim=T)`` (0 < T < 1) is the same request
+in the measure the model is trained and compared in: an index passes when the fp32 MS-SSIM of its
+8-bit decode against the original, over the image's own H×W and read as a float64, is ≥ T (NaN does
+not pass). The search is ``search_quality``'s plain bisection (at most 6 probes); the probe
+(``msssim_probe``) is ``quality_probe`` with ``kernels.image_msssim`` as its last step, whose value
+is bit for bit what ``evaluate_images(want_msssim=True)`` reports for the decode at that index.
+Both sides of an image must be at least 161 (five levels of an 11-tap window): a smaller image
+raises on the host, before the ingest. Blobs, ``tile`` and the combinations that raise are as for
+``psnr``; ``estimate=True`` raises too (``distortion_sweep`` predicts squared error).
+
 Region decode. ``decompress_region(blob, box)`` returns the pixels of ``box`` = (x0, y0, x1, y1)
 (half-open, inside the image), byte for byte the crop of the full decode, from the tiles it needs
 alone. The synthesis is deconv 5×5/s2/p2, IGDN, deconv 5×5/s2/p2, IGDN, deconv 9×9/s4/p4; IGDN is
@@ -122,13 +132,14 @@ streams are decoded into a compact latent, which is dequantised and synthesised 
 its own, and ``image_egress`` runs on the crop.
 
     python -m iclr_17_compression_amd.codec encode IN.png OUT.i17c --weights CKPT [--N 192]
-                                            [--step S | --max-bytes B | --bpp R | --psnr T]
+                                            [--step S | --max-bytes B | --bpp R | --psnr T |
+                                             --msssim T]
                                             [--roi X0,Y0,X1,Y1,OFF ...] [--block G] [--rdo L]
                                             [--tile T]
     python -m iclr_17_compression_amd.codec decode IN.i17c OUT.png --weights CKPT
                                             [--region X0,Y0,X1,Y1]
     python -m iclr_17_compression_amd.codec eval IMG... --weights CKPT [--ms-ssim] [--steps 4,8,12]
-                                            [--rdo L] [--psnr T]
+                                            [--rdo L] [--psnr T | --msssim T]
 """
 from __future__ import annotations
 
@@ -259,6 +270,31 @@ def psnr_value(psnr) -> float:
     return t
 
 
+def msssim_value(msssim) -> float:
+    """An MS-SSIM target checked on the host: a real number, not a bool, finite, 0 < T < 1."""
+    if isinstance(msssim, bool) or not isinstance(msssim, (int, float, np.integer, np.floating)):
+        raise Iclr17Error(f"iclr17: codec: msssim must be a real number (got {msssim!r})")
+    t = float(msssim)
+    if not (math.isfinite(t) and 0.0 < t < 1.0):
+        raise Iclr17Error(f"iclr17: codec: msssim must be finite, > 0 and < 1 (got {msssim!r})")
+    return t
+
+
+# one image of an MS-SSIM search: its name in messages, the target and its size
+MsssimTarget = namedtuple("MsssimTarget", "label msssim H W")
+
+
+def msssim_passes(target, value) -> bool:
+    """``search_quality``'s pass rule of an MS-SSIM target: the measured fp32 MS-SSIM, read as a
+    float64, is ≥ the target. Nothing is rounded to dB; NaN does not pass."""
+    return float(value) >= target.msssim
+
+
+def msssim_failure(target, value) -> str:
+    return (f"iclr17: codec: {target.label} cannot reach MS-SSIM {target.msssim!r}: the finest step "
+            f"(index 0) gives {float(value)!r}")
+
+
 def sse_limit(H: int, W: int, psnr) -> int:
     """The largest integer SSE of an 8-bit H×W RGB image that still reaches ``psnr`` dB:
     ⌊255²·3·H·W·10^(−psnr/10)⌋, evaluated in float64. A ladder index *passes* when the integer SSE
@@ -281,7 +317,17 @@ def _guided_guess(seed, limit: int, sse0: int) -> int:
     return max(ok) if ok else -1
 
 
-def search_quality(probe, n: int, seeds=None, targets=None) -> QualityResult:
+def sse_passes(target, sse) -> bool:
+    return sse <= target.limit
+
+
+def psnr_failure(target, sse) -> str:
+    return (f"iclr17: codec: {target.label} cannot reach {target.psnr:g} dB: the finest step "
+            f"(index 0) gives {_psnr_of(sse, target.H, target.W):.4f} dB")
+
+
+def search_quality(probe, n: int, seeds=None, targets=None, passes=None,
+                   failure=None) -> QualityResult:
     """The search of a quality target for ``n`` images (a pure host function: the measuring is
     ``probe``). ``targets``: one ``QualityTarget`` per image. Per image the bracket L < F holds an
     index that passed (L, −1 at first: virtual) and one that failed (F, 32 at first: virtual).
@@ -296,7 +342,15 @@ def search_quality(probe, n: int, seeds=None, targets=None) -> QualityResult:
     bisection) image k first probes UNIT_STEP, then the coarsest index that the prediction
     calibrated on that probe passes (``_guided_guess``, moved inside the bracket), then that
     index's neighbour on the side of the boundary, then bisects: ``MAX_PROBES`` = 8 at most. An
-    image's sequence depends on its own seed, limit and measurements alone."""
+    image's sequence depends on its own seed, limit and measurements alone.
+
+    ``passes(target, value)`` and ``failure(target, value at index 0)`` (the message of a target
+    that index 0 misses) make the same search serve another measure: by default the probe's values
+    are integer SSEs against ``target.limit``; with ``passes`` they are kept as the probe returns
+    them (``msssim_passes`` / ``msssim_failure``: fp32 MS-SSIM values, seeds unused)."""
+    convert = int if passes is None else (lambda e: e)
+    passes = sse_passes if passes is None else passes
+    failure = psnr_failure if failure is None else failure
     if targets is None or len(targets) != n or (seeds is not None and len(seeds) != n):
         raise Iclr17Error(f"iclr17: codec: search_quality takes one target (and seed) per image "
                           f"for {n} images")
@@ -330,17 +384,16 @@ def search_quality(probe, n: int, seeds=None, targets=None) -> QualityResult:
         for k, s, e in zip(todo, indices, sses):
             if not lo[k] < s < hi[k] or len(seen[k]) >= MAX_PROBES:
                 raise Iclr17Error("iclr17: codec: search_quality: probe outside its bracket or cap")
-            seen[k][s] = int(e)
+            seen[k][s] = convert(e)
             last[k] = s
-            if int(e) <= targets[k].limit:
+            if passes(targets[k], seen[k][s]):
                 lo[k] = s
             else:
                 hi[k] = s
         todo = [k for k in todo if hi[k] > lo[k] + 1]
     for k, t in enumerate(targets):
         if lo[k] < 0:
-            raise Iclr17Error(f"iclr17: codec: {t.label} cannot reach {t.psnr:g} dB: the finest step "
-                              f"(index 0) gives {_psnr_of(seen[k][0], t.H, t.W):.4f} dB")
+            raise Iclr17Error(failure(t, seen[k][0]))
     return QualityResult(list(lo), [len(v) for v in seen], [seen[k][lo[k]] for k in range(n)],
                          guesses)
 
@@ -707,12 +760,33 @@ PSNR_WITH_MAP = ("iclr17: codec: psnr with step_offsets / a step map: a quality 
                  "per-block steps is not built")
 
 
+MSSSIM_WITH_RDO = ("iclr17: codec: msssim with rdo: a quality target over rate–distortion optimised "
+                   "levels is not built")
+MSSSIM_WITH_MAP = ("iclr17: codec: msssim with step_offsets / a step map: a quality target over "
+                   "per-block steps is not built")
+MSSSIM_WITH_ESTIMATE = ("iclr17: codec: msssim with estimate=True: a guided probe order for "
+                        "MS-SSIM is not built (distortion_sweep predicts squared error)")
+
+
+def _per_image(name: str, value, n: int, check) -> List[float]:
+    """A scalar or one value per image of a quality target, each through ``check``."""
+    if isinstance(value, (list, tuple)):    # element by element: an array would turn a bool
+        per = list(value)                   # among floats into 1.0
+    else:
+        per = [value] * n if np.ndim(value) == 0 else list(np.asarray(value).reshape(-1))
+    if len(per) != n:
+        raise Iclr17Error(f"iclr17: codec: {name} has {len(per)} values for {n} images")
+    return [check(v.item() if isinstance(v, np.generic) else v) for v in per]
+
+
 def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None, rdo=None,
-                 tile=None, psnr=None):
+                 tile=None, psnr=None, msssim=None, estimate: bool = False):
     """The rate options of ``compress_images`` for ``n`` images, checked on the host before any
     device use → None (the plain path), ("step", index), ("budget", per-image values, is_bpp) or,
     for ``psnr`` (a quality target in dB, a scalar or one value per image; not with another rate
-    option, ``rdo`` or ``step_offsets``; with ``tile``), ("quality", per-image values).
+    option, ``rdo`` or ``step_offsets``; with ``tile``), ("quality", per-image values), or, for
+    ``msssim`` (an MS-SSIM target in (0, 1), the fifth rate option, under ``psnr``'s rules and not
+    with ``estimate=True``), ("msssim", per-image values).
     At most one option; a budget is a scalar or one value per image. ``step_offsets`` goes with
     any one of them, the option then giving the base index; alone it means the unit step. So does
     ``rdo`` (``rdo_value`` checks it); ``rdo`` with ``step_offsets`` raises. ``tile`` (the tile
@@ -729,24 +803,28 @@ def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None,
         rdo_value(rdo)
         if step_offsets is not None:
             raise Iclr17Error(RDO_WITH_MAP)
-    given = [k for k, v in (("step", step), ("max_bytes", max_bytes), ("bpp", bpp), ("psnr", psnr))
-             if v is not None]
+    given = [k for k, v in (("step", step), ("max_bytes", max_bytes), ("bpp", bpp), ("psnr", psnr),
+                            ("msssim", msssim)) if v is not None]
     if len(given) > 1:
         raise Iclr17Error(f"iclr17: codec: {' and '.join(given)} given together (at most one of "
-                          f"step, max_bytes, bpp{'' if psnr is None else ', psnr'})")
+                          f"step, max_bytes, bpp{'' if psnr is None else ', psnr'}"
+                          f"{'' if msssim is None else ', msssim'})")
     if psnr is not None:
-        if isinstance(psnr, (list, tuple)):     # element by element: an array would turn a bool
-            per = list(psnr)                    # among floats into 1.0
-        else:
-            per = [psnr] * n if np.ndim(psnr) == 0 else list(np.asarray(psnr).reshape(-1))
-        if len(per) != n:
-            raise Iclr17Error(f"iclr17: codec: psnr has {len(per)} values for {n} images")
-        per = [psnr_value(v.item() if isinstance(v, np.generic) else v) for v in per]
+        per = _per_image("psnr", psnr, n, psnr_value)
         if rdo is not None:
             raise Iclr17Error(PSNR_WITH_RDO)
         if step_offsets is not None:
             raise Iclr17Error(PSNR_WITH_MAP)
         return "quality", per
+    if msssim is not None:
+        per = _per_image("msssim", msssim, n, msssim_value)
+        if rdo is not None:
+            raise Iclr17Error(MSSSIM_WITH_RDO)
+        if step_offsets is not None:
+            raise Iclr17Error(MSSSIM_WITH_MAP)
+        if estimate:
+            raise Iclr17Error(MSSSIM_WITH_ESTIMATE)
+        return "msssim", per
     if not given:
         return None if step_offsets is None and rdo is None else ("step", UNIT_STEP)
     if step is not None:
@@ -773,19 +851,27 @@ def quality_seeds(net, y) -> np.ndarray:
     return 255.0 ** 2 * net.distortion_sweep(y, latent=True).cpu().numpy()
 
 
-def quality_probe(net, y, packed, offsets, shapes):
+# What a probe measures on the device: the kernel's name in messages, its *_device wrapper, the
+# bytes and dtype of a value in the buffer that comes back, and the host type of a value.
+Measure = namedtuple("Measure", "what device_fn size dtype host")
+SSE_MEASURE = Measure("image_sse", kernels.image_sse_device, 8, torch.int64, int)
+MSSSIM_MEASURE = Measure("image_msssim", kernels.image_msssim_device, 4, torch.float32, float)
+
+
+def quality_probe(net, y, packed, offsets, shapes, measure: Measure = SSE_MEASURE):
     """``search_quality``'s probe of one canvas batch: ``y`` its NHWC latent, ``packed`` /
     ``offsets`` / ``shapes`` the uploaded originals as ``upload_packed`` returns them. A call
     quantises every member at its own index (kernels.quantise_steps), runs the synthesis of the
     current precision mode as ``decompress`` does and sums the squared 8-bit error on the device
     (kernels.image_sse): no entropy coding, no 8-bit pixels, and 8·members + 8 bytes come back.
     The sums are those of the real decode at that index. Raises as ``quantise_step`` and
-    ``image_egress`` do (in h3: ``H3_RANGE_MESSAGE``)."""
+    ``image_egress`` do (in h3: ``H3_RANGE_MESSAGE``). With another ``measure`` the last step is
+    that kernel's (``msssim_probe``)."""
     from . import chain
     device = y.device
     B = y.shape[0]
     Hc, Wc = canvas(*shapes[0])
-    desc = kernels._image_desc("image_sse", packed.numel(), offsets, shapes, (Hc, Wc)).to(device)
+    desc = kernels._image_desc(measure.what, packed.numel(), offsets, shapes, (Hc, Wc)).to(device)
     ladder = torch.tensor([step_size(s) for s in range(STEPS)], dtype=torch.float32, device=device)
 
     def probe(members, indices):
@@ -797,20 +883,29 @@ def quality_probe(net, y, packed, offsets, shapes):
         m = chain.MODES[kernels.precision()]
         clipped, _, _ = m.synthesis(net.Decoder, y_deq, m.latent_operand(y_deq), None, False, False,
                                     None, False)
-        buf, _, _, spare = kernels.image_sse_device(clipped, None, None, packed,
-                                                    desc if whole else desc[pick].contiguous())
+        buf, _, _, spare = measure.device_fn(clipped, None, None, packed,
+                                             desc if whole else desc[pick].contiguous())
         spare.copy_(qstatus)
         host = buf.cpu()
         n = len(members)
-        words = host[8 * n:].view(torch.int32)
+        words = host[measure.size * n:].view(torch.int32)
         kernels._step_status(words[1:2], "quantise_steps")
         if int(words[0]):
             if kernels.precision() == "h3":
                 raise Iclr17Error(kernels.H3_RANGE_MESSAGE)
-            raise Iclr17Error("iclr17: image_sse: non-finite reconstruction")
-        return [int(v) for v in host[:8 * n].view(torch.int64)]
+            raise Iclr17Error(f"iclr17: {measure.what}: non-finite reconstruction")
+        return [measure.host(v) for v in host[:measure.size * n].view(measure.dtype)]
 
     return probe
+
+
+def msssim_probe(net, y, packed, offsets, shapes):
+    """``quality_probe`` measuring MS-SSIM (kernels.image_msssim) in place of the squared error:
+    per member the fp32 MS-SSIM of its 8-bit decode at its index against the original over its own
+    H×W, as a float — the value ``evaluate_images(step=index, want_msssim=True)`` reports, bit for
+    bit — and 4·members + 8 bytes come back. The images must be large enough for MS-SSIM
+    (kernels.check_msssim_shapes): the caller checks, before any device use."""
+    return quality_probe(net, y, packed, offsets, shapes, MSSSIM_MEASURE)
 
 
 def compress_images(net, images, max_batch: int = 64,
@@ -818,10 +913,14 @@ def compress_images(net, images, max_batch: int = 64,
                     K: int = kernels.ENTROPY_K, step: Optional[int] = None, max_bytes=None,
                     bpp=None, stats: Optional[dict] = None, step_offsets=None,
                     block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None,
-                    tile: Optional[int] = None, psnr=None, estimate: bool = DEFAULT_ESTIMATE
-                    ) -> List[bytes]:
+                    tile: Optional[int] = None, psnr=None, estimate: bool = DEFAULT_ESTIMATE,
+                    msssim=None) -> List[bytes]:
     imgs = [as_u8_hwc(im) for im in images]
-    request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets, rdo, tile, psnr)
+    request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets, rdo, tile, psnr, msssim,
+                           estimate)
+    if request is not None and request[0] == "msssim":   # on the host, before the ingest
+        sizes = [im.shape[:2] for im in imgs]
+        kernels.check_msssim_shapes(sizes, [f"image {i} ({H}x{W})" for i, (H, W) in enumerate(sizes)])
     how = {} if rdo is None else {"rdo": rdo, "rdo_weights": rdo_weights}
     per_image = None
     if step_offsets is not None:
@@ -867,6 +966,14 @@ def compress_images(net, images, max_batch: int = 64,
             chosen = found.indices
             for k, i in enumerate(idx):
                 probes[i], sses[i] = found.probes[k], found.sse[k]
+        elif request[0] == "msssim":
+            targets = [MsssimTarget(f"image {i} ({H}x{W})", request[1][i], H, W)
+                       for i, (H, W) in zip(idx, shapes)]
+            found = search_quality(msssim_probe(net, y, packed, offsets, shapes), len(idx), None,
+                                   targets, msssim_passes, msssim_failure)
+            chosen = found.indices
+            for k, i in enumerate(idx):
+                probes[i], sses[i] = found.probes[k], found.sse[k]
         else:
             est = (net.rate_sweep(y, latent=True, **how) if offs is None
                    else net.rate_sweep_offsets(y, offs, block)).cpu().numpy()
@@ -901,6 +1008,8 @@ def compress_images(net, images, max_batch: int = 64,
         stats["reencodes"] = reencodes
         if request is not None and request[0] == "quality":
             stats["probes"], stats["sse"] = probes, sses
+        if request is not None and request[0] == "msssim":
+            stats["probes"], stats["ms_ssim"] = probes, sses
     return blobs
 
 
@@ -1006,11 +1115,12 @@ def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
                     step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
                     block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None,
                     tile: Optional[int] = None, psnr=None,
-                    estimate: bool = DEFAULT_ESTIMATE) -> List[dict]:
+                    estimate: bool = DEFAULT_ESTIMATE, msssim=None) -> List[dict]:
     imgs = [as_u8_hwc(im) for im in images]
     blobs = compress_images(net, imgs, max_batch=max_batch, step=step, max_bytes=max_bytes, bpp=bpp,
                             step_offsets=step_offsets, block=block, rdo=rdo, rdo_weights=rdo_weights,
-                            tile=tile, psnr=psnr, estimate=estimate)
+                            tile=tile, psnr=psnr, estimate=estimate, msssim=msssim)
+    want_msssim = want_msssim or msssim is not None
     recons, sses = decode_groups(net, blobs, max_batch, refs=imgs)
     device = next(net.parameters()).device
     res = []
@@ -1095,6 +1205,10 @@ def build_parser() -> argparse.ArgumentParser:
     rate.add_argument("--psnr", type=float, default=None, metavar="T",
                       help="quality target in dB: the coarsest ladder index found whose 8-bit "
                            "decode reaches T (not with --rdo or --roi)")
+    rate.add_argument("--msssim", type=float, default=None, metavar="T",
+                      help="MS-SSIM target, 0 < T < 1: the coarsest ladder index found whose "
+                           "8-bit decode reaches T (not with --rdo or --roi; both sides of the "
+                           "image at least 161)")
     enc.add_argument("--roi", action="append", default=None, metavar="X0,Y0,X1,Y1,OFF",
                      help="a pixel box whose blocks get the ladder offset OFF (negative: finer); "
                           "repeatable, the finest offset wins where boxes overlap")
@@ -1122,6 +1236,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="rate-distortion optimised quantisation with lambda L >= 0")
     ev.add_argument("--psnr", type=float, default=None, metavar="T",
                     help="quality target in dB per image (not with --steps or --rdo)")
+    ev.add_argument("--msssim", type=float, default=None, metavar="T",
+                    help="MS-SSIM target per image (not with --steps, --rdo or --psnr)")
     return ap
 
 
@@ -1133,6 +1249,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if getattr(args, "steps", None):
             raise Iclr17Error("iclr17: codec: step and psnr given together (at most one of step, "
                               "max_bytes, bpp, psnr)")
+    if getattr(args, "msssim", None) is not None:   # the same, for the MS-SSIM target
+        rate_request(1, step=getattr(args, "step", None), rdo=args.rdo,
+                     psnr=getattr(args, "psnr", None), msssim=args.msssim,
+                     step_offsets=[None] if getattr(args, "roi", None) else None)
+        if getattr(args, "steps", None):
+            raise Iclr17Error("iclr17: codec: step and msssim given together (at most one of step, "
+                              "max_bytes, bpp, msssim)")
     net = _model(args)
     with kernels.precision_scope(args.precision or kernels.precision()):
         if args.cmd == "encode":
@@ -1142,7 +1265,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                        "block": args.block}
             blob = net.compress_images([image], step=args.step, max_bytes=args.max_bytes,
                                        bpp=args.bpp, rdo=args.rdo, tile=args.tile,
-                                       psnr=args.psnr, **roi)[0]
+                                       psnr=args.psnr, msssim=args.msssim, **roi)[0]
             with open(args.output, "wb") as f:
                 f.write(blob)
         elif args.cmd == "decode":
@@ -1159,17 +1282,20 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             steps = [int(t) for t in args.steps.split(",")] if args.steps else [None]
             for step in steps:
                 rows = net.evaluate_images(imgs, want_msssim=args.ms_ssim, step=step,
-                                           rdo=args.rdo, psnr=args.psnr)
+                                           rdo=args.rdo, psnr=args.psnr, msssim=args.msssim)
                 tag = {} if step is None else {"step": step}
                 if args.psnr is not None:
                     tag["psnr"] = args.psnr
+                if args.msssim is not None:
+                    tag["msssim"] = args.msssim
                 if args.rdo is not None:
                     tag["rdo"] = args.rdo
                 for p, im, r in zip(args.images, imgs, rows):
                     print(json.dumps({"name": p, **tag, "H": im.shape[0], "W": im.shape[1],
                                       "bytes": r["bytes"], "bpp": r["bpp"], "psnr_u8": r["psnr_u8"],
                                       "ms_ssim": r.get("ms_ssim"),
-                                      **({} if args.psnr is None else {"index": r["step"]})}))
+                                      **({} if args.psnr is None and args.msssim is None
+                                         else {"index": r["step"]})}))
                 ms = [r["ms_ssim"] for r in rows if r.get("ms_ssim") is not None]
                 print(json.dumps({"name": "mean", **tag, "images": len(rows),
                                   "bpp": float(np.mean([r["bpp"] for r in rows])),

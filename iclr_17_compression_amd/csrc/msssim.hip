@@ -20,6 +20,10 @@
 // The gradient path (the loss λ·(1 − MS-SSIM) + bpp; "Backward" below): saving variants of the
 // level kernel also write the per-pixel derivative maps, and one backward kernel per level, from
 // the coarsest up, turns them into dX / dY.
+//
+// iclr17_image_msssim_u8 (the probe of an MS-SSIM target) runs the same level,
+// pooling and finish kernels over a canvas batch of the image codec: images of different true
+// sizes, measured each over its own H×W on the 8-bit decode ("extent sources" below).
 #include <string.h>
 
 #include "common.h"
@@ -45,10 +49,15 @@ struct Level {
   int tiles;        // output tiles per plane
 };
 
+// What the finish kernel sums for image b at level l: n(l, b) partial pairs from first(l, b),
+// divided by mean_over(l, b).
 struct FinishPlan {
   long poff[LEVELS];     // first partial (doubles) of each level
   int tiles[LEVELS];     // tiles per plane
   double count[LEVELS];  // 3 · Ho · Wo
+  __device__ __forceinline__ long n(int l, int) const { return 3L * tiles[l]; }
+  __device__ __forceinline__ long first(int l, int b) const { return poff[l] + 2 * (long)b * n(l, b); }
+  __device__ __forceinline__ double mean_over(int l, int) const { return count[l]; }
 };
 
 // g·v + acc: one fused multiply-add (the filter's rounding differs from the reference's
@@ -63,37 +72,180 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// F.avg_pool2d(kernel 2, stride 2, padding n % 2): the next level's size
+__host__ __device__ inline int pooled(int n) { return (n + 2 * (n % 2) - 2) / 2 + 1; }
+
+// ------------------------------------------------------------------------- extent sources
+// The level, pooling and finish kernels are one body over an *extent source*, which says where a
+// plane's size and pixels come from (as ladder.h's step sources do for Δ):
+//   Uniform      every plane of the batch is H×W, dense fp32: iclr17_ms_ssim and the gradient path
+//   ImageU8      a canvas batch of the image codec at level 0: plane 3b + c is image b's own
+//                H_b×W_b (the descriptors) of the 8-bit decode of recon and of the packed uint8
+//                original, converted as they are read; no level-0 plane exists in memory
+//   ImagePlanes  the same batch at levels ≥ 1: image b's level size follows from its descriptor by
+//                `pooled`, its planes lie dense (row stride = its own width) in a slot of the
+//                canvas's level size
+// view(plane) gives the plane: H, W, x(r, c, bad) and y(r, c). A ragged source (kRagged) is
+// launched on the grid of the canvas; a workgroup beyond the image's own grid returns before any
+// barrier, and an image's partials are indexed by its own tile grid in (plane, tile row, tile
+// column) order from the first slot of the image, so that they are the partials, in the order,
+// of that image as a Uniform batch of one.
+struct PlaneView {
+  int H, W;
+  const float* __restrict__ xp;
+  const float* __restrict__ yp;
+  __device__ __forceinline__ float x(int r, int c, bool&) const { return xp[(long)r * W + c]; }
+  __device__ __forceinline__ float y(int r, int c) const { return yp[(long)r * W + c]; }
+};
+
+struct Uniform {
+  static constexpr bool kRagged = false;
+  const float* __restrict__ X;
+  const float* __restrict__ Y;
+  int H, W;
+  __device__ __forceinline__ PlaneView view(int plane) const {
+    return PlaneView{H, W, X + (long)plane * H * W, Y + (long)plane * H * W};
+  }
+  __device__ __forceinline__ void report(bool) const {}
+};
+
+// int64 descriptor row per image (imageio.hip): byte offset in the packed uint8 buffer, H, W, 0
+constexpr int kDescOff = 0, kDescH = 1, kDescW = 2, kDescN = 4;
+
+struct Extent {
+  int H, W;
+};
+
+// image b's size at `level`, from its (host-checked) descriptor, kept inside the canvas
+__device__ __forceinline__ Extent image_extent(const long* __restrict__ desc, int b, int Hc, int Wc,
+                                               int level) {
+  const long h = desc[(long)b * kDescN + kDescH], w = desc[(long)b * kDescN + kDescW];
+  Extent e{h < 1 ? 1 : (h > Hc ? Hc : (int)h), w < 1 ? 1 : (w > Wc ? Wc : (int)w)};
+  for (int l = 0; l < level; ++l) {
+    e.H = pooled(e.H);
+    e.W = pooled(e.W);
+  }
+  return e;
+}
+
+// X = the byte image_egress_u8 writes and Y = the original's byte, each times fl(1/255): the planes
+// codec.evaluate_images feeds iclr17_ms_ssim (torch divides a device tensor by the scalar 255 as
+// the product with the fp32 reciprocal, which is not the quotient for 126 of the 256 bytes), so
+// that a value here is the value reported there. bad: a recon value that is not finite.
+constexpr float kInv255 = 1.0f / 255.0f;
+
+struct U8View {
+  int H, W, Wc;
+  const float* __restrict__ rp;            // recon plane [Hc][Wc]
+  const unsigned char* __restrict__ yp;    // the image's HWC bytes, from this channel's first
+  __device__ __forceinline__ float x(int r, int c, bool& bad) const {
+    const float v = rp[(long)r * Wc + c];
+    bad |= (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
+    return rintf(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f) * kInv255;
+  }
+  __device__ __forceinline__ float y(int r, int c) const {
+    return (float)yp[((long)r * W + c) * 3] * kInv255;
+  }
+};
+
+struct ImageU8 {
+  static constexpr bool kRagged = true;
+  const float* __restrict__ recon;
+  const long* __restrict__ desc;
+  const unsigned char* __restrict__ ref;
+  int Hc, Wc;
+  int* __restrict__ status;
+  __device__ __forceinline__ U8View view(int plane) const {
+    const int b = plane / 3, c = plane - 3 * b;
+    const Extent e = image_extent(desc, b, Hc, Wc, 0);
+    return U8View{e.H, e.W, Wc, recon + (long)plane * Hc * Wc,
+                  ref + desc[(long)b * kDescN + kDescOff] + c};
+  }
+  __device__ __forceinline__ void report(bool bad) const {
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(status, 1);
+  }
+};
+
+struct ImagePlanes {
+  static constexpr bool kRagged = true;
+  const float* __restrict__ X;    // the level's X and Y slots: `slot` floats per plane
+  const float* __restrict__ Y;
+  long slot;
+  const long* __restrict__ desc;
+  int Hc, Wc, level;
+  __device__ __forceinline__ PlaneView view(int plane) const {
+    const Extent e = image_extent(desc, plane / 3, Hc, Wc, level);
+    return PlaneView{e.H, e.W, X + (long)plane * slot, Y + (long)plane * slot};
+  }
+  __device__ __forceinline__ void report(bool) const {}
+};
+
+// The finish of a canvas batch: `canvas` is the plan of the canvas (where an image's partials
+// start); the image sums the 3·tiles of its own grid, as its Uniform batch of one would.
+struct ImageFinish {
+  FinishPlan canvas;
+  const long* __restrict__ desc;
+  int Hc, Wc;
+  __device__ __forceinline__ Extent maps(int l, int b) const {   // Ho × Wo
+    const Extent e = image_extent(desc, b, Hc, Wc, l);
+    return Extent{e.H - (WIN - 1), e.W - (WIN - 1)};
+  }
+  __device__ __forceinline__ long n(int l, int b) const {
+    const Extent o = maps(l, b);
+    if (o.H <= 0 || o.W <= 0) return 0;   // too small for the level (the host wrapper rejects it)
+    return 3L * ((o.W + TOW - 1) / TOW) * ((o.H + TOH - 1) / TOH);
+  }
+  __device__ __forceinline__ long first(int l, int b) const {
+    return canvas.poff[l] + 2 * (long)b * 3 * canvas.tiles[l];
+  }
+  __device__ __forceinline__ double mean_over(int l, int b) const {
+    const Extent o = maps(l, b);
+    return 3.0 * o.H * o.W;
+  }
+};
+
 // SAVE (the gradient path, see "Backward" below): bit 0 also writes the per-pixel derivatives of
 // the cs map, bit 1 those of the ssim map, to dcs / dss as planes [map][plane][Ho][Wo] with
 // map 0 = ∂/∂mx, 1 = ∂/∂exx (= ∂/∂eyy), 2 = ∂/∂exy and, with want_dy, 3 = ∂/∂my. SAVE = 0 is the
 // evaluation kernel; the partial sums and their arithmetic are the same in every variant.
-template <int SAVE>
-__global__ void __launch_bounds__(256, 2) ssim_level_kernel(const float* __restrict__ X,
-                                                            const float* __restrict__ Y, int H,
-                                                            int W, float c1, float c2,
+template <int SAVE, class Ext>
+__global__ void __launch_bounds__(256, 2) ssim_level_kernel(const Ext ext, float c1, float c2,
                                                             double* __restrict__ partial,
                                                             float* __restrict__ dcs,
                                                             float* __restrict__ dss, int want_dy) {
+  static_assert(SAVE == 0 || !Ext::kRagged, "the derivative maps are laid out for uniform planes");
   __shared__ __attribute__((aligned(16))) float sx[IH * IWP], sy[IH * IWP];
   __shared__ __attribute__((aligned(16))) float h[5][IH][TOW];
   __shared__ double red[2][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int Ho = H - (WIN - 1), Wo = W - (WIN - 1);
   const int plane = blockIdx.z;
+  const auto pv = ext.view(plane);
+  const int H = pv.H, W = pv.W;
+  const int Ho = H - (WIN - 1), Wo = W - (WIN - 1);
+  // the plane's own tile grid and its first partial
+  int tgx = gridDim.x, tgy = gridDim.y;
+  long tile0 = (long)plane * gridDim.y * gridDim.x;
+  if constexpr (Ext::kRagged) {
+    tgx = (Wo + TOW - 1) / TOW;
+    tgy = (Ho + TOH - 1) / TOH;
+    if ((int)blockIdx.x >= tgx || (int)blockIdx.y >= tgy) return;   // uniform over the workgroup
+    const int img = plane / 3;
+    tile0 = 3L * img * gridDim.y * gridDim.x + (long)(plane - 3 * img) * tgy * tgx;
+  }
   const int r0 = blockIdx.y * TOH, c0 = blockIdx.x * TOW;
-  const float* xp = X + (long)plane * H * W;
-  const float* yp = Y + (long)plane * H * W;
   float g[WIN];
 #pragma unroll
   for (int k = 0; k < WIN; ++k) g[k] = c_gauss[k];
 
+  bool bad = false;
   for (int i = tid; i < IH * IW; i += 256) {
     const int r = i / IW, c = i - r * IW;
     const int gr = r0 + r, gc = c0 + c;
     const bool ok = gr < H && gc < W;
-    sx[r * IWP + c] = ok ? xp[(long)gr * W + gc] : 0.f;
-    sy[r * IWP + c] = ok ? yp[(long)gr * W + gc] : 0.f;
+    sx[r * IWP + c] = ok ? pv.x(gr, gc, bad) : 0.f;
+    sy[r * IWP + c] = ok ? pv.y(gr, gc) : 0.f;
   }
+  ext.report(bad);
   __syncthreads();
   // along W: 42 rows × 16 column quads; a thread filters columns cq .. cq+3 of row r
   for (int task = tid; task < IH * (TOW / 4); task += 256) {
@@ -193,45 +345,51 @@ __global__ void __launch_bounds__(256, 2) ssim_level_kernel(const float* __restr
   }
   __syncthreads();
   if (tid == 0) {
-    const long tile = ((long)plane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    const long tile = tile0 + (long)blockIdx.y * tgx + blockIdx.x;
     partial[2 * tile] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
     partial[2 * tile + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
   }
 }
 
 // F.avg_pool2d(kernel 2, stride 2, padding (H % 2, W % 2)), count_include_pad: /4 always.
-// grid (⌈Wo/256⌉, Ho, 2P): output row oy of plane z % P of X (z < P) or Y.
-__global__ void __launch_bounds__(256) avgpool2_kernel(const float* __restrict__ inx,
-                                                       const float* __restrict__ iny, int P, int H,
-                                                       int W, float* __restrict__ outx,
+// grid (⌈Wo/256⌉, Ho, 2P): output row oy of plane z % P of X (z < P) or Y. The output planes are
+// dense (row stride Wo), `out_plane` floats apart: Ho·Wo, or a ragged source's next slot, on whose
+// canvas grid a row or column beyond the image's own output returns.
+template <class Ext>
+__global__ void __launch_bounds__(256) avgpool2_kernel(const Ext ext, int P, long out_plane,
+                                                       float* __restrict__ outx,
                                                        float* __restrict__ outy) {
-  const int ph = H % 2, pw = W % 2;
-  const int Ho = (H + 2 * ph - 2) / 2 + 1, Wo = (W + 2 * pw - 2) / 2 + 1;
-  const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
-  if (ox >= Wo) return;
   const int z = blockIdx.z;
   const int p = z < P ? z : z - P;
-  const float* src = (z < P ? inx : iny) + (long)p * H * W;
+  const auto pv = ext.view(p);
+  const int H = pv.H, W = pv.W;
+  const int ph = H % 2, pw = W % 2;
+  const int Ho = pooled(H), Wo = pooled(W);
+  const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
+  if (ox >= Wo || oy >= Ho) return;
   float s = 0.f;
+  bool bad = false;   // the level kernel of the source's level reports it
   for (int dy = 0; dy < 2; ++dy)
     for (int dx = 0; dx < 2; ++dx) {
       const int iy = 2 * oy - ph + dy, ix = 2 * ox - pw + dx;
-      if (iy >= 0 && iy < H && ix >= 0 && ix < W) s += src[(long)iy * W + ix];
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) s += z < P ? pv.x(iy, ix, bad) : pv.y(iy, ix);
     }
-  (z < P ? outx : outy)[((long)p * Ho + oy) * Wo + ox] = s / 4.0f;
+  (z < P ? outx : outy)[(long)p * out_plane + (long)oy * Wo + ox] = s / 4.0f;
 }
 
 // One workgroup per image: the per-level means (Σ over the 3 planes × tiles, a fixed-order
 // strided sum + tree, / (3·Ho·Wo)) and the MS-SSIM product.
+template <class Plan>
 __global__ void __launch_bounds__(256) msssim_finish_kernel(const double* __restrict__ partial,
-                                                            const FinishPlan pl, int B,
+                                                            const Plan pl, int B,
                                                             double* __restrict__ means /* [L][B][2] */,
                                                             float* __restrict__ out) {
   __shared__ double red[2][256];
   const int b = blockIdx.x, tid = threadIdx.x;
   for (int l = 0; l < LEVELS; ++l) {
-    const long n = 3L * pl.tiles[l];
-    const double* p = partial + pl.poff[l] + 2 * (long)b * n;
+    const long n = pl.n(l, b);
+    const double* p = partial + pl.first(l, b);
+    const double count = pl.mean_over(l, b);
     double a = 0.0, c = 0.0;
     for (long t = tid; t < n; t += 256) {
       a += p[2 * t];
@@ -248,8 +406,8 @@ __global__ void __launch_bounds__(256) msssim_finish_kernel(const double* __rest
       __syncthreads();
     }
     if (tid == 0) {
-      means[((long)l * B + b) * 2] = red[0][0] / pl.count[l];
-      means[((long)l * B + b) * 2 + 1] = red[1][0] / pl.count[l];
+      means[((long)l * B + b) * 2] = red[0][0] / count;
+      means[((long)l * B + b) * 2 + 1] = red[1][0] / count;
     }
     __syncthreads();
   }
@@ -451,8 +609,8 @@ int level_plan(int H, int W, Level* lv, int B, long* pyr_floats, long* partial_d
     if (l > 0) off += 2L * B * 3 * H * W;   // X and Y planes of this level
     lv[l].tiles = ((W - WIN + 1 + TOW - 1) / TOW) * ((H - WIN + 1 + TOH - 1) / TOH);
     part += 2L * B * 3 * lv[l].tiles;
-    H = (H + 2 * (H % 2) - 2) / 2 + 1;
-    W = (W + 2 * (W % 2) - 2) / 2 + 1;
+    H = pooled(H);
+    W = pooled(W);
   }
   *pyr_floats = off;
   *partial_doubles = part;
@@ -537,22 +695,95 @@ int iclr17_ms_ssim(const float* x, const float* y, int B, int H, int W, float da
       float* Xn = pyrbuf + lv[l].off;
       float* Yn = Xn + (long)B * 3 * Hl * Wl;
       const int Hp = lv[l - 1].H, Wp = lv[l - 1].W;
-      hipLaunchKernelGGL(avgpool2_kernel, dim3((Wl + 255) / 256, Hl, 2 * B * 3), dim3(256), 0, st,
-                         X, Y, B * 3, Hp, Wp, Xn, Yn);
+      hipLaunchKernelGGL(avgpool2_kernel<Uniform>, dim3((Wl + 255) / 256, Hl, 2 * B * 3),
+                         dim3(256), 0, st, Uniform{X, Y, Hp, Wp}, B * 3, (long)Hl * Wl, Xn, Yn);
       X = Xn;
       Y = Yn;
     }
     const int Ho = Hl - WIN + 1, Wo = Wl - WIN + 1;
     dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
-    hipLaunchKernelGGL(ssim_level_kernel<0>, grid, dim3(256), 0, st, X, Y, Hl, Wl, c1, c2, pl,
-                       (float*)nullptr, (float*)nullptr, 0);
+    hipLaunchKernelGGL((ssim_level_kernel<0, Uniform>), grid, dim3(256), 0, st,
+                       Uniform{X, Y, Hl, Wl}, c1, c2, pl, (float*)nullptr, (float*)nullptr, 0);
     fp.poff[l] = pl - partial;
     fp.tiles[l] = lv[l].tiles;
     fp.count[l] = 3.0 * Ho * Wo;
     pl += 2L * B * 3 * lv[l].tiles;
   }
-  hipLaunchKernelGGL(msssim_finish_kernel, dim3(B), dim3(256), 0, st, partial, fp, B, means, out);
+  hipLaunchKernelGGL(msssim_finish_kernel<FinishPlan>, dim3(B), dim3(256), 0, st, partial, fp, B, means, out);
   return check_launch("ms_ssim");
+}
+
+// The pyramid, the partials and the means of a canvas batch are laid out for B images of the
+// canvas's size; an image uses the front of each of its slots.
+size_t iclr17_image_msssim_workspace_size(int B, int Hc, int Wc) {
+  return iclr17_ms_ssim_workspace_size(B, Hc, Wc);
+}
+
+int iclr17_image_msssim_u8(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
+                           const uint8_t* ref, void* workspace, size_t workspace_bytes, float* out,
+                           int32_t* status, void* stream) {
+  ICLR17_REQUIRE(recon && desc && ref && workspace && out && status, ICLR17_EINVAL,
+                 "image_msssim: null pointer");
+  if (int rc = check_image(B, Hc, Wc, 128)) return rc;
+  ICLR17_REQUIRE(B <= 10000 && Hc <= 65535 * 2, ICLR17_EUNSUPPORTED,
+                 "image_msssim: B=%d or canvas height %d beyond the launch grid", B, Hc);
+  Level lv[LEVELS];
+  long pyr = 0, part = 0;
+  ICLR17_REQUIRE(level_plan(Hc, Wc, lv, B, &pyr, &part) == 0, ICLR17_EINVAL,
+                 "image_msssim: the canvas %dx%d is too small for 5 levels of an 11-tap window", Hc,
+                 Wc);
+  ICLR17_REQUIRE(workspace_bytes >= iclr17_image_msssim_workspace_size(B, Hc, Wc), ICLR17_EINVAL,
+                 "image_msssim: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+  if (e != hipSuccess) {
+    set_error(ICLR17_ELAUNCH, "image_msssim: %s", hipGetErrorString(e));
+    return ICLR17_ELAUNCH;
+  }
+  char* ws = aligned_base(workspace);
+  float* pyrbuf = (float*)ws;
+  double* partial = (double*)(ws + pyr * 4);
+  double* means = partial + part;
+  const float data_range = 1.0f;
+  const float c1 = (0.01f * data_range) * (0.01f * data_range);
+  const float c2 = (0.03f * data_range) * (0.03f * data_range);
+  const long* d = (const long*)desc;
+  const ImageU8 level0{recon, d, (const unsigned char*)ref, Hc, Wc, (int*)status};
+  double* pl = partial;
+  ImageFinish fin{{}, d, Hc, Wc};
+  for (int l = 0; l < LEVELS; ++l) {
+    const int Hl = lv[l].H, Wl = lv[l].W;   // of the canvas: the launch grids and the slots
+    const long slot = (long)Hl * Wl;
+    float* Xl = l ? pyrbuf + lv[l].off : nullptr;
+    float* Yl = l ? Xl + (long)B * 3 * slot : nullptr;
+    const ImagePlanes here{Xl, Yl, slot, d, Hc, Wc, l};
+    const dim3 pool_grid((Wl + 255) / 256, Hl, 2 * B * 3);
+    if (l == 1)
+      hipLaunchKernelGGL(avgpool2_kernel<ImageU8>, pool_grid, dim3(256), 0, st, level0, B * 3, slot,
+                         Xl, Yl);
+    if (l > 1) {
+      const long up = (long)lv[l - 1].H * lv[l - 1].W;
+      const float* Xu = pyrbuf + lv[l - 1].off;
+      hipLaunchKernelGGL(avgpool2_kernel<ImagePlanes>, pool_grid, dim3(256), 0, st,
+                         ImagePlanes{Xu, Xu + (long)B * 3 * up, up, d, Hc, Wc, l - 1}, B * 3, slot,
+                         Xl, Yl);
+    }
+    const int Ho = Hl - WIN + 1, Wo = Wl - WIN + 1;
+    const dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
+    if (l == 0)
+      hipLaunchKernelGGL((ssim_level_kernel<0, ImageU8>), grid, dim3(256), 0, st, level0, c1, c2, pl,
+                         (float*)nullptr, (float*)nullptr, 0);
+    else
+      hipLaunchKernelGGL((ssim_level_kernel<0, ImagePlanes>), grid, dim3(256), 0, st, here, c1, c2,
+                         pl, (float*)nullptr, (float*)nullptr, 0);
+    fin.canvas.poff[l] = pl - partial;
+    fin.canvas.tiles[l] = lv[l].tiles;
+    fin.canvas.count[l] = 3.0 * Ho * Wo;
+    pl += 2L * B * 3 * lv[l].tiles;
+  }
+  hipLaunchKernelGGL(msssim_finish_kernel<ImageFinish>, dim3(B), dim3(256), 0, st, partial, fin, B,
+                     means, out);
+  return check_launch("image_msssim");
 }
 
 size_t iclr17_ssim_workspace_size(int B, int H, int W) {
@@ -579,8 +810,8 @@ int iclr17_ssim(const float* x, const float* y, int B, int H, int W, float data_
   const float c2 = (0.03f * data_range) * (0.03f * data_range);
   const int Ho = H - WIN + 1, Wo = W - WIN + 1;
   dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
-  hipLaunchKernelGGL(ssim_level_kernel<0>, grid, dim3(256), 0, st, x, y, H, W, c1, c2, partial,
-                     (float*)nullptr, (float*)nullptr, 0);
+  hipLaunchKernelGGL((ssim_level_kernel<0, Uniform>), grid, dim3(256), 0, st, Uniform{x, y, H, W},
+                     c1, c2, partial, (float*)nullptr, (float*)nullptr, 0);
   hipLaunchKernelGGL(ssim_finish_kernel, dim3(B), dim3(256), 0, st, partial, 3L * lv[0].tiles,
                      3.0 * Ho * Wo, out_ssim, out_cs);
   return check_launch("ssim");
@@ -621,8 +852,9 @@ int iclr17_ms_ssim_fwd_saved(const float* x, const float* y, int B, int H, int W
     if (l > 0) {
       float* Xn = pyrbuf + gp.lv[l].off;
       float* Yn = Xn + (long)B * 3 * Hl * Wl;
-      hipLaunchKernelGGL(avgpool2_kernel, dim3((Wl + 255) / 256, Hl, 2 * B * 3), dim3(256), 0, st,
-                         X, Y, B * 3, gp.lv[l - 1].H, gp.lv[l - 1].W, Xn, Yn);
+      hipLaunchKernelGGL(avgpool2_kernel<Uniform>, dim3((Wl + 255) / 256, Hl, 2 * B * 3),
+                         dim3(256), 0, st, Uniform{X, Y, gp.lv[l - 1].H, gp.lv[l - 1].W}, B * 3,
+                         (long)Hl * Wl, Xn, Yn);
       X = Xn;
       Y = Yn;
     }
@@ -630,17 +862,17 @@ int iclr17_ms_ssim_fwd_saved(const float* x, const float* y, int B, int H, int W
     dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
     float* d = maps + gp.maps[l];
     if (l < LEVELS - 1)
-      hipLaunchKernelGGL(ssim_level_kernel<1>, grid, dim3(256), 0, st, X, Y, Hl, Wl, c1, c2, pl, d,
-                         (float*)nullptr, want_dy);
+      hipLaunchKernelGGL((ssim_level_kernel<1, Uniform>), grid, dim3(256), 0, st,
+                         Uniform{X, Y, Hl, Wl}, c1, c2, pl, d, (float*)nullptr, want_dy);
     else
-      hipLaunchKernelGGL(ssim_level_kernel<2>, grid, dim3(256), 0, st, X, Y, Hl, Wl, c1, c2, pl,
-                         (float*)nullptr, d, want_dy);
+      hipLaunchKernelGGL((ssim_level_kernel<2, Uniform>), grid, dim3(256), 0, st,
+                         Uniform{X, Y, Hl, Wl}, c1, c2, pl, (float*)nullptr, d, want_dy);
     fp.poff[l] = pl - partial;
     fp.tiles[l] = gp.lv[l].tiles;
     fp.count[l] = 3.0 * Ho * Wo;
     pl += 2L * B * 3 * gp.lv[l].tiles;
   }
-  hipLaunchKernelGGL(msssim_finish_kernel, dim3(B), dim3(256), 0, st, partial, fp, B, means, out);
+  hipLaunchKernelGGL(msssim_finish_kernel<FinishPlan>, dim3(B), dim3(256), 0, st, partial, fp, B, means, out);
   return check_launch("ms_ssim_fwd_saved");
 }
 
@@ -712,8 +944,8 @@ int iclr17_ssim_fwd_saved(const float* x, const float* y, int B, int H, int W, f
   const int Ho = H - WIN + 1, Wo = W - WIN + 1;
   const long set = (long)gp.nmaps * B * 3 * Ho * Wo;
   dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
-  hipLaunchKernelGGL(ssim_level_kernel<3>, grid, dim3(256), 0, st, x, y, H, W, c1, c2, partial,
-                     maps + set, maps, want_dy);
+  hipLaunchKernelGGL((ssim_level_kernel<3, Uniform>), grid, dim3(256), 0, st, Uniform{x, y, H, W},
+                     c1, c2, partial, maps + set, maps, want_dy);
   hipLaunchKernelGGL(ssim_finish_kernel, dim3(B), dim3(256), 0, st, partial, 3L * gp.lv[0].tiles,
                      3.0 * Ho * Wo, out_ssim, out_cs);
   return check_launch("ssim_fwd_saved");

@@ -1827,6 +1827,71 @@ def image_sse(recon: Tensor, offsets, shapes, ref: Tensor):
     return host[:8 * B].view(torch.int64)
 
 
+MSSSIM_MIN_SIDE = 161    # five levels of an 11-tap window: 161 → 81 → 41 → 21 → 11 (160 ends at 10)
+
+
+def check_msssim_shapes(shapes, labels=None) -> None:
+    """The size rule of MS-SSIM on the host (csrc/msssim.hip's level_plan: every one of the five
+    levels at least 11×11, a level being ⌈previous / 2⌉): raises naming the first image that is
+    too small. ``labels``: the images' names in the message (default "image b")."""
+    for b, (H, W) in enumerate(shapes):
+        h, w = int(H), int(W)
+        for _ in range(5):
+            if h < 11 or w < 11:
+                name = labels[b] if labels is not None else f"image {b}"
+                raise Iclr17Error(f"iclr17: image_msssim: {name} is {int(H)}x{int(W)}, too small for "
+                                  f"5 levels of an 11-tap window (both sides at least "
+                                  f"{MSSSIM_MIN_SIDE})")
+            h, w = (h + 1) // 2, (w + 1) // 2
+
+
+def image_msssim_device(recon: Tensor, offsets, shapes, ref: Tensor, desc: Optional[Tensor] = None):
+    """``image_msssim`` without the transfer: → (buffer, values fp32 [B], status int32 [1], spare
+    int32 [1]), views of the one uint8 ``buffer`` of 4·B + 8 bytes on the device; ``spare`` is
+    zeroed for a caller's own status word, as ``image_sse_device``'s. ``desc``: the checked
+    descriptors of an earlier call with the same offsets, shapes and canvas, already on the device
+    (the caller has then run ``check_msssim_shapes`` too: the library cannot see them)."""
+    _check(recon, "reconstruction", 4)
+    B, C, Hc, Wc = recon.shape
+    if C != 3:
+        raise Iclr17Error(f"iclr17: image_msssim takes a [B,3,Hc,Wc] reconstruction (got {C} channels)")
+    _check_u8(ref, "reference bytes")
+    if desc is None:
+        check_msssim_shapes(shapes)
+        desc = _image_desc("image_msssim", ref.numel(), offsets, shapes, (Hc, Wc)).to(recon.device)
+    if tuple(desc.shape) != (B, 4):
+        raise Iclr17Error(f"iclr17: image_msssim: {desc.shape[0]} images for a batch of {B}")
+    ref = _check_u8_gpu(ref, "reference bytes")
+    nbytes = query("iclr17_image_msssim_workspace_size", B, Hc, Wc)
+    if nbytes == 0:
+        raise Iclr17Error(f"iclr17: image_msssim: the canvas {Hc}x{Wc} is too small for 5 levels of "
+                          "an 11-tap window")
+    ws = torch.empty(nbytes, device=recon.device, dtype=torch.uint8)
+    buf = torch.zeros(4 * B + 8, device=recon.device, dtype=torch.uint8)
+    values = buf[:4 * B].view(torch.float32)
+    status = buf[4 * B:4 * B + 4].view(torch.int32)
+    spare = buf[4 * B + 4:].view(torch.int32)
+    call("iclr17_image_msssim_u8", _p(recon.contiguous()), _p(desc), B, Hc, Wc, _p(ref), _p(ws),
+         nbytes, _p(values), _p(status), _stream(recon))
+    return buf, values, status, spare
+
+
+def image_msssim(recon: Tensor, offsets, shapes, ref: Tensor):
+    """Per image the MS-SSIM (data_range 1) of the 8-bit image ``image_egress(recon, offsets,
+    shapes)`` would write against the original ``ref``, each over the image's own H×W: fp32 [B] on
+    the HOST, bit for bit ``ms_ssim(egress bytes / 255, ref / 255)`` of that image alone, without
+    writing or moving a pixel. An image with a side below ``MSSSIM_MIN_SIDE`` raises, naming it; a
+    non-finite value inside an image raises as ``image_egress`` does."""
+    buf, _, _, _ = image_msssim_device(recon, offsets, shapes, ref)
+    host = buf.cpu()
+    B = recon.shape[0]
+    if int(host[4 * B:4 * B + 4].view(torch.int32).item()):
+        if precision() == "h3":
+            raise Iclr17Error(H3_RANGE_MESSAGE)
+        raise Iclr17Error("iclr17: image_msssim: non-finite reconstruction")
+    return host[:4 * B].view(torch.float32)
+
+
 # ------------------------------------------------------------------------------ modules
 def gdn(x: Tensor, beta_eff: Tensor, gp: Tensor, inverse: bool) -> Tensor:
     """GDN.forward (models/GDN.py:64-94) on a 4-D tensor; keeps the input's memory format."""

@@ -531,7 +531,8 @@ class ImageCompressor(nn.Module):
                         K: int = kernels.ENTROPY_K, step: Optional[int] = None,
                         max_bytes=None, bpp=None, stats: Optional[dict] = None,
                         step_offsets=None, block: int = 4, rdo=None, rdo_weights=None,
-                        tile: Optional[int] = None, psnr=None, estimate: Optional[bool] = None):
+                        tile: Optional[int] = None, psnr=None, estimate: Optional[bool] = None,
+                        msssim=None):
         """8-bit images of any sizes ≥ 1×1 (a sequence of uint8 HWC RGB arrays, numpy or torch) →
         one self-describing blob per image, in input order: codec.py's 28-byte header (true size,
         N, P, K, weights fingerprint) + the image's ``compress`` string. Images are batched by
@@ -577,13 +578,23 @@ class ImageCompressor(nn.Module):
         ``distortion_sweep``'s prediction, False bisects (None: codec.DEFAULT_ESTIMATE, which is
         bisection). The blobs are byte for byte those of ``step=`` at the index found (I17Q, or I17T with ``tile``); ``stats`` receives
         "probes" and "sse" (the SSE at the index) per image. A target above what index 0 reaches
-        raises; with ``rdo`` or ``step_offsets`` it raises (not built)."""
+        raises; with ``rdo`` or ``step_offsets`` it raises (not built).
+
+        ``msssim`` (0 < T < 1; a scalar or one value per image) is the same target in MS-SSIM, the
+        fifth rate option (codec.py, "MS-SSIM targets"): an index passes when the
+        fp32 MS-SSIM of its 8-bit decode over the image's own H×W is ≥ T. Plain bisection, at most
+        6 probes per image, each a quantise–synthesis–MS-SSIM pass on the device
+        (kernels.image_msssim); ``stats`` receives "probes" and "ms_ssim" (the value at the index,
+        which is ``evaluate_images``' ``ms_ssim`` of the blob). Both sides of every image must be
+        at least 161; with another rate option, ``rdo``, ``step_offsets`` or ``estimate=True`` it
+        raises."""
         from . import codec
         return codec.compress_images(self, images, max_batch, streams_per_image, K, step=step,
                                      max_bytes=max_bytes, bpp=bpp, stats=stats,
                                      step_offsets=step_offsets, block=block, rdo=rdo,
                                      rdo_weights=rdo_weights, tile=tile, psnr=psnr,
-                                     estimate=codec.DEFAULT_ESTIMATE if estimate is None else estimate)
+                                     estimate=codec.DEFAULT_ESTIMATE if estimate is None else estimate,
+                                     msssim=msssim)
 
     @torch.no_grad()
     def decompress_images(self, blobs, max_batch: int = 64):
@@ -613,7 +624,7 @@ class ImageCompressor(nn.Module):
     def evaluate_images(self, images, want_msssim: bool = False, max_batch: int = 64,
                         step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
                         block: int = 4, rdo=None, rdo_weights=None, tile: Optional[int] = None,
-                        psnr=None, estimate: Optional[bool] = None):
+                        psnr=None, estimate: Optional[bool] = None, msssim=None):
         """The real codec path per image, compress_images then decompress_images, measured on
         the 8-bit decoded image as codecs are reported: a dict per image with ``bytes``, ``bpp`` =
         8·len(blob)/(H·W) (header included, true pixel count), ``sse_u8`` (int), ``psnr_u8`` =
@@ -624,13 +635,15 @@ class ImageCompressor(nn.Module):
         ``rdo_weights`` as in ``compress_images``; a mapped blob's row has its base index as
         ``step`` and also ``step_map`` and ``block``; with ``tile`` a row has the blob's ladder
         index as ``step`` and also ``tile``. ``psnr`` / ``estimate`` as in ``compress_images``: the
-        row's ``step`` is the index found. Precision as ``decompress_images``."""
+        row's ``step`` is the index found; so is ``msssim``, whose rows also carry ``ms_ssim`` and
+        ``ms_ssim_db`` as ``want_msssim`` gives them. Precision as ``decompress_images``."""
         from . import codec
         return codec.evaluate_images(self, images, want_msssim, max_batch, step=step,
                                      max_bytes=max_bytes, bpp=bpp, step_offsets=step_offsets,
                                      block=block, rdo=rdo, rdo_weights=rdo_weights, tile=tile,
                                      psnr=psnr,
-                                     estimate=codec.DEFAULT_ESTIMATE if estimate is None else estimate)
+                                     estimate=codec.DEFAULT_ESTIMATE if estimate is None else estimate,
+                                     msssim=msssim)
 
     @torch.no_grad()
     def evaluate(self, x: torch.Tensor, want_y: bool = False,

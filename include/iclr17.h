@@ -528,6 +528,28 @@ int iclr17_image_egress_u8(const float* recon, const int64_t* desc, int B, int H
  * int64 sums and status bit; no 8-bit pixel is written. ref is required. */
 int iclr17_image_sse_u8(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
                         const uint8_t* ref, int64_t* sse, int32_t* status, void* stream);
+/* MS-SSIM of the 8-bit decode of every image of a canvas batch against its original (the probe of
+ * an MS-SSIM target; csrc/msssim.hip). recon, desc and ref as iclr17_image_sse_u8
+ * takes them. For image b, over its own H_b×W_b:
+ *   X = rintf(fminf(fmaxf(recon, 0), 1) · 255.0f) · r   (the byte iclr17_image_egress_u8 writes),
+ *   Y = float(ref) · r, with r = 1.0f / 255.0f rounded once to fp32: a product, not the quotient
+ *   (they differ for 126 of the 256 bytes). It is what torch gives for `bytes.float() / 255` on
+ *   the device, the planes codec.evaluate_images measures, so that a value here is the value
+ *   reported there;
+ *   out[b] = MS-SSIM(X, Y) with data_range 1,
+ * bit for bit the value iclr17_ms_ssim returns for those two planes as a batch of one at H_b×W_b:
+ * the same tiles, the same partial sums in the same order. It does not depend on the batch or on
+ * recon's padding, which is never read. The conversion happens as level 0 is read; nothing goes
+ * to the host. status (int32; cleared first): |= 1 when a recon value inside an image's own
+ * region is not finite. The caller guarantees min(H_b, W_b) ≥ 161 (five levels of an 11-tap
+ * window: 161 → 81 → 41 → 21 → 11) besides what the descriptors always need; a NaN result (a mean
+ * that is not positive, as in the reference) is not an error. workspace:
+ * iclr17_image_msssim_workspace_size(B, Hc, Wc) bytes (0: the canvas itself is too small).
+ * out: fp32 [B]. */
+size_t iclr17_image_msssim_workspace_size(int B, int Hc, int Wc);
+int iclr17_image_msssim_u8(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
+                           const uint8_t* ref, void* workspace, size_t workspace_bytes, float* out,
+                           int32_t* status, void* stream);
 
 /* train.py:106-112: element-wise gradient clamp to ±grad_clip (≤ 0: none; written back to the
  * gradient) fused with one torch.optim.Adam step (no weight decay, no amsgrad) over n_tensors
