@@ -124,6 +124,10 @@ SIGNATURES = {
     "iclr17_step_rate_bwd_partials": (_I, [_I, _I]),
     "iclr17_step_noise_rate_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "iclr17_grad_recon_images": (_I, [_P, _P, _P, _P, _I, _I64, _P, _P]),
+    "iclr17_refine_grad_recon": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "iclr17_refine_step": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _D, ctypes.c_long, _P,
+                                _P, _P, _P, _P, _P]),
+    "iclr17_refine_keep": (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _I, _P, _P, _P, _P, _P, _P, _P]),
     "iclr17_ms_ssim_workspace_size": (_SZ, [_I, _I, _I]),
     "iclr17_ms_ssim": (_I, [_P, _P, _I, _I, _I, _F, _P, _SZ, _P, _P]),
     "iclr17_ssim_workspace_size": (_SZ, [_I, _I, _I]),

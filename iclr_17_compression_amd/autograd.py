@@ -193,6 +193,21 @@ def synthesis_backward(dec, saved: chain.SynthesisSaved, g_recon: Tensor,
     return g_y, grads, rpart, g_ys
 
 
+def synthesis_latent_grad(dec, saved: chain.SynthesisSaved, g_recon: Tensor, *, mode: str) -> Tensor:
+    """∂L/∂recon (NCHW) → ∂L/∂ỹ (fp32 NHWC) alone: the data-gradient chain of
+    ``synthesis_backward`` — the same three fused input-gradient kernels on the same operands, so
+    the same ∂L/∂ỹ — without the weight, bias and GDN-parameter gradients and with no rate term.
+    What latent refinement (codec.refine_loop) runs per iteration. ``mode`` as there."""
+    bw = chain.train_mode(mode).backward
+    d3, d2c, d1c = dec.packed_bwd(bw.x6)
+    q2, q1 = bw.gdn_params(dec.igdn2), bw.gdn_params(dec.igdn1)
+    _, h, w, _ = saved.y.shape
+    g_v2, _, _, _ = bw.deconv3_layer(g_recon, d3, saved.v2, q2)
+    g_v1, _, _, _ = bw.layer(kernels.bwd_deconv_igdn, g_v2, d2c, saved.v1, q1)
+    g_y, _, _ = bw.rate_layer(g_v1, d1c, None, None, None, 0.0, h, w, want_split=False)
+    return g_y
+
+
 def _ordered(module, prefix: str, grads: Dict[str, Tensor]) -> List[Optional[Tensor]]:
     return [grads.get(name) for name, _ in module.named_parameters()]
 

@@ -121,6 +121,19 @@ Both sides of an image must be at least 161 (five levels of an 11-tap window): a
 raises on the host, before the ingest. Blobs, ``tile`` and the combinations that raise are as for
 ``psnr``; ``estimate=True`` raises too (``distortion_sweep`` predicts squared error).
 
+Latent refinement. ``compress_images(..., step=s, refine=K, refine_lambda=λ)``
+improves the latent of each image before it is coded: K Adam steps on y lower
+J = bits + (λ/3)·SSE8/255² — the rate model's bits of ŷ = rint(y/Δ) and the squared 8-bit error of its
+decode over the image's own pixels, H·W times train.py's λ·mse + bpp — with the gradient taken
+through the synthesis and the rate model and straight through the rounding (``refine_loop``: no
+host synchronisation). The best ŷ seen is then judged against the plain one through the eval
+chain, as ``evaluate_images`` measures, and coded only where its J is strictly lower
+(``refine_latents``), so ``stats["objective"]`` ≤ ``stats["objective_plain"]`` and a diverged run
+gives the plain blob. It is an encoder-side choice: ordinary I17Q blobs (with ``tile`` I17T), any
+decoder reads them. ``refine`` goes with ``step`` (none: index 8) and ``tile``; with a budget, a
+quality target, ``rdo`` or ``step_offsets`` and in the bf16 mode it raises; 0 and None are the call
+without it. ``refine_lr`` (in units of Δ) defaults to ``DEFAULT_REFINE_LR``.
+
 Region decode. ``decompress_region(blob, box)`` returns the pixels of ``box`` = (x0, y0, x1, y1)
 (half-open, inside the image), byte for byte the crop of the full decode, from the tiles it needs
 alone. The synthesis is deconv 5×5/s2/p2, IGDN, deconv 5×5/s2/p2, IGDN, deconv 9×9/s4/p4; IGDN is
@@ -135,11 +148,12 @@ its own, and ``image_egress`` runs on the crop.
                                             [--step S | --max-bytes B | --bpp R | --psnr T |
                                              --msssim T]
                                             [--roi X0,Y0,X1,Y1,OFF ...] [--block G] [--rdo L]
-                                            [--tile T]
+                                            [--tile T] [--refine K --refine-lambda L [--refine-lr R]]
     python -m iclr_17_compression_amd.codec decode IN.i17c OUT.png --weights CKPT
                                             [--region X0,Y0,X1,Y1]
     python -m iclr_17_compression_amd.codec eval IMG... --weights CKPT [--ms-ssim] [--steps 4,8,12]
                                             [--rdo L] [--psnr T | --msssim T]
+                                            [--refine K --refine-lambda L [--refine-lr R]]
 """
 from __future__ import annotations
 
@@ -779,8 +793,71 @@ def _per_image(name: str, value, n: int, check) -> List[float]:
     return [check(v.item() if isinstance(v, np.generic) else v) for v in per]
 
 
+# ------------------------------------------------------------------------------ refinement
+# refine_lr=None: the learning rate in units of Δ per Adam step that tools/refine_rd.py's sweep
+# chose (profiles/refine_rd.txt)
+DEFAULT_REFINE_LR = 0.003
+
+_REFINE_NOT_BUILT = {
+    "max_bytes": "refinement under a byte budget",
+    "bpp": "refinement under a byte budget",
+    "psnr": "refinement under a quality target",
+    "msssim": "refinement under a quality target",
+    "rdo": "refinement of rate–distortion optimised levels",
+    "step_offsets": "refinement over per-block steps",
+}
+REFINE_WITH = {k: f"iclr17: codec: refine with {'step_offsets / a step map' if k == 'step_offsets' else k}"
+                  f": {v} is not built" for k, v in _REFINE_NOT_BUILT.items()}
+REFINE_NEEDS_LAMBDA = ("iclr17: codec: refine without refine_lambda: the objective bits + λ·SSE needs "
+                       "its λ (train.py's units: 650.25 for the golden checkpoints)")
+REFINE_IN_BF16 = ("iclr17: codec: refine in the bf16 precision mode: that mode has no training "
+                  "kernels, and refining through another chain than the decoder's is not built")
+
+
+def refine_value(refine) -> int:
+    """``refine`` (gradient iterations of latent refinement) checked on the host: None (0) or an
+    integer ≥ 0, not a bool → int."""
+    if refine is None:
+        return 0
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0:
+        raise Iclr17Error(f"iclr17: codec: refine must be an integer >= 0 (got {refine!r})")
+    return int(refine)
+
+
+def refine_lambda_value(lam) -> float:
+    """One ``refine_lambda`` checked on the host: a real number, not a bool, finite (as an fp32
+    value too) and ≥ 0 → float."""
+    if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)):
+        raise Iclr17Error(f"iclr17: codec: refine_lambda must be a real number (got {lam!r})")
+    v = float(lam)
+    if not (math.isfinite(v) and 0.0 <= v <= float(np.finfo(np.float32).max)):
+        raise Iclr17Error(f"iclr17: codec: refine_lambda must be finite and >= 0 (got {lam!r})")
+    return v
+
+
+def refine_lr_value(lr) -> float:
+    """``refine_lr`` checked on the host: None (``DEFAULT_REFINE_LR``) or a real number, not a
+    bool, finite and > 0 → float. The Adam learning rate of image b is this times Δ_b."""
+    if lr is None:
+        return DEFAULT_REFINE_LR
+    if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)):
+        raise Iclr17Error(f"iclr17: codec: refine_lr must be a real number (got {lr!r})")
+    v = float(lr)
+    if not (math.isfinite(v) and v > 0.0):
+        raise Iclr17Error(f"iclr17: codec: refine_lr must be finite and > 0 (got {lr!r})")
+    return v
+
+
+def refine_objective(bits: float, sse: int, lam: float) -> float:
+    """J = bits + (λ/3)·SSE8/255² in float64, evaluated left to right as written here (the device
+    evaluates the same operations, kernels.refine_keep): H·W times train.py's λ·mse + bpp of the
+    8-bit decode."""
+    return float(bits) + (float(lam) / 3.0) * float(int(sse)) / 65025.0
+
+
 def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None, rdo=None,
-                 tile=None, psnr=None, msssim=None, estimate: bool = False):
+                 tile=None, psnr=None, msssim=None, estimate: bool = False, refine=None,
+                 refine_lambda=None, refine_lr=None):
     """The rate options of ``compress_images`` for ``n`` images, checked on the host before any
     device use → None (the plain path), ("step", index), ("budget", per-image values, is_bpp) or,
     for ``psnr`` (a quality target in dB, a scalar or one value per image; not with another rate
@@ -791,7 +868,26 @@ def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None,
     any one of them, the option then giving the base index; alone it means the unit step. So does
     ``rdo`` (``rdo_value`` checks it); ``rdo`` with ``step_offsets`` raises. ``tile`` (the tile
     edge of tiled streams: 8, 16, 32 or 64) changes the layout and not the rate: it goes with every
-    option but ``step_offsets``, with which it raises, and does not change the answer."""
+    option but ``step_offsets``, with which it raises, and does not change the answer.
+
+    ``refine`` (K > 0 iterations of latent refinement, ``refine_value``) goes with ``step`` (none
+    given: the unit step) and ``tile`` and gives ("refine", index, K, per-image λ, learning rate);
+    with ``max_bytes``, ``bpp``, ``psnr``, ``msssim``, ``rdo`` or ``step_offsets`` (``REFINE_WITH``),
+    without ``refine_lambda`` (a scalar or one value per image, ``refine_lambda_value``) and in the
+    bf16 precision mode it raises. ``refine`` 0 or None gives the request of the call without it."""
+    iters = refine_value(refine)
+    if refine_lambda is not None:
+        lams = _per_image("refine_lambda", refine_lambda, n, refine_lambda_value)
+    lr = refine_lr_value(refine_lr)
+    if iters:
+        for name, v in (("max_bytes", max_bytes), ("bpp", bpp), ("psnr", psnr), ("msssim", msssim),
+                        ("rdo", rdo), ("step_offsets", step_offsets)):
+            if v is not None:
+                raise Iclr17Error(REFINE_WITH[name])
+        if refine_lambda is None:
+            raise Iclr17Error(REFINE_NEEDS_LAMBDA)
+        if kernels.precision() == "bf16":
+            raise Iclr17Error(REFINE_IN_BF16)
     if tile is not None:
         if (isinstance(tile, bool) or not isinstance(tile, (int, np.integer))
                 or tile not in kernels.TILES):
@@ -825,11 +921,13 @@ def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None,
         if estimate:
             raise Iclr17Error(MSSSIM_WITH_ESTIMATE)
         return "msssim", per
+    if not given and iters:
+        return "refine", UNIT_STEP, iters, lams, lr
     if not given:
         return None if step_offsets is None and rdo is None else ("step", UNIT_STEP)
     if step is not None:
         step_size(step)
-        return "step", int(step)
+        return ("refine", int(step), iters, lams, lr) if iters else ("step", int(step))
     value = max_bytes if max_bytes is not None else bpp
     per = [value] * n if np.ndim(value) == 0 else list(np.asarray(value).reshape(-1))
     if len(per) != n:
@@ -908,16 +1006,152 @@ def msssim_probe(net, y, packed, offsets, shapes):
     return quality_probe(net, y, packed, offsets, shapes, MSSSIM_MEASURE)
 
 
+# what refine_loop leaves on the device: the best iterate's ŷ and the plain ŷ (fp32 NHWC), per
+# image the iteration kept (int32; −1: none passed), its J, bits (float64) and SSE (int64) as the
+# loop measured them, and iteration 0's bits and quantiser status (int32 [B])
+RefineState = namedtuple("RefineState", "best plain best_iter best_J best_bits best_sse bits0 status0")
+
+
+def refine_loop(net, y, steps_dev, lam, wt, packed, desc, iters: int, lr: float,
+                mode: str) -> RefineState:
+    """The K + 1 iterations of latent refinement on one canvas batch, without a
+    host synchronisation: everything it decides is decided on the device. ``y``: the fp32 NHWC
+    latent of ``net.latents`` (not modified); ``steps_dev`` fp32 [B] (Δ_b), ``lam`` float64 [B]
+    (λ_b) and ``wt`` fp32 [B] (λ_b/3) on the device; ``packed`` / ``desc`` the uploaded originals
+    and their checked descriptors on the device; ``mode`` a precision mode with training kernels,
+    whose packs the caller has warmed (``net._warm_packs``: their first build may synchronise).
+
+    Iteration t: ŷ_t = rint(y/Δ_b) and its bits (kernels.refine_step), the training forward of the
+    synthesis from Δ_b·ŷ_t, the 8-bit SSE of its output over the image's own pixels
+    (kernels.image_sse_device on the unclipped output, which the kernel clamps as the clipped one
+    is: the same sums, and a non-finite value is seen), keep-the-best (kernels.refine_keep), and
+    while t < K the gradient of the distortion through the synthesis
+    (kernels.refine_grad_recon, autograd.synthesis_latent_grad) into the next refine_step, which
+    adds the rate derivative straight through the rounding and takes the Adam step."""
+    from . import chain
+    from .autograd import synthesis_latent_grad
+    m = chain.train_mode(mode)
+    dec, rate = net.Decoder, net.bitEstimator.packed()
+    dev, B = y.device, y.shape[0]
+    y = y.clone().contiguous()
+    mom, var = torch.zeros_like(y), torch.zeros_like(y)
+    y_hat, y_deq, best = torch.empty_like(y), torch.empty_like(y), torch.zeros_like(y)
+    status = torch.zeros(B, device=dev, dtype=torch.int32)
+    flag = torch.zeros(B, device=dev, dtype=torch.int32)
+    partial = kernels.refine_bits_partials(y)
+    best_J = torch.full((B,), math.inf, device=dev, dtype=torch.float64)
+    best_iter = torch.full((B,), -1, device=dev, dtype=torch.int32)
+    best_bits = torch.zeros(B, device=dev, dtype=torch.float64)
+    best_sse = torch.zeros(B, device=dev, dtype=torch.int64)
+    plain = bits0 = status0 = None
+    with kernels.precision_scope(m.name):
+        kernels.refine_step(y, steps_dev, rate, y_hat, y_deq, status, partial)
+        for t in range(iters + 1):
+            _, recon, _, saved = m.train_synthesis(dec, y_deq, None, None)
+            _, sse, rstatus, _ = kernels.image_sse_device(recon, None, None, packed, desc)
+            bits, _ = kernels.reduce_partials(partial)
+            kernels.refine_keep(bits, sse, lam, status, rstatus, y_hat, t, best_J, best_iter,
+                                best_bits, best_sse, best, flag)
+            if t == 0:
+                plain, bits0, status0 = y_hat.clone(), bits, status.clone()
+            if t < iters:
+                g_recon = kernels.refine_grad_recon(recon, packed, desc, wt)
+                g_y = synthesis_latent_grad(dec, saved, g_recon, mode=m.name)
+                kernels.refine_step(y, steps_dev, rate, y_hat, y_deq, status, partial,
+                                    g_deq=g_y.contiguous(), m=mom, v=var, lr=lr, t=t + 1)
+    return RefineState(best, plain, best_iter, best_J, best_bits, best_sse, bits0, status0)
+
+
+def refine_latents(net, y, indices: Sequence[int], lams: Sequence[float], packed, offsets, shapes,
+                   iters: int, lr: Optional[float] = None, stats: Optional[dict] = None):
+    """``ImageCompressor.refine_latents``: the ŷ to code (fp32 NHWC, integer-valued) for one canvas
+    batch after ``iters`` iterations of refinement. ``y``: its latent (``net.latents``);
+    ``indices`` / ``lams``: per image the ladder index and λ; ``packed`` / ``offsets`` / ``shapes``
+    the originals as ``upload_packed`` returns them.
+
+    After ``refine_loop`` the choice is judged as ``evaluate_images`` measures: the best iterate
+    and the plain ŷ = rint(y/Δ) are synthesised through the eval chain of the current precision
+    mode (as a decoder does), ``image_sse`` is taken on both, and with the bits the loop summed
+    J = ``refine_objective`` of both; the best iterate is coded only where its J is strictly lower
+    (a non-finite decode counts as +inf), else the plain ŷ. One transfer, the call's only
+    synchronisation. ``stats`` (a dict) receives per image "refine_kept" (the iteration coded; 0:
+    the plain ŷ), "objective", "objective_plain" and "refine_iters"."""
+    from . import chain
+    mode = kernels.precision()
+    if mode == "bf16":
+        raise Iclr17Error(REFINE_IN_BF16)
+    iters, lr = refine_value(iters), refine_lr_value(lr)
+    kernels._check(y, "latent", 4)
+    B, dev = y.shape[0], y.device
+    if not (len(indices) == len(lams) == len(shapes) == B):
+        raise Iclr17Error(f"iclr17: codec: refine_latents takes one index, λ and shape per image "
+                          f"for {B} images")
+    lams = [refine_lambda_value(v) for v in lams]
+    Hc, Wc = canvas(*shapes[0])
+    if (y.shape[1], y.shape[2]) != (Hc // 16, Wc // 16):
+        raise Iclr17Error("iclr17: codec: refine_latents: the latent is not the canvas batch's")
+    desc = kernels._image_desc("refine", packed.numel(), offsets, shapes, (Hc, Wc))
+    host = torch.empty(B, 3, dtype=torch.float64, pin_memory=True)
+    for b in range(B):
+        host[b, 0], host[b, 1], host[b, 2] = step_size(indices[b]), lams[b], lams[b] / 3.0
+    args = host.to(dev, non_blocking=True)
+    steps_dev, lam = args[:, 0].float().contiguous(), args[:, 1].contiguous()
+    wt = args[:, 2].float().contiguous()
+    desc = desc.pin_memory().to(dev, non_blocking=True)
+    net._warm_packs(backward=True, mode=mode)
+    net._warm_packs(mode=mode)
+    st = refine_loop(net, y, steps_dev, lam, wt, packed, desc, iters, lr, mode)
+    em = chain.MODES[mode]
+
+    def decode_sse(y_hat):
+        y_deq = y_hat * steps_dev.view(B, 1, 1, 1)   # the fp32 product dequantise_step writes
+        clipped, _, _ = em.synthesis(net.Decoder, y_deq, em.latent_operand(y_deq), None, False,
+                                     False, None, False)
+        return kernels.image_sse_device(clipped, None, None, packed, desc)[0]
+
+    parts = [decode_sse(st.best), decode_sse(st.plain), st.best_bits.view(torch.uint8),
+             st.bits0.view(torch.uint8), st.best_iter.view(torch.uint8),
+             st.status0.view(torch.uint8)]
+    flat = torch.cat(parts).cpu().numpy()
+    n = 8 * B + 8
+    sse_b, bad_b = flat[:8 * B].view(np.int64), int(flat[8 * B:8 * B + 4].view(np.int32)[0])
+    sse_p = flat[n:n + 8 * B].view(np.int64)
+    bad_p = int(flat[n + 8 * B:n + 8 * B + 4].view(np.int32)[0])
+    rest = flat[2 * n:]
+    bits_b, bits_p = rest[:8 * B].view(np.float64), rest[8 * B:16 * B].view(np.float64)
+    kept = rest[16 * B:20 * B].view(np.int32)
+    kernels._step_status(torch.from_numpy(np.bitwise_or.reduce(rest[20 * B:24 * B].view(np.int32),
+                                                               keepdims=True).copy()),
+                         "quantise_steps")
+    use, J, J_plain = [], [], []
+    for b in range(B):
+        jp = math.inf if bad_p else refine_objective(bits_p[b], sse_p[b], lams[b])
+        jb = math.inf if bad_b or kept[b] <= 0 else refine_objective(bits_b[b], sse_b[b], lams[b])
+        use.append(jb < jp)
+        J.append(jb if use[b] else jp)
+        J_plain.append(jp)
+    if any(use):
+        pick = torch.tensor(use).pin_memory().to(dev, non_blocking=True)
+        y_hat = torch.where(pick.view(B, 1, 1, 1), st.best, st.plain)
+    else:
+        y_hat = st.plain
+    if stats is not None:
+        stats["refine_kept"] = [int(kept[b]) if use[b] else 0 for b in range(B)]
+        stats["objective"], stats["objective_plain"] = J, J_plain
+        stats["refine_iters"] = [iters] * B
+    return y_hat
+
+
 def compress_images(net, images, max_batch: int = 64,
                     streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                     K: int = kernels.ENTROPY_K, step: Optional[int] = None, max_bytes=None,
                     bpp=None, stats: Optional[dict] = None, step_offsets=None,
                     block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None,
                     tile: Optional[int] = None, psnr=None, estimate: bool = DEFAULT_ESTIMATE,
-                    msssim=None) -> List[bytes]:
+                    msssim=None, refine=None, refine_lambda=None, refine_lr=None) -> List[bytes]:
     imgs = [as_u8_hwc(im) for im in images]
     request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets, rdo, tile, psnr, msssim,
-                           estimate)
+                           estimate, refine, refine_lambda, refine_lr)
     if request is not None and request[0] == "msssim":   # on the host, before the ingest
         sizes = [im.shape[:2] for im in imgs]
         kernels.check_msssim_shapes(sizes, [f"image {i} ({H}x{W})" for i, (H, W) in enumerate(sizes)])
@@ -934,6 +1168,8 @@ def compress_images(net, images, max_batch: int = 64,
             budgets[i] = int(math.floor(float(v) * im.shape[0] * im.shape[1] / 8)) if request[2] else int(v)
     reencodes = [0] * len(imgs)
     probes, sses = [0] * len(imgs), [None] * len(imgs)
+    refined = {k: [None] * len(imgs) for k in ("refine_kept", "objective", "objective_plain",
+                                               "refine_iters")}
     for idx in group_by_canvas([im.shape[:2] for im in imgs], max_batch):
         group = [imgs[i] for i in idx]
         packed, offsets, shapes = upload_packed(group, device)
@@ -956,6 +1192,20 @@ def compress_images(net, images, max_batch: int = 64,
         overhead = blob_overhead(P) + (0 if offs is None else offs[0].size)
         if tile is not None:
             overhead = tiled_blob_overhead(P, *shapes[0], tile)   # one canvas: one tile grid
+        if request[0] == "refine":   # the refined ŷ, coded as the step's own
+            _, s, iters, lams, lr = request
+            got: dict = {}
+            y_hat = refine_latents(net, y, [s] * len(idx), [lams[i] for i in idx], packed, offsets,
+                                   shapes, iters, lr, got)
+            enc = net._entropy_code(y_hat, net.bitEstimator.entropy_tables(K, step=s), P, K,
+                                    tile=tile)
+            for k, (i, (H, W), string) in enumerate(zip(idx, shapes, enc["strings"])):
+                head = (pack_step_header(P, N, K, s, H, W, fp) if tile is None
+                        else pack_tile_header(P, N, K, s, tile, H, W, fp))
+                blobs[i] = head + string
+                for name in refined:
+                    refined[name][i] = got[name][k]
+            continue
         if request[0] == "step":
             chosen = [request[1]] * len(idx)
         elif request[0] == "quality":
@@ -1010,6 +1260,8 @@ def compress_images(net, images, max_batch: int = 64,
             stats["probes"], stats["sse"] = probes, sses
         if request is not None and request[0] == "msssim":
             stats["probes"], stats["ms_ssim"] = probes, sses
+        if request is not None and request[0] == "refine":
+            stats.update(refined)
     return blobs
 
 
@@ -1115,11 +1367,14 @@ def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
                     step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
                     block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None,
                     tile: Optional[int] = None, psnr=None,
-                    estimate: bool = DEFAULT_ESTIMATE, msssim=None) -> List[dict]:
+                    estimate: bool = DEFAULT_ESTIMATE, msssim=None, refine=None,
+                    refine_lambda=None, refine_lr=None) -> List[dict]:
     imgs = [as_u8_hwc(im) for im in images]
+    stats: dict = {}
     blobs = compress_images(net, imgs, max_batch=max_batch, step=step, max_bytes=max_bytes, bpp=bpp,
                             step_offsets=step_offsets, block=block, rdo=rdo, rdo_weights=rdo_weights,
-                            tile=tile, psnr=psnr, estimate=estimate, msssim=msssim)
+                            tile=tile, psnr=psnr, estimate=estimate, msssim=msssim, stats=stats,
+                            refine=refine, refine_lambda=refine_lambda, refine_lr=refine_lr)
     want_msssim = want_msssim or msssim is not None
     recons, sses = decode_groups(net, blobs, max_batch, refs=imgs)
     device = next(net.parameters()).device
@@ -1141,6 +1396,9 @@ def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
                 ms = float(kernels.ms_ssim(unit(rec), unit(im), data_range=1.0)[0])
                 r["ms_ssim"] = ms
                 r["ms_ssim_db"] = -10.0 * math.log10(1.0 - ms) if ms < 1.0 else math.inf
+        for name in ("refine_kept", "objective", "objective_plain", "refine_iters"):
+            if name in stats:
+                r[name] = stats[name][len(res)]
         res.append(r)
     return res
 
@@ -1221,6 +1479,7 @@ def build_parser() -> argparse.ArgumentParser:
                      help="independent streams per tile of T x T latent positions (16 pixels "
                           "each; 8, 16, 32 or 64): parallel coding of a large image and region "
                           "decode (not with --roi)")
+    _refine_arguments(enc, "--step or none (the unit step) and --tile")
     dec = sub.add_parser("decode", parents=[common], help="IN.i17c OUT.png")
     dec.add_argument("input")
     dec.add_argument("output")
@@ -1238,7 +1497,26 @@ def build_parser() -> argparse.ArgumentParser:
                     help="quality target in dB per image (not with --steps or --rdo)")
     ev.add_argument("--msssim", type=float, default=None, metavar="T",
                     help="MS-SSIM target per image (not with --steps, --rdo or --psnr)")
+    _refine_arguments(ev, "--steps or none")
     return ap
+
+
+def _refine_arguments(parser, goes_with: str) -> None:
+    parser.add_argument("--refine", type=int, default=None, metavar="K",
+                        help="K gradient iterations of latent refinement: lower bits + lambda * SSE "
+                             f"of this image, any decoder reads the result (with {goes_with}; "
+                             "needs --refine-lambda)")
+    parser.add_argument("--refine-lambda", type=float, default=None, metavar="L",
+                        help="lambda of the refinement objective in the training loss's units "
+                             "(lambda * mse + bpp)")
+    parser.add_argument("--refine-lr", type=float, default=None, metavar="R",
+                        help="Adam learning rate of the refinement in units of the quantiser "
+                             f"step (default {DEFAULT_REFINE_LR})")
+
+
+def _refine_of(args) -> dict:
+    return {"refine": args.refine, "refine_lambda": args.refine_lambda,
+            "refine_lr": args.refine_lr}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -1256,6 +1534,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if getattr(args, "steps", None):
             raise Iclr17Error("iclr17: codec: step and msssim given together (at most one of step, "
                               "max_bytes, bpp, msssim)")
+    if getattr(args, "refine", None) is not None:   # the same, for refinement
+        with kernels.precision_scope(args.precision or kernels.precision()):
+            rate_request(1, step=getattr(args, "step", None),
+                         max_bytes=getattr(args, "max_bytes", None), bpp=getattr(args, "bpp", None),
+                         rdo=args.rdo, psnr=args.psnr, msssim=args.msssim,
+                         step_offsets=[None] if getattr(args, "roi", None) else None,
+                         **_refine_of(args))
     net = _model(args)
     with kernels.precision_scope(args.precision or kernels.precision()):
         if args.cmd == "encode":
@@ -1265,7 +1550,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                        "block": args.block}
             blob = net.compress_images([image], step=args.step, max_bytes=args.max_bytes,
                                        bpp=args.bpp, rdo=args.rdo, tile=args.tile,
-                                       psnr=args.psnr, msssim=args.msssim, **roi)[0]
+                                       psnr=args.psnr, msssim=args.msssim, **roi,
+                                       **_refine_of(args))[0]
             with open(args.output, "wb") as f:
                 f.write(blob)
         elif args.cmd == "decode":
@@ -1282,7 +1568,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             steps = [int(t) for t in args.steps.split(",")] if args.steps else [None]
             for step in steps:
                 rows = net.evaluate_images(imgs, want_msssim=args.ms_ssim, step=step,
-                                           rdo=args.rdo, psnr=args.psnr, msssim=args.msssim)
+                                           rdo=args.rdo, psnr=args.psnr, msssim=args.msssim,
+                                           **_refine_of(args))
                 tag = {} if step is None else {"step": step}
                 if args.psnr is not None:
                     tag["psnr"] = args.psnr
@@ -1290,6 +1577,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     tag["msssim"] = args.msssim
                 if args.rdo is not None:
                     tag["rdo"] = args.rdo
+                if args.refine:
+                    tag["refine"] = args.refine
                 for p, im, r in zip(args.images, imgs, rows):
                     print(json.dumps({"name": p, **tag, "H": im.shape[0], "W": im.shape[1],
                                       "bytes": r["bytes"], "bpp": r["bpp"], "psnr_u8": r["psnr_u8"],

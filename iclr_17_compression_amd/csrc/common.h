@@ -182,11 +182,12 @@ __device__ __forceinline__ float bits_regs(float z, float sp0, const float (&p)[
 }
 
 // The backward of element_bits at one element, as the autograd of model.py:71-78 /
-// bitEstimator.py:20-25 evaluates it: returns gsc · ∂bits/∂z and adds gsc · ∂bits/∂(row k of the
-// pack) into pg[k]. Shared by the rate epilogue of deconv1's dgrad (engine.h) and the stepped
-// training step (steptrain.hip).
-__device__ __forceinline__ float rate_bwd_element(float z, const float* __restrict__ rp, int C,
-                                                  int c, float gsc, float (&pg)[11]) {
+// bitEstimator.py:20-25 evaluates it: returns gsc · ∂bits/∂z and, with PARAMS, adds gsc ·
+// ∂bits/∂(row k of the pack) into pg[k] (without: pg is not touched and may be null). One body for
+// rate_bwd_element and rate_dz_element below.
+template <bool PARAMS>
+__device__ __forceinline__ float rate_bwd_body(float z, const float* __restrict__ rp, int C, int c,
+                                               float gsc, float* pg) {
   float xs[2][4], Ts[2][3], F[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -213,22 +214,60 @@ __device__ __forceinline__ float rate_bwd_element(float z, const float* __restri
   for (int h = 0; h < 2; ++h) {
     const float gF = h == 0 ? gl : -gl;
     const float gt4 = (gF * (1.0f - F[h])) * F[h];        // sigmoid backward
-    pg[10] += gt4;                                          // b4
-    pg[9] += gt4 * xs[h][3];                                // softplus(h4)
+    if constexpr (PARAMS) {
+      pg[10] += gt4;                                        // b4
+      pg[9] += gt4 * xs[h][3];                              // softplus(h4)
+    }
     float gx = gt4 * rp[9 * C + c];
 #pragma unroll
     for (int k = 2; k >= 0; --k) {
       const float T = Ts[h][k];
       const float gT = gx * rp[(3 * k + 2) * C + c];
-      pg[3 * k + 2] += gx * T;                              // tanh(a_k)
+      if constexpr (PARAMS) pg[3 * k + 2] += gx * T;        // tanh(a_k)
       const float gt = gx + gT * (1.0f - T * T);            // tanh backward
-      pg[3 * k + 1] += gt;                                  // b_k
-      pg[3 * k] += gt * xs[h][k];                           // softplus(h_k)
+      if constexpr (PARAMS) {
+        pg[3 * k + 1] += gt;                                // b_k
+        pg[3 * k] += gt * xs[h][k];                         // softplus(h_k)
+      }
       gx = gt * rp[(3 * k) * C + c];
     }
     dz += gx;
   }
   return dz;
+}
+
+// Shared by the rate epilogue of deconv1's dgrad (engine.h) and the stepped training step
+// (steptrain.hip).
+__device__ __forceinline__ float rate_bwd_element(float z, const float* __restrict__ rp, int C,
+                                                  int c, float gsc, float (&pg)[11]) {
+  return rate_bwd_body<true>(z, rp, C, c, gsc, pg);
+}
+
+// gsc · ∂bits/∂z alone, the same operations in the same order: latent refinement (refine.hip)
+__device__ __forceinline__ float rate_dz_element(float z, const float* __restrict__ rp, int C,
+                                                 int c, float gsc) {
+  return rate_bwd_body<false>(z, rp, C, c, gsc, nullptr);
+}
+
+// ----------------------------------------------------------------------------- Adam
+// One element of torch.optim.Adam's single-tensor step (optim.hip has the derivation): the new
+// moments go back through m and v, the new parameter is returned. -ffp-contract=off: the two fmas
+// are explicit and nothing else fuses.
+struct AdamScalars {
+  float neg_step_size;   // −lr / (1 − β1^t)
+  float bc2_sqrt;        // √(1 − β2^t)
+  float w1;              // 1 − β1
+  float beta2;
+  float c2;              // 1 − β2
+  float eps;
+};
+
+__device__ __forceinline__ float adam_element(float p, float g, float& m, float& v,
+                                              const AdamScalars& a) {
+  m = fmaf(a.w1, g - m, m);
+  v = fmaf(a.c2 * g, g, v * a.beta2);
+  const float d = sqrtf(v) / a.bc2_sqrt + a.eps;
+  return p + (a.neg_step_size * m) / d;
 }
 
 // Exact three-way bf16 split of 8 floats: x = hi + mid + lo, each part a bf16 (truncation

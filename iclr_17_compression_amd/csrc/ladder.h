@@ -12,6 +12,8 @@
 //                   wave_sum, float64 over waves 0..3, partial[b][s][chunk]) and run_sweep is the
 //                   host's sequence up to iclr17_reduce_partials. chunk_sum_store is the tail of
 //                   one sum.
+//   a step pack     the rate parameters with row 0 · Δ_b staged in LDS (stage_step_pack) and the
+//                   shape checks of a kernel that stages one: steptrain.hip and refine.hip.
 //
 // The chunk is aux.hip's kRateChunk and the thread → element map is rate_bits_kernel's, so a
 // sweep's partials are rate_bits' own, term for term and in its order of addition: no atomics in a
@@ -265,6 +267,29 @@ __device__ __forceinline__ void chunk_sum_store(float v, const Chunk& k, int chu
   __shared__ float red[4][1];
   sweep_wave(red, k, 0, v);
   sweep_store(red, 1, k, chunks, partial);
+}
+
+// ------------------------------------------------------------------------------ step packs
+constexpr size_t kStepLdsMax = 64 * 1024;
+
+// The step pack of image b in LDS: the [11][C] rate floats with row 0 · Δ_b, the fp32 product
+// pack_rate_step_kernel (ratectl.hip) makes. Shared by steptrain.hip and refine.hip.
+__device__ __forceinline__ void stage_step_pack(const float* __restrict__ rp, int C, float d,
+                                                float* __restrict__ sp) {
+  for (int i = threadIdx.x; i < kRateRows * C; i += blockDim.x) sp[i] = i < C ? rp[i] * d : rp[i];
+  __syncthreads();
+}
+
+// the shape checks of a kernel that stages a step pack; *shm: its LDS bytes
+inline int check_step_shape(const char* what, int B, int h, int w, int N, size_t* shm) {
+  const int rc = check_latent(what, B, h, w, N);
+  if (rc) return rc;
+  *shm = (size_t)kRateRows * N * sizeof(float);
+  ICLR17_REQUIRE(*shm <= kStepLdsMax - 64, ICLR17_EUNSUPPORTED, "%s: N=%d needs %zu bytes of LDS",
+                 what, N, *shm);
+  ICLR17_REQUIRE((long)B * h * w * N < (1L << 40), ICLR17_EUNSUPPORTED, "%s: %ld latents", what,
+                 (long)B * h * w * N);
+  return 0;
 }
 
 }  // namespace iclr17

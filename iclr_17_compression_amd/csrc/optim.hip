@@ -10,7 +10,7 @@
 //   d  = √v / √bc2 + ε                   bc2 = 1 − β2^t, from double scalars cast to fp32
 //   p  = p + (−lr/bc1 · m) / d           addcdiv_(m, d, value=−lr/bc1), bc1 = 1 − β1^t
 // The library is built with -ffp-contract=off, so the two fmas are explicit and nothing else
-// fuses.
+// fuses. The element update is common.h's adam_element, which latent refinement (refine.hip) shares.
 #include "common.h"
 
 namespace iclr17 {
@@ -25,9 +25,7 @@ struct AdamTensor {   // mirrors the int64 [5] rows of the descriptor table
 };
 
 __global__ void __launch_bounds__(256) adam_step_kernel(const AdamTensor* __restrict__ desc,
-                                                        float neg_step_size, float bc2_sqrt,
-                                                        float w1, float beta2, float c2, float eps,
-                                                        float clip) {
+                                                        AdamScalars a, float clip) {
   const AdamTensor t = desc[blockIdx.y];
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < t.n; i += (long)gridDim.x * 256) {
     float g = t.g[i];
@@ -35,12 +33,11 @@ __global__ void __launch_bounds__(256) adam_step_kernel(const AdamTensor* __rest
       g = fminf(fmaxf(g, -clip), clip);
       t.g[i] = g;
     }
-    const float m = fmaf(w1, g - t.m[i], t.m[i]);
-    const float v = fmaf(c2 * g, g, t.v[i] * beta2);
+    float m = t.m[i], v = t.v[i];
+    const float p = adam_element(t.p[i], g, m, v, a);
     t.m[i] = m;
     t.v[i] = v;
-    const float d = sqrtf(v) / bc2_sqrt + eps;
-    t.p[i] = t.p[i] + (neg_step_size * m) / d;
+    t.p[i] = p;
   }
 }
 
@@ -65,8 +62,9 @@ int iclr17_adam_step(const int64_t* desc, int n_tensors, long max_numel, double 
   const long bx = (max_numel + per_block - 1) / per_block;
   dim3 grid((unsigned)(bx < 1024 ? bx : 1024), (unsigned)n_tensors);
   hipLaunchKernelGGL(adam_step_kernel, grid, dim3(256), 0, (hipStream_t)stream,
-                     (const AdamTensor*)desc, (float)(-step_size), (float)bc2_sqrt,
-                     (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                     (const AdamTensor*)desc,
+                     AdamScalars{(float)(-step_size), (float)bc2_sqrt, (float)(1.0 - beta1),
+                                 (float)beta2, (float)(1.0 - beta2), (float)eps},
                      grad_clip);
   return check_launch("adam_step");
 }

@@ -25,15 +25,6 @@ namespace iclr17 {
 namespace {
 
 constexpr int kStepBwdPixels = 16;   // pixels per workgroup (and per partial row) of the backward
-constexpr size_t kStepLdsMax = 64 * 1024;
-
-// The step pack of image b in LDS: the [11][C] rate floats with row 0 · Δ_b, the fp32 product
-// pack_rate_step_kernel (ratectl.hip) makes.
-__device__ __forceinline__ void stage_step_pack(const float* __restrict__ rp, int C, float d,
-                                                float* __restrict__ sp) {
-  for (int i = threadIdx.x; i < kRateRows * C; i += blockDim.x) sp[i] = i < C ? rp[i] * d : rp[i];
-  __syncthreads();
-}
 
 // One workgroup per (image, 4096-element chunk of its NHWC latent). noise is NCHW, as
 // ImageCompressor._latent_noise draws it and conv3's noise quantiser reads it.
@@ -107,17 +98,6 @@ __global__ void grad_recon_images_kernel(const float* __restrict__ recon,
     if (g_clip != nullptr && r >= 0.0f && r <= 1.0f) g = g + g_clip[i];
     out[i] = g;
   }
-}
-
-int check_step_shape(const char* what, int B, int h, int w, int N, size_t* shm) {
-  const int rc = check_latent(what, B, h, w, N);
-  if (rc) return rc;
-  *shm = (size_t)kRateRows * N * sizeof(float);
-  ICLR17_REQUIRE(*shm <= kStepLdsMax - 64, ICLR17_EUNSUPPORTED, "%s: N=%d needs %zu bytes of LDS",
-                 what, N, *shm);
-  ICLR17_REQUIRE((long)B * h * w * N < (1L << 40), ICLR17_EUNSUPPORTED, "%s: %ld latents", what,
-                 (long)B * h * w * N);
-  return 0;
 }
 
 }  // namespace

@@ -1693,6 +1693,103 @@ def grad_recon_images(recon: Tensor, x: Tensor, g_mse: Optional[Tensor],
     return out
 
 
+# ------------------------------------------------------------ latent refinement (csrc/refine.hip)
+def refine_grad_recon(recon: Tensor, ref: Tensor, desc: Tensor, wt: Tensor) -> Tensor:
+    """∂(wt_b · Σ (recon − ref/255)²)/∂recon over each image's own H×W: recon fp32 [B,3,Hc,Wc]
+    (unclipped), ``ref`` the packed uint8 originals and ``desc`` their checked int64 [B, 4]
+    descriptors on the device (``_image_desc``, as ``image_sse_device`` takes them), ``wt`` fp32 [B]
+    → g[b,c,i,j] = wt_b·(2·(recon − ref/255)) for i < H_b, j < W_b and exact zeros on the canvas
+    padding."""
+    _check(recon, "reconstruction", 4)
+    B, C, Hc, Wc = recon.shape
+    if C != 3:
+        raise Iclr17Error(f"iclr17: refine_grad_recon takes a [B,3,Hc,Wc] reconstruction (got {C} "
+                          "channels)")
+    _check_u8(ref, "reference bytes")
+    ref = _check_u8_gpu(ref, "reference bytes")
+    _check(wt, "weights", 1)
+    if (tuple(desc.shape) != (B, 4) or desc.dtype != torch.int64 or desc.device != recon.device
+            or wt.numel() != B):
+        raise Iclr17Error(f"iclr17: refine_grad_recon: descriptors int64 [{B}, 4] on the device and "
+                          f"{B} weights (got {desc.dtype} {tuple(desc.shape)}, {wt.numel()})")
+    out = torch.empty_like(recon)
+    call("iclr17_refine_grad_recon", _p(recon.contiguous()), _p(ref), _p(desc.contiguous()),
+         _p(wt.contiguous()), B, Hc, Wc, _p(out), _stream(recon))
+    return out
+
+
+def refine_bits_partials(y: Tensor) -> Tensor:
+    """The float64 [B, T] partials buffer of ``refine_step`` for a latent batch y [B,h,w,N]."""
+    B, h, w, N = y.shape
+    return torch.empty(B, query("iclr17_rate_bits_partials", N, h, w), device=y.device,
+                       dtype=torch.float64)
+
+
+def refine_step(y: Tensor, steps_dev: Tensor, rate_packed: Tensor, y_hat: Tensor, y_deq: Tensor,
+                status: Tensor, bits_partial: Tensor, g_deq: Optional[Tensor] = None,
+                m: Optional[Tensor] = None, v: Optional[Tensor] = None, lr: float = 0.0,
+                t: int = 0, g_out: Optional[Tensor] = None) -> None:
+    """One pass of latent refinement over y fp32 NHWC [B,h,w,N], everything in place (no tensor is
+    made here and nothing is read back: the loop has no host synchronisation).
+
+    With ``g_deq`` (∂J/∂ỹ, the synthesis data gradient): g = g_deq + ∂bits/∂z(ŷ)/Δ_b on the step
+    pack of Δ_b (``step_noise_rate_backward``'s derivative with g_bits = 1, bit for bit; into
+    ``g_out`` when given), then Adam step number ``t`` ≥ 1 on (y, ``m``, ``v``) with torch.optim.Adam's
+    defaults and the learning rate ``lr``·Δ_b. Then, and without ``g_deq`` only this (iteration 0),
+    the next iterate: ``y_hat`` = rint(y/Δ_b) and ``y_deq`` = Δ_b·ŷ as ``quantise_steps`` gives them,
+    ``status`` (int32 [B]) the quantiser's bits per image and ``bits_partial``
+    (``refine_bits_partials``) ``rate_bits``' partials of ŷ on the step pack, for
+    ``reduce_partials``. ``steps_dev``: fp32 [B], finite and > 0 (the caller's duty)."""
+    B, h, w, N = _step_args(y, steps_dev, rate_packed, "refine_step")
+    tensors = [y_hat, y_deq] + ([] if g_deq is None else [g_deq, m, v]) + \
+        ([] if g_out is None else [g_out])
+    for q in [y] + tensors:
+        _check(q, "latent", 4)
+        if tuple(q.shape) != (B, h, w, N) or not q.is_contiguous():
+            raise Iclr17Error("iclr17: refine_step: every latent-shaped tensor must be contiguous "
+                              f"[{B}, {h}, {w}, {N}]")
+    T = query("iclr17_rate_bits_partials", N, h, w)
+    if (status.dtype != torch.int32 or status.numel() != B or status.device != y.device
+            or bits_partial.dtype != torch.float64 or tuple(bits_partial.shape) != (B, T)
+            or bits_partial.device != y.device or not bits_partial.is_contiguous()):
+        raise Iclr17Error(f"iclr17: refine_step: status int32 [{B}] and partials float64 [{B}, {T}] "
+                          "on the latent's device")
+    call("iclr17_refine_step", _p(y_hat if g_deq is not None else None), _p(g_deq), _p(y), _p(m),
+         _p(v), B, h, w, N, _p(steps_dev.contiguous()), _p(rate_packed), ctypes.c_double(lr),
+         int(t), _p(g_out), _p(y_hat), _p(y_deq), _p(status), _p(bits_partial), _stream(y))
+
+
+def refine_keep(bits: Tensor, sse: Tensor, lam: Tensor, qstatus: Tensor,
+                recon_status: Optional[Tensor], y_hat: Tensor, it: int, best_J: Tensor,
+                best_iter: Tensor, best_bits: Tensor, best_sse: Tensor, best: Tensor,
+                flag: Tensor) -> None:
+    """Keep the best iterate, in place: J_b = bits_b + ((λ_b/3)·SSE_b)/255² in float64 (``bits``,
+    ``lam`` float64 [B], ``sse`` int64 [B]); where J_b < ``best_J``[b] — strictly; a NaN, a non-zero
+    ``qstatus``[b] (int32 [B]) and a non-zero ``recon_status`` (int32 [1] | None, ``image_sse``'s)
+    count as not better — ``best_J``, ``best_iter`` (int32, = ``it``), ``best_bits`` and ``best_sse``
+    take the iterate's values and image b of ``y_hat`` is copied into ``best``. ``flag``: int32 [B]
+    of scratch (1 where kept)."""
+    _check(y_hat, "latent")
+    B = y_hat.shape[0]
+    dev = y_hat.device
+    want = ((bits, torch.float64), (sse, torch.int64), (lam, torch.float64),
+            (qstatus, torch.int32), (best_J, torch.float64), (best_iter, torch.int32),
+            (best_bits, torch.float64), (best_sse, torch.int64), (flag, torch.int32))
+    for q, dt in want:
+        if q.dtype != dt or q.numel() != B or q.device != dev or not q.is_contiguous():
+            raise Iclr17Error(f"iclr17: refine_keep: a per-image argument is not {dt} [{B}] on the "
+                              "latent's device")
+    if (best.shape != y_hat.shape or best.dtype != torch.float32 or best.device != dev
+            or not best.is_contiguous() or not y_hat.is_contiguous()):
+        raise Iclr17Error("iclr17: refine_keep: best must be a contiguous fp32 tensor of the latent's "
+                          "shape")
+    if recon_status is not None and (recon_status.dtype != torch.int32 or recon_status.device != dev):
+        raise Iclr17Error("iclr17: refine_keep: recon_status must be an int32 tensor on the device")
+    call("iclr17_refine_keep", _p(bits), _p(sse), _p(lam), _p(qstatus), _p(recon_status),
+         _p(y_hat), B, y_hat.numel() // B, int(it), _p(best_J), _p(best_iter), _p(best_bits),
+         _p(best_sse), _p(best), _p(flag), _stream(y_hat))
+
+
 # ---------------------------------------------------------------- image files (§1 f5)
 def _image_desc(what: str, nbytes: int, offsets, shapes, canvas) -> Tensor:
     """The int64 [B][4] descriptors {byte offset, H, W, 0} of uint8 HWC images packed in a buffer

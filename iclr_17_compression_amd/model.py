@@ -532,7 +532,7 @@ class ImageCompressor(nn.Module):
                         max_bytes=None, bpp=None, stats: Optional[dict] = None,
                         step_offsets=None, block: int = 4, rdo=None, rdo_weights=None,
                         tile: Optional[int] = None, psnr=None, estimate: Optional[bool] = None,
-                        msssim=None):
+                        msssim=None, refine=None, refine_lambda=None, refine_lr=None):
         """8-bit images of any sizes ≥ 1×1 (a sequence of uint8 HWC RGB arrays, numpy or torch) →
         one self-describing blob per image, in input order: codec.py's 28-byte header (true size,
         N, P, K, weights fingerprint) + the image's ``compress`` string. Images are batched by
@@ -587,14 +587,48 @@ class ImageCompressor(nn.Module):
         (kernels.image_msssim); ``stats`` receives "probes" and "ms_ssim" (the value at the index,
         which is ``evaluate_images``' ``ms_ssim`` of the blob). Both sides of every image must be
         at least 161; with another rate option, ``rdo``, ``step_offsets`` or ``estimate=True`` it
-        raises."""
+        raises.
+
+        ``refine`` (K ≥ 0 gradient iterations; 0 and None: today's code and bytes) refines the
+        latent of each image before it is coded (codec.py, "Latent refinement"):
+        Adam steps on y lower J = bits + (λ/3)·SSE8/255² through the real synthesis and the real
+        rate model, straight through the rounding, and the best ŷ seen is coded where its 8-bit
+        decode has a strictly lower J than the plain one. ``refine_lambda`` (finite, ≥ 0; a scalar
+        or one value per image; required) is λ in train.py's units (λ·mse + bpp), ``refine_lr`` the
+        Adam learning rate in units of Δ (None: codec.DEFAULT_REFINE_LR). It goes with ``step``
+        (none given: index 8) and ``tile``; the blobs are ordinary I17Q / I17T ones and any decoder
+        reads them. With a budget, a quality target, ``rdo`` or ``step_offsets`` and in the bf16
+        mode it raises. ``stats`` receives "refine_kept", "objective", "objective_plain" and
+        "refine_iters" per image."""
         from . import codec
         return codec.compress_images(self, images, max_batch, streams_per_image, K, step=step,
                                      max_bytes=max_bytes, bpp=bpp, stats=stats,
                                      step_offsets=step_offsets, block=block, rdo=rdo,
                                      rdo_weights=rdo_weights, tile=tile, psnr=psnr,
                                      estimate=codec.DEFAULT_ESTIMATE if estimate is None else estimate,
-                                     msssim=msssim)
+                                     msssim=msssim, refine=refine, refine_lambda=refine_lambda,
+                                     refine_lr=refine_lr)
+
+    @torch.no_grad()
+    def refine_latents(self, y: torch.Tensor, steps, refine_lambda, packed, offsets, shapes,
+                       refine: int, refine_lr=None, stats: Optional[dict] = None) -> torch.Tensor:
+        """Latent refinement of one canvas batch → the ŷ to code, fp32 NHWC,
+        integer-valued. ``y``: the batch's latent (``latents``); ``steps``: a ladder index or one
+        per image; ``refine_lambda``: λ, a scalar or one per image; ``packed`` / ``offsets`` /
+        ``shapes``: the 8-bit originals on the device as codec.upload_packed returns them (all of
+        one canvas); ``refine``: the iterations K; ``refine_lr``: the learning rate in units of Δ
+        (None: codec.DEFAULT_REFINE_LR). K + 1 passes of quantiser, training forward of the
+        synthesis, 8-bit SSE and keep-the-best with K data-gradient backwards between them, no
+        host synchronisation inside (codec.refine_loop); then the best iterate and the plain
+        ŷ = rint(y/Δ) are judged through the eval chain, and the best is returned only where its
+        J = bits + (λ/3)·SSE8/255² is strictly lower. ``stats`` as in ``compress_images``. Not in the
+        bf16 mode."""
+        from . import codec
+        B = y.shape[0]
+        idx = self._step_indices(steps, B)
+        lams = codec._per_image("refine_lambda", refine_lambda, B, codec.refine_lambda_value)
+        return codec.refine_latents(self, y, idx, lams, packed, offsets, shapes, refine,
+                                    refine_lr, stats)
 
     @torch.no_grad()
     def decompress_images(self, blobs, max_batch: int = 64):
@@ -624,7 +658,8 @@ class ImageCompressor(nn.Module):
     def evaluate_images(self, images, want_msssim: bool = False, max_batch: int = 64,
                         step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
                         block: int = 4, rdo=None, rdo_weights=None, tile: Optional[int] = None,
-                        psnr=None, estimate: Optional[bool] = None, msssim=None):
+                        psnr=None, estimate: Optional[bool] = None, msssim=None, refine=None,
+                        refine_lambda=None, refine_lr=None):
         """The real codec path per image, compress_images then decompress_images, measured on
         the 8-bit decoded image as codecs are reported: a dict per image with ``bytes``, ``bpp`` =
         8·len(blob)/(H·W) (header included, true pixel count), ``sse_u8`` (int), ``psnr_u8`` =
@@ -636,14 +671,18 @@ class ImageCompressor(nn.Module):
         ``step`` and also ``step_map`` and ``block``; with ``tile`` a row has the blob's ladder
         index as ``step`` and also ``tile``. ``psnr`` / ``estimate`` as in ``compress_images``: the
         row's ``step`` is the index found; so is ``msssim``, whose rows also carry ``ms_ssim`` and
-        ``ms_ssim_db`` as ``want_msssim`` gives them. Precision as ``decompress_images``."""
+        ``ms_ssim_db`` as ``want_msssim`` gives them. ``refine`` / ``refine_lambda`` /
+        ``refine_lr`` as in ``compress_images``: the rows then also carry ``refine_kept``,
+        ``objective``, ``objective_plain`` and ``refine_iters``. Precision as
+        ``decompress_images``."""
         from . import codec
         return codec.evaluate_images(self, images, want_msssim, max_batch, step=step,
                                      max_bytes=max_bytes, bpp=bpp, step_offsets=step_offsets,
                                      block=block, rdo=rdo, rdo_weights=rdo_weights, tile=tile,
                                      psnr=psnr,
                                      estimate=codec.DEFAULT_ESTIMATE if estimate is None else estimate,
-                                     msssim=msssim)
+                                     msssim=msssim, refine=refine, refine_lambda=refine_lambda,
+                                     refine_lr=refine_lr)
 
     @torch.no_grad()
     def evaluate(self, x: torch.Tensor, want_y: bool = False,

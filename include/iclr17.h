@@ -448,6 +448,44 @@ int iclr17_grad_recon_images(const float* recon, const float* x, const float* g_
                              const float* g_clip, int B, int64_t per_image, float* g_recon,
                              void* stream);
 
+/* ------------------------------------------------------------ latent refinement (csrc/refine.hip)
+ * The per-iteration kernels of an encoder that lowers J_b = bits_b + (λ_b/3)·SSE8_b/255² of each
+ * image by Adam steps on its latent, straight through the rounding. The stream and
+ * the decoder are unchanged. */
+/* g[b][c][i][j] = wt[b] · (2 · (recon − float(ref)/255)) for i < H_b, j < W_b, else 0. recon, g:
+ * fp32 [B][3][Hc][Wc]; ref: the packed uint8 HWC originals (any byte alignment); desc: the int64
+ * [B][4] rows {byte offset, H, W, 0} of iclr17_image_sse_u8 (the caller checks them: the library
+ * sees device memory); wt: device fp32 [B]. */
+int iclr17_refine_grad_recon(const float* recon, const uint8_t* ref, const int64_t* desc,
+                             const float* wt, int B, int Hc, int Wc, float* g, void* stream);
+/* One pass over the latent per iteration; every tensor fp32 NHWC [B][h][w][N], Δ = steps_dev[b]
+ * (device fp32 [B], finite and > 0: the caller's duty), rate_packed the UNscaled pack.
+ * With g_deq (= ∂J/∂ỹ):  g = g_deq + ∂bits/∂z(y_hat)/Δ on the step pack of Δ (the derivative
+ * iclr17_step_noise_rate_bwd takes, bit for bit, with g_bits = 1);  Adam step number `step` ≥ 1 of
+ * torch.optim.Adam (β = 0.9, 0.999, ε = 1e-8, bias correction; iclr17_adam_step's element update)
+ * with the learning rate lr·Δ on y, m, v in place;  g_out (nullable) receives g.
+ * Then, and with g_deq NULL only this (y_hat, m, v, g_out, lr, step unused: iteration 0):
+ * y_hat_out = rintf(y/Δ), y_deq = Δ·y_hat_out as iclr17_quantise_steps writes them, status[b] (int32
+ * [B], zeroed here) the quantiser's bits of image b, and bits_partial[B][iclr17_rate_bits_partials(
+ * N, h, w)]: rate_bits' own partials of y_hat_out on the step pack of Δ, for
+ * iclr17_reduce_partials. y_hat_out may be y_hat. No atomics in a sum: bitwise reproducible, an
+ * image's outputs independent of its batch. */
+int iclr17_refine_step(const float* y_hat, const float* g_deq, float* y, float* m, float* v, int B,
+                       int h, int w, int N, const float* steps_dev, const float* rate_packed,
+                       double lr, long step, float* g_out, float* y_hat_out, float* y_deq,
+                       int32_t* status, double* bits_partial, void* stream);
+/* J_b = bits[b] + ((lam[b]/3)·sse[b])/255² in float64 (bits, lam: device float64 [B]; sse: int64
+ * [B]). Where J_b < best_J[b] (strict; NaN, a non-zero qstatus[b] (int32 [B]) and a non-zero
+ * *recon_status (int32, nullable: iclr17_image_sse_u8's) count as not better): best_J[b] = J_b,
+ * best_iter[b] = iter, best_bits[b] = bits[b], best_sse[b] = sse[b] and image b of y_hat
+ * (per_image fp32 each) is copied into best. A first one-workgroup launch decides into flag
+ * (int32 [B] of scratch), the copy reads it: every block of an image sees one decision. */
+int iclr17_refine_keep(const double* bits, const int64_t* sse, const double* lam,
+                       const int32_t* qstatus, const int32_t* recon_status, const float* y_hat,
+                       int B, int64_t per_image, int iter, double* best_J, int32_t* best_iter,
+                       double* best_bits, int64_t* best_sse, float* best, int32_t* flag,
+                       void* stream);
+
 /* testKodak's MS-SSIM (train.py:178 → models/ms_ssim_torch.py:123-196): per-image
  * ms_ssim(x, y, data_range) of NCHW [B,3,H,W] fp32 images, 11-tap σ=1.5 window, 5 levels (each
  * level must be ≥ 11×11: H, W ≥ 161 or so), the reference's level weights and final product.

@@ -1,0 +1,129 @@
+"""Rate–distortion effect of latent refinement on trained weights (diagnostic, needs
+a GPU): tests/golden/g9_weights_n192.npz on the synthetic Kodak-24 set, ladder indices 4…16,
+K in 0, 5, 20, 100 iterations with λ = 650.25/Δ² (the checkpoint's λ where the latent distortion of
+the quantiser scales as it does at Δ = 1). Real blobs through ``evaluate_images``: per arm and index
+the means over the 24 images of bpp, psnr_u8 and MS-SSIM and how many images kept a refined
+latent; then, per refined point, the plain curve's PSNR and MS-SSIM at the same bpp (linear in bpp
+between the two neighbouring plain indices) and the difference: positive means above the plain
+curve.
+
+First a small sweep chooses the learning rate (``refine_lr``, in units of Δ): index 8, K = 20, the
+first six images, the candidate with the lowest mean objective relative to the plain one. The
+table is then made with that value, and it is what codec.DEFAULT_REFINE_LR records.
+
+    python tools/refine_rd.py [--out profiles/refine_rd.txt] [--first 4] [--last 16]
+                              [--iters 0,5,20,100] [--lr R]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from iclr_17_compression_amd import codec, synth  # noqa: E402
+from iclr_17_compression_amd.model import ImageCompressor  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--out", default="")
+ap.add_argument("--first", type=int, default=4)
+ap.add_argument("--last", type=int, default=16)
+ap.add_argument("--iters", default="0,5,20,100")
+ap.add_argument("--lr", type=float, default=None, help="skip the sweep and use this value")
+ap.add_argument("--sweep", default="0.001,0.003,0.01,0.03,0.1")
+args = ap.parse_args()
+dev = torch.device("cuda:0")
+ITERS = [int(v) for v in args.iters.split(",")]
+LAMBDA = 650.25
+PORTRAIT = (3, 8, 9, 16, 17, 18)
+out = open(args.out, "w") if args.out else None
+
+
+def emit(row):
+    line = json.dumps(row)
+    print(line, flush=True)
+    if out:
+        out.write(line + "\n")
+        out.flush()
+
+
+def lam_of(s):
+    return LAMBDA / codec.step_size(s) ** 2
+
+
+d = np.load(os.path.join(REPO, "tests", "golden", "g9_weights_n192.npz"))
+net = ImageCompressor(out_channel_N=192)
+net.load_state_dict({k: torch.from_numpy(d[k].astype(np.float32)) for k in d.files})
+net = net.to(dev).eval()
+imgs = [np.ascontiguousarray(synth.smooth_image_u8(100 + i, *((768, 512) if i in PORTRAIT
+                                                             else (512, 768))).transpose(1, 2, 0))
+        for i in range(24)]
+emit({"weights": "g9_weights_n192.npz", "images": "kodak-synth 24", "lambda": "650.25 / step^2",
+      "iters": ITERS})
+
+lr = args.lr
+if lr is None:
+    best = None
+    for cand in (float(v) for v in args.sweep.split(",")):
+        rows = net.evaluate_images(imgs[:6], step=8, refine=20, refine_lambda=lam_of(8),
+                                   refine_lr=cand)
+        rel = float(np.mean([r["objective"] / r["objective_plain"] for r in rows]))
+        emit({"lr_sweep": cand, "index": 8, "iters": 20, "images": 6,
+              "mean_objective_over_plain": round(rel, 6),
+              "kept": sum(r["refine_kept"] > 0 for r in rows),
+              "bpp": round(float(np.mean([r["bpp"] for r in rows])), 5),
+              "psnr_u8": round(float(np.mean([r["psnr_u8"] for r in rows])), 4)})
+        if best is None or rel < best[0]:
+            best = (rel, cand)
+    lr = best[1]
+emit({"refine_lr": lr, "default_in_codec_at_this_run": codec.DEFAULT_REFINE_LR})
+
+curves = {}
+for K in ITERS:
+    for s in range(args.first, args.last + 1):
+        rows = net.evaluate_images(imgs, want_msssim=True, step=s, refine=K,
+                                   refine_lambda=lam_of(s), refine_lr=lr)
+        point = {"bpp": float(np.mean([r["bpp"] for r in rows])),
+                 "psnr_u8": float(np.mean([r["psnr_u8"] for r in rows])),
+                 "ms_ssim": float(np.mean([r["ms_ssim"] for r in rows]))}
+        curves.setdefault(K, {})[s] = point
+        extra = {}
+        if K:
+            extra = {"kept": sum(r["refine_kept"] > 0 for r in rows),
+                     "mean_objective_over_plain": round(float(np.mean(
+                         [r["objective"] / r["objective_plain"] for r in rows])), 6)}
+        emit({"arm": f"refine={K}", "index": s, "bpp": round(point["bpp"], 5),
+              "psnr_u8": round(point["psnr_u8"], 4), "ms_ssim": round(point["ms_ssim"], 6), **extra})
+
+if 0 in curves:
+    plain = sorted(curves[0].values(), key=lambda q: q["bpp"])
+    xs = [q["bpp"] for q in plain]
+    for K in ITERS:
+        if not K:
+            continue
+        wins, wins_ms = [], []
+        for s, q in curves[K].items():
+            if not xs[0] <= q["bpp"] <= xs[-1]:
+                continue
+            at = {k: float(np.interp(q["bpp"], xs, [u[k] for u in plain]))
+                  for k in ("psnr_u8", "ms_ssim")}
+            row = {"arm": f"refine={K}", "index": s, "bpp": round(q["bpp"], 5),
+                   "bpp_saved_vs_plain_same_index": round(curves[0][s]["bpp"] - q["bpp"], 5),
+                   "plain_curve_psnr_at_bpp": round(at["psnr_u8"], 4),
+                   "psnr_minus_plain_curve_db": round(q["psnr_u8"] - at["psnr_u8"], 4),
+                   "plain_curve_ms_ssim_at_bpp": round(at["ms_ssim"], 6),
+                   "ms_ssim_minus_plain_curve": round(q["ms_ssim"] - at["ms_ssim"], 6)}
+            wins.append(row["psnr_minus_plain_curve_db"])
+            wins_ms.append(row["ms_ssim_minus_plain_curve"])
+            emit(row)
+        if wins:
+            emit({"arm": f"refine={K}", "summary": "psnr minus the plain curve at equal bpp, over "
+                  "the indices inside the plain curve's range", "points": len(wins),
+                  "above": sum(v > 0 for v in wins), "mean_db": round(float(np.mean(wins)), 4),
+                  "min_db": round(min(wins), 4), "max_db": round(max(wins), 4),
+                  "mean_ms_ssim_diff": round(float(np.mean(wins_ms)), 6)})
+if out:
+    out.close()
