@@ -105,6 +105,9 @@ SIGNATURES = {
     "iclr17_image_sse_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "iclr17_image_msssim_workspace_size": (_SZ, [_I, _I, _I]),
     "iclr17_image_msssim_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _SZ, _P, _P, _P]),
+    "iclr17_image_msssim_grad_workspace_size": (_SZ, [_I, _I, _I]),
+    "iclr17_image_msssim_u8_fwd_saved": (_I, [_P, _P, _I, _I, _I, _P, _P, _SZ, _P, _P, _P]),
+    "iclr17_image_msssim_u8_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _SZ, _P, _P, _P]),
     "iclr17_rate_sweep_rdo_partials": (_I, [_I, _I, _I]),
     "iclr17_quantise_rdo": (_I, [_P, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
     "iclr17_rate_sweep_rdo": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
@@ -128,6 +131,8 @@ SIGNATURES = {
     "iclr17_refine_step": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _D, ctypes.c_long, _P,
                                 _P, _P, _P, _P, _P]),
     "iclr17_refine_keep": (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "iclr17_refine_keep_msssim": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, _I, _P, _P, _P, _P, _P,
+                                       _P, _P]),
     "iclr17_ms_ssim_workspace_size": (_SZ, [_I, _I, _I]),
     "iclr17_ms_ssim": (_I, [_P, _P, _I, _I, _I, _F, _P, _SZ, _P, _P]),
     "iclr17_ssim_workspace_size": (_SZ, [_I, _I, _I]),

@@ -134,6 +134,14 @@ decoder reads them. ``refine`` goes with ``step`` (none: index 8) and ``tile``; 
 quality target, ``rdo`` or ``step_offsets`` and in the bf16 mode it raises; 0 and None are the call
 without it. ``refine_lr`` (in units of Δ) defaults to ``DEFAULT_REFINE_LR``.
 
+The objective rides on λ: ``refine_lambda=msssim_lambda(λ)`` (a scalar, or one per
+image; mixing the two kinds raises) refines for J = bits + λ·H·W·(1 − MS-SSIM8), H·W times train.py's
+λ·(1 − MS-SSIM) + bpp on the 8-bit decode. The loop then measures with
+``kernels.image_msssim_fwd_saved``, decides with ``kernels.refine_keep_msssim`` and takes the
+distortion gradient from ``kernels.image_msssim_bwd``; the judge measures ``image_msssim`` on both
+decodes. Both sides of every image must be at least 161. ``stats`` and ``evaluate_images`` rows
+also carry ``refine_distortion`` ("ms-ssim"), ``ms_ssim`` and ``ms_ssim_plain``.
+
 Region decode. ``decompress_region(blob, box)`` returns the pixels of ``box`` = (x0, y0, x1, y1)
 (half-open, inside the image), byte for byte the crop of the full decode, from the tiles it needs
 alone. The synthesis is deconv 5×5/s2/p2, IGDN, deconv 5×5/s2/p2, IGDN, deconv 9×9/s4/p4; IGDN is
@@ -148,12 +156,14 @@ its own, and ``image_egress`` runs on the crop.
                                             [--step S | --max-bytes B | --bpp R | --psnr T |
                                              --msssim T]
                                             [--roi X0,Y0,X1,Y1,OFF ...] [--block G] [--rdo L]
-                                            [--tile T] [--refine K --refine-lambda L [--refine-lr R]]
+                                            [--tile T] [--refine K --refine-lambda L [--refine-lr R]
+                                             [--refine-distortion mse|ms-ssim]]
     python -m iclr_17_compression_amd.codec decode IN.i17c OUT.png --weights CKPT
                                             [--region X0,Y0,X1,Y1]
     python -m iclr_17_compression_amd.codec eval IMG... --weights CKPT [--ms-ssim] [--steps 4,8,12]
                                             [--rdo L] [--psnr T | --msssim T]
-                                            [--refine K --refine-lambda L [--refine-lr R]]
+                                            [--refine K --refine-lambda L [--refine-lr R]
+                                             [--refine-distortion mse|ms-ssim]]
 """
 from __future__ import annotations
 
@@ -824,15 +834,45 @@ def refine_value(refine) -> int:
     return int(refine)
 
 
+class MsssimLambda(float):
+    """A ``refine_lambda`` whose distortion is MS-SSIM: J = bits + λ·H·W·(1 −
+    MS-SSIM of the 8-bit decode), H·W times train.py's λ·(1 − MS-SSIM) + bpp. The objective rides
+    on λ, whose unit it fixes; make one with ``msssim_lambda``."""
+    __slots__ = ()
+
+    def __repr__(self) -> str:
+        return f"msssim_lambda({float(self)!r})"
+
+
+def msssim_lambda(lam) -> MsssimLambda:
+    """λ of latent refinement for MS-SSIM, checked as ``refine_lambda_value`` checks a plain one:
+    ``compress_images(..., refine=K, refine_lambda=msssim_lambda(8.0))``."""
+    return MsssimLambda(refine_lambda_value(float(lam) if isinstance(lam, MsssimLambda) else lam))
+
+
 def refine_lambda_value(lam) -> float:
     """One ``refine_lambda`` checked on the host: a real number, not a bool, finite (as an fp32
-    value too) and ≥ 0 → float."""
+    value too) and ≥ 0 → float; a ``MsssimLambda`` stays one."""
     if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)):
         raise Iclr17Error(f"iclr17: codec: refine_lambda must be a real number (got {lam!r})")
     v = float(lam)
     if not (math.isfinite(v) and 0.0 <= v <= float(np.finfo(np.float32).max)):
         raise Iclr17Error(f"iclr17: codec: refine_lambda must be finite and >= 0 (got {lam!r})")
-    return v
+    return MsssimLambda(v) if isinstance(lam, MsssimLambda) else v
+
+
+REFINE_DISTORTIONS = ("mse", "ms-ssim")   # what refine_objective_kind answers; --refine-distortion
+REFINE_MIXED_OBJECTIVES = ("iclr17: codec: refine_lambda mixes plain and MS-SSIM values: mixed "
+                           "objectives in one call are not built")
+
+
+def refine_objective_kind(lams) -> str:
+    """"ms-ssim" when every λ is a ``MsssimLambda``, "mse" when none is; a mixture raises
+    ``REFINE_MIXED_OBJECTIVES``."""
+    kinds = {isinstance(v, MsssimLambda) for v in lams}
+    if len(kinds) > 1:
+        raise Iclr17Error(REFINE_MIXED_OBJECTIVES)
+    return "ms-ssim" if kinds == {True} else "mse"
 
 
 def refine_lr_value(lr) -> float:
@@ -855,6 +895,13 @@ def refine_objective(bits: float, sse: int, lam: float) -> float:
     return float(bits) + (float(lam) / 3.0) * float(int(sse)) / 65025.0
 
 
+def refine_objective_msssim(bits: float, ms: float, lam: float, H: int, W: int) -> float:
+    """J = bits + λ·(H·W)·(1 − MS-SSIM8) in float64, evaluated left to right as written here (the
+    device evaluates the same operations, kernels.refine_keep_msssim; ``ms`` is the fp32 value,
+    widened): H·W times train.py's λ·(1 − MS-SSIM) + bpp on the real 8-bit decode."""
+    return float(bits) + float(lam) * float(int(H) * int(W)) * (1.0 - float(ms))
+
+
 def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None, rdo=None,
                  tile=None, psnr=None, msssim=None, estimate: bool = False, refine=None,
                  refine_lambda=None, refine_lr=None):
@@ -874,10 +921,13 @@ def rate_request(n: int, step=None, max_bytes=None, bpp=None, step_offsets=None,
     given: the unit step) and ``tile`` and gives ("refine", index, K, per-image λ, learning rate);
     with ``max_bytes``, ``bpp``, ``psnr``, ``msssim``, ``rdo`` or ``step_offsets`` (``REFINE_WITH``),
     without ``refine_lambda`` (a scalar or one value per image, ``refine_lambda_value``) and in the
-    bf16 precision mode it raises. ``refine`` 0 or None gives the request of the call without it."""
+    bf16 precision mode it raises. ``refine`` 0 or None gives the request of the call without it.
+    The λ carry the objective: ``msssim_lambda`` values (all of them: a mixture raises
+    ``REFINE_MIXED_OBJECTIVES``) stay ``MsssimLambda`` in the request and mean MS-SSIM."""
     iters = refine_value(refine)
     if refine_lambda is not None:
         lams = _per_image("refine_lambda", refine_lambda, n, refine_lambda_value)
+        refine_objective_kind(lams)   # one objective per call
     lr = refine_lr_value(refine_lr)
     if iters:
         for name, v in (("max_bytes", max_bytes), ("bpp", bpp), ("psnr", psnr), ("msssim", msssim),
@@ -1008,12 +1058,14 @@ def msssim_probe(net, y, packed, offsets, shapes):
 
 # what refine_loop leaves on the device: the best iterate's ŷ and the plain ŷ (fp32 NHWC), per
 # image the iteration kept (int32; −1: none passed), its J, bits (float64) and SSE (int64) as the
-# loop measured them, and iteration 0's bits and quantiser status (int32 [B])
+# loop measured them, and iteration 0's bits and quantiser status (int32 [B]). With the MS-SSIM
+# objective (``refine_loop(..., area=)``) ``best_sse`` holds the best iterate's MS-SSIM, fp32 [B]:
+# the field is the distortion measure of the objective in hand.
 RefineState = namedtuple("RefineState", "best plain best_iter best_J best_bits best_sse bits0 status0")
 
 
 def refine_loop(net, y, steps_dev, lam, wt, packed, desc, iters: int, lr: float,
-                mode: str) -> RefineState:
+                mode: str, area=None) -> RefineState:
     """The K + 1 iterations of latent refinement on one canvas batch, without a
     host synchronisation: everything it decides is decided on the device. ``y``: the fp32 NHWC
     latent of ``net.latents`` (not modified); ``steps_dev`` fp32 [B] (Δ_b), ``lam`` float64 [B]
@@ -1027,7 +1079,14 @@ def refine_loop(net, y, steps_dev, lam, wt, packed, desc, iters: int, lr: float,
     is: the same sums, and a non-finite value is seen), keep-the-best (kernels.refine_keep), and
     while t < K the gradient of the distortion through the synthesis
     (kernels.refine_grad_recon, autograd.synthesis_latent_grad) into the next refine_step, which
-    adds the rate derivative straight through the rounding and takes the Adam step."""
+    adds the rate derivative straight through the rounding and takes the Adam step.
+
+    With ``area`` (float64 [B], H_b·W_b, on the device) the distortion is MS-SSIM:
+    ``wt`` is then g_b = −λ_b·H_b·W_b (fp32 [B]), the measure is kernels.image_msssim_fwd_saved on
+    the unclipped output, the decision kernels.refine_keep_msssim and the gradient
+    kernels.image_msssim_bwd, on a workspace made once before the loop; ``best_sse`` of the result
+    holds the best iterate's MS-SSIM (fp32). The images have passed
+    ``kernels.check_msssim_shapes``."""
     from . import chain
     from .autograd import synthesis_latent_grad
     m = chain.train_mode(mode)
@@ -1042,20 +1101,34 @@ def refine_loop(net, y, steps_dev, lam, wt, packed, desc, iters: int, lr: float,
     best_J = torch.full((B,), math.inf, device=dev, dtype=torch.float64)
     best_iter = torch.full((B,), -1, device=dev, dtype=torch.int32)
     best_bits = torch.zeros(B, device=dev, dtype=torch.float64)
-    best_sse = torch.zeros(B, device=dev, dtype=torch.int64)
+    msssim = area is not None
+    best_sse = torch.zeros(B, device=dev, dtype=torch.float32 if msssim else torch.int64)
+    if msssim:
+        ws = kernels.image_msssim_grad_workspace(B, 16 * y.shape[1], 16 * y.shape[2], dev)
+        measured = (torch.empty(B, device=dev, dtype=torch.float32),
+                    torch.empty(1, device=dev, dtype=torch.int32))
+        d_recon = torch.empty(B, 3, 16 * y.shape[1], 16 * y.shape[2], device=dev)
     plain = bits0 = status0 = None
     with kernels.precision_scope(m.name):
         kernels.refine_step(y, steps_dev, rate, y_hat, y_deq, status, partial)
         for t in range(iters + 1):
             _, recon, _, saved = m.train_synthesis(dec, y_deq, None, None)
-            _, sse, rstatus, _ = kernels.image_sse_device(recon, None, None, packed, desc)
-            bits, _ = kernels.reduce_partials(partial)
-            kernels.refine_keep(bits, sse, lam, status, rstatus, y_hat, t, best_J, best_iter,
-                                best_bits, best_sse, best, flag)
+            if msssim:
+                recon = recon.contiguous()   # the chain's NCHW output: no copy
+                ms, rstatus = kernels.image_msssim_fwd_saved(recon, packed, desc, ws, measured)
+                bits, _ = kernels.reduce_partials(partial)
+                kernels.refine_keep_msssim(bits, ms, lam, area, status, rstatus, y_hat, t, best_J,
+                                           best_iter, best_bits, best_sse, best, flag)
+            else:
+                _, sse, rstatus, _ = kernels.image_sse_device(recon, None, None, packed, desc)
+                bits, _ = kernels.reduce_partials(partial)
+                kernels.refine_keep(bits, sse, lam, status, rstatus, y_hat, t, best_J, best_iter,
+                                    best_bits, best_sse, best, flag)
             if t == 0:
                 plain, bits0, status0 = y_hat.clone(), bits, status.clone()
             if t < iters:
-                g_recon = kernels.refine_grad_recon(recon, packed, desc, wt)
+                g_recon = (kernels.image_msssim_bwd(recon, packed, desc, ws, wt, d_recon)
+                           if msssim else kernels.refine_grad_recon(recon, packed, desc, wt))
                 g_y = synthesis_latent_grad(dec, saved, g_recon, mode=m.name)
                 kernels.refine_step(y, steps_dev, rate, y_hat, y_deq, status, partial,
                                     g_deq=g_y.contiguous(), m=mom, v=var, lr=lr, t=t + 1)
@@ -1075,7 +1148,13 @@ def refine_latents(net, y, indices: Sequence[int], lams: Sequence[float], packed
     J = ``refine_objective`` of both; the best iterate is coded only where its J is strictly lower
     (a non-finite decode counts as +inf), else the plain ŷ. One transfer, the call's only
     synchronisation. ``stats`` (a dict) receives per image "refine_kept" (the iteration coded; 0:
-    the plain ŷ), "objective", "objective_plain" and "refine_iters"."""
+    the plain ŷ), "objective", "objective_plain" and "refine_iters".
+
+    With ``MsssimLambda`` values in ``lams`` (all of them) the images must pass
+    ``kernels.check_msssim_shapes``, the judge takes ``image_msssim`` on both decodes and
+    J = ``refine_objective_msssim``; a NaN J (an MS-SSIM that is NaN: a level's mean is not
+    positive) counts as +inf on either side, as the device's "NaN is not better". ``stats`` then
+    also receives "refine_distortion" ("ms-ssim"), "ms_ssim" and "ms_ssim_plain", the judged values."""
     from . import chain
     mode = kernels.precision()
     if mode == "bf16":
@@ -1087,46 +1166,63 @@ def refine_latents(net, y, indices: Sequence[int], lams: Sequence[float], packed
         raise Iclr17Error(f"iclr17: codec: refine_latents takes one index, λ and shape per image "
                           f"for {B} images")
     lams = [refine_lambda_value(v) for v in lams]
+    msssim = refine_objective_kind(lams) == "ms-ssim"
+    if msssim:   # on the host, before any device work
+        kernels.check_msssim_shapes(shapes, [f"image {b} ({H}x{W})" for b, (H, W) in enumerate(shapes)])
     Hc, Wc = canvas(*shapes[0])
     if (y.shape[1], y.shape[2]) != (Hc // 16, Wc // 16):
         raise Iclr17Error("iclr17: codec: refine_latents: the latent is not the canvas batch's")
     desc = kernels._image_desc("refine", packed.numel(), offsets, shapes, (Hc, Wc))
-    host = torch.empty(B, 3, dtype=torch.float64, pin_memory=True)
+    host = torch.empty(B, 4, dtype=torch.float64, pin_memory=True)
     for b in range(B):
-        host[b, 0], host[b, 1], host[b, 2] = step_size(indices[b]), lams[b], lams[b] / 3.0
+        area = float(int(shapes[b][0]) * int(shapes[b][1]))
+        # the weight of the distortion gradient: λ_b/3 on 2·(recon − x), or ∂J/∂MS-SSIM_b
+        weight = float(np.float32(-(float(lams[b]) * area))) if msssim else lams[b] / 3.0
+        host[b, 0], host[b, 1], host[b, 2], host[b, 3] = step_size(indices[b]), lams[b], weight, area
     args = host.to(dev, non_blocking=True)
     steps_dev, lam = args[:, 0].float().contiguous(), args[:, 1].contiguous()
     wt = args[:, 2].float().contiguous()
     desc = desc.pin_memory().to(dev, non_blocking=True)
     net._warm_packs(backward=True, mode=mode)
     net._warm_packs(mode=mode)
-    st = refine_loop(net, y, steps_dev, lam, wt, packed, desc, iters, lr, mode)
+    st = refine_loop(net, y, steps_dev, lam, wt, packed, desc, iters, lr, mode,
+                     area=args[:, 3].contiguous() if msssim else None)
     em = chain.MODES[mode]
+    measure = MSSSIM_MEASURE if msssim else SSE_MEASURE
 
-    def decode_sse(y_hat):
+    def decode_measure(y_hat):
         y_deq = y_hat * steps_dev.view(B, 1, 1, 1)   # the fp32 product dequantise_step writes
         clipped, _, _ = em.synthesis(net.Decoder, y_deq, em.latent_operand(y_deq), None, False,
                                      False, None, False)
-        return kernels.image_sse_device(clipped, None, None, packed, desc)[0]
+        return measure.device_fn(clipped, None, None, packed, desc)[0]
 
-    parts = [decode_sse(st.best), decode_sse(st.plain), st.best_bits.view(torch.uint8),
+    parts = [decode_measure(st.best), decode_measure(st.plain), st.best_bits.view(torch.uint8),
              st.bits0.view(torch.uint8), st.best_iter.view(torch.uint8),
              st.status0.view(torch.uint8)]
     flat = torch.cat(parts).cpu().numpy()
-    n = 8 * B + 8
-    sse_b, bad_b = flat[:8 * B].view(np.int64), int(flat[8 * B:8 * B + 4].view(np.int32)[0])
-    sse_p = flat[n:n + 8 * B].view(np.int64)
-    bad_p = int(flat[n + 8 * B:n + 8 * B + 4].view(np.int32)[0])
+    size = measure.size * B
+    n = size + 8
+    dt = np.float32 if msssim else np.int64
+    got_b, bad_b = flat[:size].view(dt), int(flat[size:size + 4].view(np.int32)[0])
+    got_p = flat[n:n + size].view(dt)
+    bad_p = int(flat[n + size:n + size + 4].view(np.int32)[0])
     rest = flat[2 * n:]
     bits_b, bits_p = rest[:8 * B].view(np.float64), rest[8 * B:16 * B].view(np.float64)
     kept = rest[16 * B:20 * B].view(np.int32)
     kernels._step_status(torch.from_numpy(np.bitwise_or.reduce(rest[20 * B:24 * B].view(np.int32),
                                                                keepdims=True).copy()),
                          "quantise_steps")
+
+    def objective(b, bits, got):
+        if msssim:   # NaN (a NaN MS-SSIM): not better than anything, so +inf
+            J = refine_objective_msssim(bits[b], got[b], lams[b], *shapes[b])
+            return math.inf if math.isnan(J) else J
+        return refine_objective(bits[b], got[b], lams[b])
+
     use, J, J_plain = [], [], []
     for b in range(B):
-        jp = math.inf if bad_p else refine_objective(bits_p[b], sse_p[b], lams[b])
-        jb = math.inf if bad_b or kept[b] <= 0 else refine_objective(bits_b[b], sse_b[b], lams[b])
+        jp = math.inf if bad_p else objective(b, bits_p, got_p)
+        jb = math.inf if bad_b or kept[b] <= 0 else objective(b, bits_b, got_b)
         use.append(jb < jp)
         J.append(jb if use[b] else jp)
         J_plain.append(jp)
@@ -1139,6 +1235,10 @@ def refine_latents(net, y, indices: Sequence[int], lams: Sequence[float], packed
         stats["refine_kept"] = [int(kept[b]) if use[b] else 0 for b in range(B)]
         stats["objective"], stats["objective_plain"] = J, J_plain
         stats["refine_iters"] = [iters] * B
+        if msssim:
+            stats["refine_distortion"] = ["ms-ssim"] * B
+            stats["ms_ssim"] = [float(got_b[b] if use[b] else got_p[b]) for b in range(B)]
+            stats["ms_ssim_plain"] = [float(got_p[b]) for b in range(B)]
     return y_hat
 
 
@@ -1152,7 +1252,9 @@ def compress_images(net, images, max_batch: int = 64,
     imgs = [as_u8_hwc(im) for im in images]
     request = rate_request(len(imgs), step, max_bytes, bpp, step_offsets, rdo, tile, psnr, msssim,
                            estimate, refine, refine_lambda, refine_lr)
-    if request is not None and request[0] == "msssim":   # on the host, before the ingest
+    refine_msssim = (request is not None and request[0] == "refine"
+                     and refine_objective_kind(request[3]) == "ms-ssim")
+    if (request is not None and request[0] == "msssim") or refine_msssim:   # on the host, before the ingest
         sizes = [im.shape[:2] for im in imgs]
         kernels.check_msssim_shapes(sizes, [f"image {i} ({H}x{W})" for i, (H, W) in enumerate(sizes)])
     how = {} if rdo is None else {"rdo": rdo, "rdo_weights": rdo_weights}
@@ -1169,7 +1271,8 @@ def compress_images(net, images, max_batch: int = 64,
     reencodes = [0] * len(imgs)
     probes, sses = [0] * len(imgs), [None] * len(imgs)
     refined = {k: [None] * len(imgs) for k in ("refine_kept", "objective", "objective_plain",
-                                               "refine_iters")}
+                                               "refine_iters")
+               + (("refine_distortion", "ms_ssim", "ms_ssim_plain") if refine_msssim else ())}
     for idx in group_by_canvas([im.shape[:2] for im in imgs], max_batch):
         group = [imgs[i] for i in idx]
         packed, offsets, shapes = upload_packed(group, device)
@@ -1399,6 +1502,9 @@ def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
         for name in ("refine_kept", "objective", "objective_plain", "refine_iters"):
             if name in stats:
                 r[name] = stats[name][len(res)]
+        if "refine_distortion" in stats:   # an MS-SSIM refinement: the judged values (with
+            for name in ("refine_distortion", "ms_ssim", "ms_ssim_plain"):   # want_msssim the decode's
+                r.setdefault(name, stats[name][len(res)])                    # own: the same bits)
         res.append(r)
     return res
 
@@ -1512,11 +1618,17 @@ def _refine_arguments(parser, goes_with: str) -> None:
     parser.add_argument("--refine-lr", type=float, default=None, metavar="R",
                         help="Adam learning rate of the refinement in units of the quantiser "
                              f"step (default {DEFAULT_REFINE_LR})")
+    parser.add_argument("--refine-distortion", choices=REFINE_DISTORTIONS, default="mse",
+                        help="the distortion of the refinement objective: mse (lambda * mse + bpp) "
+                             "or ms-ssim (lambda * (1 - MS-SSIM) + bpp; both sides of the image at "
+                             f"least {kernels.MSSSIM_MIN_SIDE})")
 
 
 def _refine_of(args) -> dict:
-    return {"refine": args.refine, "refine_lambda": args.refine_lambda,
-            "refine_lr": args.refine_lr}
+    lam = args.refine_lambda
+    if lam is not None and args.refine_distortion == "ms-ssim":
+        lam = msssim_lambda(lam)
+    return {"refine": args.refine, "refine_lambda": lam, "refine_lr": args.refine_lr}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -1579,6 +1691,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     tag["rdo"] = args.rdo
                 if args.refine:
                     tag["refine"] = args.refine
+                    if args.refine_distortion != "mse":
+                        tag["refine_distortion"] = args.refine_distortion
                 for p, im, r in zip(args.images, imgs, rows):
                     print(json.dumps({"name": p, **tag, "H": im.shape[0], "W": im.shape[1],
                                       "bytes": r["bytes"], "bpp": r["bpp"], "psnr_u8": r["psnr_u8"],

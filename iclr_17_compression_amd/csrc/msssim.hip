@@ -24,6 +24,9 @@
 // iclr17_image_msssim_u8 (the probe of an MS-SSIM target) runs the same level,
 // pooling and finish kernels over a canvas batch of the image codec: images of different true
 // sizes, measured each over its own H×W on the 8-bit decode ("extent sources" below).
+// iclr17_image_msssim_u8_fwd_saved / _bwd (the distortion gradient of latent refinement for
+// MS-SSIM) run the gradient path over the same sources: the gradient on recon,
+// straight through the 8-bit rounding, gated at the clamp, zero on the canvas padding.
 #include <string.h>
 
 #include "common.h"
@@ -90,12 +93,22 @@ __host__ __device__ inline int pooled(int n) { return (n + 2 * (n % 2) - 2) / 2 
 // barrier, and an image's partials are indexed by its own tile grid in (plane, tile row, tile
 // column) order from the first slot of the image, so that they are the partials, in the order,
 // of that image as a Uniform batch of one.
+//
+// The gradient path adds: map_slot(Ho, Wo), the floats between the derivative maps of two planes
+// (a ragged source: the canvas's map size at the level, an image's maps dense at its own size in
+// the front of its slot, as its pyramid planes are), and for the backward at(r, c), where the
+// gradient of pixel (r, c) goes, gate(r, c, d), what is stored for the gradient d there, and
+// kFill: the view's output is a whole canvas plane, whose padding the backward zeroes.
 struct PlaneView {
+  static constexpr bool kFill = false;
   int H, W;
   const float* __restrict__ xp;
   const float* __restrict__ yp;
+  long po;   // the plane's first float in a buffer laid out as the source's
   __device__ __forceinline__ float x(int r, int c, bool&) const { return xp[(long)r * W + c]; }
   __device__ __forceinline__ float y(int r, int c) const { return yp[(long)r * W + c]; }
+  __device__ __forceinline__ long at(int r, int c) const { return po + (long)r * W + c; }
+  __device__ __forceinline__ float gate(int, int, float d) const { return d; }
 };
 
 struct Uniform {
@@ -104,9 +117,11 @@ struct Uniform {
   const float* __restrict__ Y;
   int H, W;
   __device__ __forceinline__ PlaneView view(int plane) const {
-    return PlaneView{H, W, X + (long)plane * H * W, Y + (long)plane * H * W};
+    const long po = (long)plane * H * W;
+    return PlaneView{H, W, X + po, Y + po, po};
   }
   __device__ __forceinline__ void report(bool) const {}
+  __device__ __forceinline__ long map_slot(int Ho, int Wo) const { return (long)Ho * Wo; }
 };
 
 // int64 descriptor row per image (imageio.hip): byte offset in the packed uint8 buffer, H, W, 0
@@ -135,9 +150,11 @@ __device__ __forceinline__ Extent image_extent(const long* __restrict__ desc, in
 constexpr float kInv255 = 1.0f / 255.0f;
 
 struct U8View {
+  static constexpr bool kFill = true;
   int H, W, Wc;
   const float* __restrict__ rp;            // recon plane [Hc][Wc]
   const unsigned char* __restrict__ yp;    // the image's HWC bytes, from this channel's first
+  long po;                                 // the plane's first float in a [B][3][Hc][Wc] buffer
   __device__ __forceinline__ float x(int r, int c, bool& bad) const {
     const float v = rp[(long)r * Wc + c];
     bad |= (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
@@ -145,6 +162,13 @@ struct U8View {
   }
   __device__ __forceinline__ float y(int r, int c) const {
     return (float)yp[((long)r * W + c) * 3] * kInv255;
+  }
+  __device__ __forceinline__ long at(int r, int c) const { return po + (long)r * Wc + c; }
+  // straight through the rounding, gated at the clamp: a descent step along −d would only push a
+  // clamped value further out
+  __device__ __forceinline__ float gate(int r, int c, float d) const {
+    const float v = rp[(long)r * Wc + c];
+    return ((v < 0.0f && d > 0.0f) || (v > 1.0f && d < 0.0f)) ? 0.0f : d;
   }
 };
 
@@ -155,15 +179,17 @@ struct ImageU8 {
   const unsigned char* __restrict__ ref;
   int Hc, Wc;
   int* __restrict__ status;
+  long mslot = 0;   // the gradient path's: (Hc − 10)·(Wc − 10)
   __device__ __forceinline__ U8View view(int plane) const {
     const int b = plane / 3, c = plane - 3 * b;
     const Extent e = image_extent(desc, b, Hc, Wc, 0);
-    return U8View{e.H, e.W, Wc, recon + (long)plane * Hc * Wc,
-                  ref + desc[(long)b * kDescN + kDescOff] + c};
+    const long po = (long)plane * Hc * Wc;
+    return U8View{e.H, e.W, Wc, recon + po, ref + desc[(long)b * kDescN + kDescOff] + c, po};
   }
   __device__ __forceinline__ void report(bool bad) const {
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(status, 1);
   }
+  __device__ __forceinline__ long map_slot(int, int) const { return mslot; }
 };
 
 struct ImagePlanes {
@@ -173,11 +199,14 @@ struct ImagePlanes {
   long slot;
   const long* __restrict__ desc;
   int Hc, Wc, level;
+  long mslot = 0;   // the gradient path's: the canvas's map size at the level
   __device__ __forceinline__ PlaneView view(int plane) const {
     const Extent e = image_extent(desc, plane / 3, Hc, Wc, level);
-    return PlaneView{e.H, e.W, X + (long)plane * slot, Y + (long)plane * slot};
+    const long po = (long)plane * slot;
+    return PlaneView{e.H, e.W, X + po, Y + po, po};
   }
   __device__ __forceinline__ void report(bool) const {}
+  __device__ __forceinline__ long map_slot(int, int) const { return mslot; }
 };
 
 // The finish of a canvas batch: `canvas` is the plan of the canvas (where an image's partials
@@ -205,7 +234,7 @@ struct ImageFinish {
 };
 
 // SAVE (the gradient path, see "Backward" below): bit 0 also writes the per-pixel derivatives of
-// the cs map, bit 1 those of the ssim map, to dcs / dss as planes [map][plane][Ho][Wo] with
+// the cs map, bit 1 those of the ssim map, to dcs / dss as planes [map][plane][map_slot] with
 // map 0 = ∂/∂mx, 1 = ∂/∂exx (= ∂/∂eyy), 2 = ∂/∂exy and, with want_dy, 3 = ∂/∂my. SAVE = 0 is the
 // evaluation kernel; the partial sums and their arithmetic are the same in every variant.
 template <int SAVE, class Ext>
@@ -213,7 +242,6 @@ __global__ void __launch_bounds__(256, 2) ssim_level_kernel(const Ext ext, float
                                                             double* __restrict__ partial,
                                                             float* __restrict__ dcs,
                                                             float* __restrict__ dss, int want_dy) {
-  static_assert(SAVE == 0 || !Ext::kRagged, "the derivative maps are laid out for uniform planes");
   __shared__ __attribute__((aligned(16))) float sx[IH * IWP], sy[IH * IWP];
   __shared__ __attribute__((aligned(16))) float h[5][IH][TOW];
   __shared__ double red[2][4];
@@ -320,8 +348,9 @@ __global__ void __launch_bounds__(256, 2) ssim_level_kernel(const Ext ext, float
         const float c_exy = 2.0f / D, c_exx = -cs / D;
         const float c_mx = (2.0f * cs * mx - 2.0f * my) / D;
         const float c_my = (2.0f * cs * my - 2.0f * mx) / D;
-        const long ms = (long)gridDim.z * Ho * Wo;   // one map of every plane
-        const long at = ((long)plane * Ho + (r0 + rs + j)) * Wo + (c0 + lane);
+        const long slot = ext.map_slot(Ho, Wo);
+        const long ms = (long)gridDim.z * slot;   // one map of every plane
+        const long at = (long)plane * slot + (long)(r0 + rs + j) * Wo + (c0 + lane);
         if constexpr ((SAVE & 1) != 0) {
           dcs[at] = c_mx;
           dcs[ms + at] = c_exx;
@@ -464,8 +493,10 @@ __global__ void __launch_bounds__(256) ssim_finish_kernel(const double* __restri
 // coef[l][b] = g[b] · ∂M/∂mean_l / (3·Ho_l·Wo_l) for M = Π_{l<4} (C_l^{w_l} · S_4^{w_4}), chained
 // as torch differentiates prod (M / t_l), mul and pow (w·v^{w−1}), in double from the fp32 means
 // the forward used. Nothing is clamped: a non-positive mean gives NaN, as in the reference.
+// Plan: the finish kernel's, for its mean_over (an image of a canvas batch: its own counts).
+template <class Plan>
 __global__ void msssim_coef_kernel(const double* __restrict__ means /* [L][B][2] */,
-                                   const float* __restrict__ g, const FinishPlan pl, int B,
+                                   const float* __restrict__ g, const Plan pl, int B,
                                    float* __restrict__ coef /* [L][B] */) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -483,10 +514,11 @@ __global__ void msssim_coef_kernel(const double* __restrict__ means /* [L][B][2]
   for (int l = 0; l < LEVELS - 1; ++l) {
     const double gt = gb * (M / t[l]);
     const double cs = (double)(float)means[((long)l * B + b) * 2 + 1], w = (double)c_msssim_w[l];
-    coef[(long)l * B + b] = (float)(gt * sp * (w * pow(cs, w - 1.0)) / pl.count[l]);
+    coef[(long)l * B + b] = (float)(gt * sp * (w * pow(cs, w - 1.0)) / pl.mean_over(l, b));
     dsp += gt * a[l];
   }
-  coef[(long)(LEVELS - 1) * B + b] = (float)(dsp * (w4 * pow(s, w4 - 1.0)) / pl.count[LEVELS - 1]);
+  coef[(long)(LEVELS - 1) * B + b] =
+      (float)(dsp * (w4 * pow(s, w4 - 1.0)) / pl.mean_over(LEVELS - 1, b));
 }
 
 // Single-scale: coef[0][b] = g_ssim[b] / count, coef[1][b] = g_cs[b] / count (a null g: unused).
@@ -506,32 +538,59 @@ __global__ void ssim_coef_kernel(const float* __restrict__ g_ssim, const float* 
 // average pooling's backward from the level below,
 //   0.25 · d_{l+1}[(iy + H%2)/2][(ix + W%2)/2]   (every pixel lies in exactly one pooling window).
 // grid (⌈W/64⌉, ⌈H/16⌉, planes). dX / dY null: not wanted.
+//
+// One body over the extent source, as the forward: X and Y come from the plane's view (at level 0
+// of a canvas batch they are recomputed from recon and the original's bytes), the maps of plane p
+// start at p·map_slot, and the level below is the plane's own pooled size in slots of `pool_slot`
+// floats. A ragged source is launched on the canvas's grid: a workgroup beyond the image's own
+// H×W returns, after zeroing its tile where the output is the canvas itself (kFill), as does a
+// thread beyond the image inside a workgroup that covers its edge.
+template <class Ext>
 __global__ void __launch_bounds__(256, 2) ssim_level_bwd_kernel(
-    const float* __restrict__ X, const float* __restrict__ Y, int H, int W,
-    const float* __restrict__ DA, const float* __restrict__ coefA, const float* __restrict__ DB,
-    const float* __restrict__ coefB, const float* __restrict__ poolX,
-    const float* __restrict__ poolY, int Hn, int Wn, float* __restrict__ dX,
-    float* __restrict__ dY) {
+    const Ext ext, const float* __restrict__ DA, const float* __restrict__ coefA,
+    const float* __restrict__ DB, const float* __restrict__ coefB,
+    const float* __restrict__ poolX, const float* __restrict__ poolY, long pool_slot,
+    float* __restrict__ dX, float* __restrict__ dY) {
   __shared__ __attribute__((aligned(16))) float sd[IH * IWP];
   __shared__ __attribute__((aligned(16))) float h[IH][TOW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int Ho = H - (WIN - 1), Wo = W - (WIN - 1);
   const int plane = blockIdx.z, img = plane / 3;
+  const auto pv = ext.view(plane);
+  constexpr bool kFill = decltype(pv)::kFill;
+  const int H = pv.H, W = pv.W;
+  const int Ho = H - (WIN - 1), Wo = W - (WIN - 1);
   const int r0 = blockIdx.y * TOH, c0 = blockIdx.x * TOW;
-  const long ms = (long)gridDim.z * Ho * Wo;
+  const int rs = wave * RS;
+  if constexpr (Ext::kRagged) {
+    if (r0 >= H || c0 >= W) {   // uniform over the workgroup
+      if constexpr (kFill) {
+        const int col = c0 + lane;
+#pragma unroll
+        for (int j = 0; j < RS; ++j) {
+          const int row = r0 + rs + j;
+          if (row < ext.Hc && col < ext.Wc) {
+            if (dX) dX[pv.at(row, col)] = 0.f;
+            if (dY) dY[pv.at(row, col)] = 0.f;
+          }
+        }
+      }
+      return;
+    }
+  }
+  const long slot = ext.map_slot(Ho, Wo);
+  const long ms = (long)gridDim.z * slot;
   const float ca = coefA[img], cb = DB ? coefB[img] : 0.f;
   float g[WIN];
 #pragma unroll
   for (int k = 0; k < WIN; ++k) g[k] = c_gauss[k];
-  const int rs = wave * RS;
   float m[4][RS];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
 #pragma unroll
     for (int j = 0; j < RS; ++j) m[q][j] = 0.f;
     if ((q == 0 && !dX) || (q == 3 && !dY)) continue;   // uniform over the grid
-    const float* da = DA + q * ms + (long)plane * Ho * Wo;
-    const float* db = DB ? DB + q * ms + (long)plane * Ho * Wo : nullptr;
+    const float* da = DA + q * ms + (long)plane * slot;
+    const float* db = DB ? DB + q * ms + (long)plane * slot : nullptr;
     // (sd is free: the barrier before the previous map's H pass followed its W pass)
     for (int i = tid; i < IH * IW; i += 256) {
       const int r = i / IW, c = i - r * IW;
@@ -576,24 +635,31 @@ __global__ void __launch_bounds__(256, 2) ssim_level_bwd_kernel(
     }
   }
   const int col = c0 + lane;
-  if (col >= W) return;
   const int ph = H % 2, pw = W % 2;
+  const int Wn = pooled(W);
 #pragma unroll
   for (int j = 0; j < RS; ++j) {
     const int row = r0 + rs + j;
-    if (row >= H) break;
-    const long at = ((long)plane * H + row) * W + col;
-    const long pat = ((long)plane * Hn + (row + ph) / 2) * Wn + (col + pw) / 2;
-    const float x = X[at], y = Y[at];
-    if (dX) {
-      float d = (m[0][j] + 2.0f * x * m[1][j]) + y * m[2][j];
-      if (poolX) d += 0.25f * poolX[pat];
-      dX[at] = d;
-    }
-    if (dY) {
-      float d = (m[3][j] + 2.0f * y * m[1][j]) + x * m[2][j];
-      if (poolY) d += 0.25f * poolY[pat];
-      dY[at] = d;
+    if (row < H && col < W) {
+      const long at = pv.at(row, col);
+      const long pat = (long)plane * pool_slot + (long)((row + ph) / 2) * Wn + (col + pw) / 2;
+      bool bad = false;   // the forward reported it
+      const float x = pv.x(row, col, bad), y = pv.y(row, col);
+      if (dX) {
+        float d = (m[0][j] + 2.0f * x * m[1][j]) + y * m[2][j];
+        if (poolX) d += 0.25f * poolX[pat];
+        dX[at] = pv.gate(row, col, d);
+      }
+      if (dY) {
+        float d = (m[3][j] + 2.0f * y * m[1][j]) + x * m[2][j];
+        if (poolY) d += 0.25f * poolY[pat];
+        dY[at] = d;
+      }
+    } else if constexpr (kFill) {
+      if (row < ext.Hc && col < ext.Wc) {
+        if (dX) dX[pv.at(row, col)] = 0.f;
+        if (dY) dY[pv.at(row, col)] = 0.f;
+      }
     }
   }
 }
@@ -651,6 +717,71 @@ int grad_plan(int B, int H, int W, int want_dy, int multiscale, GradPlan* gp) {
 
 char* aligned_base(void* workspace) {
   return (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+}
+
+// The forward of a canvas batch, for iclr17_image_msssim_u8 and its saving twin: the same
+// launches on the same partials in the same order. The pyramid, the partials and the means are
+// laid out for B images of the canvas's size (lv); an image uses the front of each of its slots.
+// maps (null: the evaluation kernels): the level's derivative maps go to maps + map_off[l].
+int image_msssim_levels(const char* what, const float* recon, const long* d, int B, int Hc, int Wc,
+                        const unsigned char* ref, const Level* lv, double* partial, double* means,
+                        float* pyrbuf, float* maps, const long* map_off, float* out,
+                        int32_t* status, hipStream_t st) {
+  const hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+  if (e != hipSuccess) {
+    set_error(ICLR17_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
+    return ICLR17_ELAUNCH;
+  }
+  const float data_range = 1.0f;
+  const float c1 = (0.01f * data_range) * (0.01f * data_range);
+  const float c2 = (0.03f * data_range) * (0.03f * data_range);
+  double* pl = partial;
+  ImageFinish fin{{}, d, Hc, Wc};
+  for (int l = 0; l < LEVELS; ++l) {
+    const int Hl = lv[l].H, Wl = lv[l].W;   // of the canvas: the launch grids and the slots
+    const int Ho = Hl - WIN + 1, Wo = Wl - WIN + 1;
+    const long slot = (long)Hl * Wl, mslot = (long)Ho * Wo;
+    float* Xl = l ? pyrbuf + lv[l].off : nullptr;
+    float* Yl = l ? Xl + (long)B * 3 * slot : nullptr;
+    const ImageU8 level0{recon, d, ref, Hc, Wc, (int*)status, mslot};
+    const ImagePlanes here{Xl, Yl, slot, d, Hc, Wc, l, mslot};
+    const dim3 pool_grid((Wl + 255) / 256, Hl, 2 * B * 3);
+    if (l == 1)
+      hipLaunchKernelGGL(avgpool2_kernel<ImageU8>, pool_grid, dim3(256), 0, st, level0, B * 3, slot,
+                         Xl, Yl);
+    if (l > 1) {
+      const long up = (long)lv[l - 1].H * lv[l - 1].W;
+      const float* Xu = pyrbuf + lv[l - 1].off;
+      hipLaunchKernelGGL(avgpool2_kernel<ImagePlanes>, pool_grid, dim3(256), 0, st,
+                         ImagePlanes{Xu, Xu + (long)B * 3 * up, up, d, Hc, Wc, l - 1}, B * 3, slot,
+                         Xl, Yl);
+    }
+    const dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
+    float* D = maps ? maps + map_off[l] : nullptr;
+    float* none = nullptr;
+    if (!maps && l == 0)
+      hipLaunchKernelGGL((ssim_level_kernel<0, ImageU8>), grid, dim3(256), 0, st, level0, c1, c2, pl,
+                         none, none, 0);
+    else if (!maps)
+      hipLaunchKernelGGL((ssim_level_kernel<0, ImagePlanes>), grid, dim3(256), 0, st, here, c1, c2,
+                         pl, none, none, 0);
+    else if (l == 0)
+      hipLaunchKernelGGL((ssim_level_kernel<1, ImageU8>), grid, dim3(256), 0, st, level0, c1, c2, pl,
+                         D, none, 0);
+    else if (l < LEVELS - 1)
+      hipLaunchKernelGGL((ssim_level_kernel<1, ImagePlanes>), grid, dim3(256), 0, st, here, c1, c2,
+                         pl, D, none, 0);
+    else
+      hipLaunchKernelGGL((ssim_level_kernel<2, ImagePlanes>), grid, dim3(256), 0, st, here, c1, c2,
+                         pl, none, D, 0);
+    fin.canvas.poff[l] = pl - partial;
+    fin.canvas.tiles[l] = lv[l].tiles;
+    fin.canvas.count[l] = 3.0 * Ho * Wo;
+    pl += 2L * B * 3 * lv[l].tiles;
+  }
+  hipLaunchKernelGGL(msssim_finish_kernel<ImageFinish>, dim3(B), dim3(256), 0, st, partial, fin, B,
+                     means, out);
+  return check_launch(what);
 }
 
 }  // namespace
@@ -734,56 +865,11 @@ int iclr17_image_msssim_u8(const float* recon, const int64_t* desc, int B, int H
                  Wc);
   ICLR17_REQUIRE(workspace_bytes >= iclr17_image_msssim_workspace_size(B, Hc, Wc), ICLR17_EINVAL,
                  "image_msssim: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
-  if (e != hipSuccess) {
-    set_error(ICLR17_ELAUNCH, "image_msssim: %s", hipGetErrorString(e));
-    return ICLR17_ELAUNCH;
-  }
   char* ws = aligned_base(workspace);
-  float* pyrbuf = (float*)ws;
   double* partial = (double*)(ws + pyr * 4);
-  double* means = partial + part;
-  const float data_range = 1.0f;
-  const float c1 = (0.01f * data_range) * (0.01f * data_range);
-  const float c2 = (0.03f * data_range) * (0.03f * data_range);
-  const long* d = (const long*)desc;
-  const ImageU8 level0{recon, d, (const unsigned char*)ref, Hc, Wc, (int*)status};
-  double* pl = partial;
-  ImageFinish fin{{}, d, Hc, Wc};
-  for (int l = 0; l < LEVELS; ++l) {
-    const int Hl = lv[l].H, Wl = lv[l].W;   // of the canvas: the launch grids and the slots
-    const long slot = (long)Hl * Wl;
-    float* Xl = l ? pyrbuf + lv[l].off : nullptr;
-    float* Yl = l ? Xl + (long)B * 3 * slot : nullptr;
-    const ImagePlanes here{Xl, Yl, slot, d, Hc, Wc, l};
-    const dim3 pool_grid((Wl + 255) / 256, Hl, 2 * B * 3);
-    if (l == 1)
-      hipLaunchKernelGGL(avgpool2_kernel<ImageU8>, pool_grid, dim3(256), 0, st, level0, B * 3, slot,
-                         Xl, Yl);
-    if (l > 1) {
-      const long up = (long)lv[l - 1].H * lv[l - 1].W;
-      const float* Xu = pyrbuf + lv[l - 1].off;
-      hipLaunchKernelGGL(avgpool2_kernel<ImagePlanes>, pool_grid, dim3(256), 0, st,
-                         ImagePlanes{Xu, Xu + (long)B * 3 * up, up, d, Hc, Wc, l - 1}, B * 3, slot,
-                         Xl, Yl);
-    }
-    const int Ho = Hl - WIN + 1, Wo = Wl - WIN + 1;
-    const dim3 grid((Wo + TOW - 1) / TOW, (Ho + TOH - 1) / TOH, B * 3);
-    if (l == 0)
-      hipLaunchKernelGGL((ssim_level_kernel<0, ImageU8>), grid, dim3(256), 0, st, level0, c1, c2, pl,
-                         (float*)nullptr, (float*)nullptr, 0);
-    else
-      hipLaunchKernelGGL((ssim_level_kernel<0, ImagePlanes>), grid, dim3(256), 0, st, here, c1, c2,
-                         pl, (float*)nullptr, (float*)nullptr, 0);
-    fin.canvas.poff[l] = pl - partial;
-    fin.canvas.tiles[l] = lv[l].tiles;
-    fin.canvas.count[l] = 3.0 * Ho * Wo;
-    pl += 2L * B * 3 * lv[l].tiles;
-  }
-  hipLaunchKernelGGL(msssim_finish_kernel<ImageFinish>, dim3(B), dim3(256), 0, st, partial, fin, B,
-                     means, out);
-  return check_launch("image_msssim");
+  return image_msssim_levels("image_msssim", recon, (const long*)desc, B, Hc, Wc,
+                             (const unsigned char*)ref, lv, partial, partial + part, (float*)ws,
+                             nullptr, nullptr, out, status, (hipStream_t)stream);
 }
 
 size_t iclr17_ssim_workspace_size(int B, int H, int W) {
@@ -899,8 +985,8 @@ int iclr17_ms_ssim_bwd(const float* x, const float* y, int B, int H, int W, int 
   FinishPlan fp;
   for (int l = 0; l < LEVELS; ++l)
     fp.count[l] = 3.0 * (gp.lv[l].H - WIN + 1) * (gp.lv[l].W - WIN + 1);
-  hipLaunchKernelGGL(msssim_coef_kernel, dim3((B + 63) / 64), dim3(64), 0, st, means, g, fp, B,
-                     coef);
+  hipLaunchKernelGGL(msssim_coef_kernel<FinishPlan>, dim3((B + 63) / 64), dim3(64), 0, st, means,
+                     g, fp, B, coef);
   for (int l = LEVELS - 1; l >= 0; --l) {
     const int Hl = gp.lv[l].H, Wl = gp.lv[l].W;
     const long n = (long)B * 3 * Hl * Wl;
@@ -909,19 +995,99 @@ int iclr17_ms_ssim_bwd(const float* x, const float* y, int B, int H, int W, int 
     float* oX = dx ? (l ? gpyr + gp.lv[l].off : dx) : nullptr;
     float* oY = dy ? (l ? gpyr + gp.lv[l].off + n : dy) : nullptr;
     const float *pX = nullptr, *pY = nullptr;
-    int Hn = 0, Wn = 0;
+    long below = 0;
     if (l < LEVELS - 1) {
-      Hn = gp.lv[l + 1].H;
-      Wn = gp.lv[l + 1].W;
+      below = (long)gp.lv[l + 1].H * gp.lv[l + 1].W;
       pX = dx ? gpyr + gp.lv[l + 1].off : nullptr;
-      pY = dy ? gpyr + gp.lv[l + 1].off + (long)B * 3 * Hn * Wn : nullptr;
+      pY = dy ? gpyr + gp.lv[l + 1].off + (long)B * 3 * below : nullptr;
     }
     dim3 grid((Wl + TOW - 1) / TOW, (Hl + TOH - 1) / TOH, B * 3);
-    hipLaunchKernelGGL(ssim_level_bwd_kernel, grid, dim3(256), 0, st, X, Y, Hl, Wl,
-                       maps + gp.maps[l], coef + (long)l * B, (const float*)nullptr,
-                       (const float*)nullptr, pX, pY, Hn, Wn, oX, oY);
+    hipLaunchKernelGGL(ssim_level_bwd_kernel<Uniform>, grid, dim3(256), 0, st,
+                       Uniform{X, Y, Hl, Wl}, maps + gp.maps[l], coef + (long)l * B,
+                       (const float*)nullptr, (const float*)nullptr, pX, pY, below, oX, oY);
   }
   return check_launch("ms_ssim_bwd");
+}
+
+// ------------------------------------------------- gradient path of a canvas batch
+// The workspace is grad_plan's for B images of the canvas's size without dY maps; an image uses
+// the front of each of its slots (partials, pyramid planes, gradient planes, maps).
+size_t iclr17_image_msssim_grad_workspace_size(int B, int Hc, int Wc) {
+  GradPlan gp;
+  return grad_plan(B, Hc, Wc, 0, 1, &gp) == 0 ? gp.bytes : 0;
+}
+
+int iclr17_image_msssim_u8_fwd_saved(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
+                                     const uint8_t* ref, void* workspace, size_t workspace_bytes,
+                                     float* out, int32_t* status, void* stream) {
+  ICLR17_REQUIRE(recon && desc && ref && workspace && out && status, ICLR17_EINVAL,
+                 "image_msssim_fwd_saved: null pointer");
+  if (int rc = check_image(B, Hc, Wc, 128)) return rc;
+  ICLR17_REQUIRE(B <= 10000 && Hc <= 65535 * 2, ICLR17_EUNSUPPORTED,
+                 "image_msssim_fwd_saved: B=%d or canvas height %d beyond the launch grid", B, Hc);
+  GradPlan gp;
+  ICLR17_REQUIRE(grad_plan(B, Hc, Wc, 0, 1, &gp) == 0, ICLR17_EINVAL,
+                 "image_msssim_fwd_saved: the canvas %dx%d is too small for 5 levels of an 11-tap "
+                 "window", Hc, Wc);
+  ICLR17_REQUIRE(workspace_bytes >= gp.bytes, ICLR17_EINVAL,
+                 "image_msssim_fwd_saved: workspace too small");
+  char* ws = aligned_base(workspace);
+  return image_msssim_levels("image_msssim_fwd_saved", recon, (const long*)desc, B, Hc, Wc,
+                             (const unsigned char*)ref, gp.lv, (double*)ws,
+                             (double*)(ws + gp.off_means), (float*)(ws + gp.off_pyr),
+                             (float*)(ws + gp.off_maps), gp.maps, out, status,
+                             (hipStream_t)stream);
+}
+
+int iclr17_image_msssim_u8_bwd(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
+                               const uint8_t* ref, void* workspace, size_t workspace_bytes,
+                               const float* g, float* d_recon, void* stream) {
+  ICLR17_REQUIRE(recon && desc && ref && workspace && g && d_recon, ICLR17_EINVAL,
+                 "image_msssim_bwd: null pointer");
+  if (int rc = check_image(B, Hc, Wc, 128)) return rc;
+  ICLR17_REQUIRE(B <= 10000 && Hc <= 65535 * 2, ICLR17_EUNSUPPORTED,
+                 "image_msssim_bwd: B=%d or canvas height %d beyond the launch grid", B, Hc);
+  GradPlan gp;
+  ICLR17_REQUIRE(grad_plan(B, Hc, Wc, 0, 1, &gp) == 0, ICLR17_EINVAL,
+                 "image_msssim_bwd: the canvas %dx%d is too small for 5 levels of an 11-tap window",
+                 Hc, Wc);
+  ICLR17_REQUIRE(workspace_bytes >= gp.bytes, ICLR17_EINVAL, "image_msssim_bwd: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = aligned_base(workspace);
+  const double* means = (const double*)(ws + gp.off_means);
+  const float* pyrbuf = (const float*)(ws + gp.off_pyr);
+  float* gpyr = (float*)(ws + gp.off_gpyr);
+  const float* maps = (const float*)(ws + gp.off_maps);
+  float* coef = (float*)(ws + gp.off_coef);
+  const long* d = (const long*)desc;
+  hipLaunchKernelGGL(msssim_coef_kernel<ImageFinish>, dim3((B + 63) / 64), dim3(64), 0, st, means,
+                     g, ImageFinish{{}, d, Hc, Wc}, B, coef);
+  for (int l = LEVELS - 1; l >= 0; --l) {
+    const int Hl = gp.lv[l].H, Wl = gp.lv[l].W;   // of the canvas: the launch grid and the slots
+    const long slot = (long)Hl * Wl, mslot = (long)(Hl - WIN + 1) * (Wl - WIN + 1);
+    const float* pX = nullptr;
+    long below = 0;
+    if (l < LEVELS - 1) {
+      below = (long)gp.lv[l + 1].H * gp.lv[l + 1].W;
+      pX = gpyr + gp.lv[l + 1].off;
+    }
+    const float* D = maps + gp.maps[l];
+    const float* c = coef + (long)l * B;
+    const dim3 grid((Wl + TOW - 1) / TOW, (Hl + TOH - 1) / TOH, B * 3);
+    if (l == 0) {
+      hipLaunchKernelGGL(ssim_level_bwd_kernel<ImageU8>, grid, dim3(256), 0, st,
+                         ImageU8{recon, d, (const unsigned char*)ref, Hc, Wc, nullptr, mslot}, D, c,
+                         (const float*)nullptr, (const float*)nullptr, pX, (const float*)nullptr,
+                         below, d_recon, (float*)nullptr);
+    } else {
+      const float* Xl = pyrbuf + gp.lv[l].off;
+      hipLaunchKernelGGL(ssim_level_bwd_kernel<ImagePlanes>, grid, dim3(256), 0, st,
+                         ImagePlanes{Xl, Xl + (long)B * 3 * slot, slot, d, Hc, Wc, l, mslot}, D, c,
+                         (const float*)nullptr, (const float*)nullptr, pX, (const float*)nullptr,
+                         below, gpyr + gp.lv[l].off, (float*)nullptr);
+    }
+  }
+  return check_launch("image_msssim_bwd");
 }
 
 int iclr17_ssim_fwd_saved(const float* x, const float* y, int B, int H, int W, float data_range,
@@ -977,9 +1143,9 @@ int iclr17_ssim_bwd(const float* x, const float* y, int B, int H, int W, int sav
   const float* cA = g_ssim ? coef : coef + B;
   const float* DB = g_ssim && g_cs ? maps + set : nullptr;
   dim3 grid((W + TOW - 1) / TOW, (H + TOH - 1) / TOH, B * 3);
-  hipLaunchKernelGGL(ssim_level_bwd_kernel, grid, dim3(256), 0, st, x, y, H, W, DA, cA, DB,
-                     (const float*)(coef + B), (const float*)nullptr, (const float*)nullptr, 0, 0,
-                     dx, dy);
+  hipLaunchKernelGGL(ssim_level_bwd_kernel<Uniform>, grid, dim3(256), 0, st, Uniform{x, y, H, W},
+                     DA, cA, DB, (const float*)(coef + B), (const float*)nullptr,
+                     (const float*)nullptr, 0L, dx, dy);
   return check_launch("ssim_bwd");
 }
 

@@ -10,6 +10,8 @@
 //   refine_keep         J_b = bits_b + (λ_b/3)·SSE_b/255², and where J_b < best_J_b the iterate
 //                       becomes the best: a one-workgroup launch decides per image, a second one
 //                       copies the latents of the images that improved
+//   refine_keep_msssim  the same decision for J_b = bits_b + λ_b·H_b·W_b·(1 − MS-SSIM_b)
+//                       (the gradient of that distortion is msssim.hip's)
 //
 // refine_step stands in ladder.h's sweep frame (one workgroup per image and 4096-element chunk,
 // the step pack of Δ_b in LDS, rate_bits' thread → element map and tail of one sum), so its bit
@@ -94,7 +96,54 @@ __global__ void __launch_bounds__(kThreads) refine_step_kernel(
   chunk_sum_store(s, k, chunks, partial);
 }
 
-// One workgroup, a thread per image: every block of the copy then reads one decision.
+// The distortion term of J and what is recorded of it, per objective:
+//   (λ_b/3)·SSE_b/255²            the 8-bit squared error (int64), codec.refine_objective
+//   (λ_b·area_b)·(1 − MS-SSIM_b)  the fp32 MS-SSIM of the 8-bit decode over area_b = H_b·W_b
+//                                 pixels, codec.refine_objective_msssim
+struct SseTerm {
+  const long* __restrict__ sse;
+  long* __restrict__ best;
+  __device__ __forceinline__ double of(int b, double lam) const {
+    return ((lam / 3.0) * (double)sse[b]) / 65025.0;
+  }
+  __device__ __forceinline__ void record(int b) const { best[b] = sse[b]; }
+};
+
+struct MsssimTerm {
+  const float* __restrict__ ms;
+  const double* __restrict__ area;
+  float* __restrict__ best;
+  __device__ __forceinline__ double of(int b, double lam) const {
+    return (lam * area[b]) * (1.0 - (double)ms[b]);
+  }
+  __device__ __forceinline__ void record(int b) const { best[b] = ms[b]; }
+};
+
+// The decision, one body for both objectives. One workgroup, a thread per image: every block of
+// the copy then reads one decision.
+template <class Term>
+__device__ __forceinline__ void refine_decide_body(const double* __restrict__ bits, const Term term,
+                                                   const double* __restrict__ lam,
+                                                   const int* __restrict__ qstatus,
+                                                   const int* __restrict__ rstatus, int B, int iter,
+                                                   double* __restrict__ best_J,
+                                                   int* __restrict__ best_iter,
+                                                   double* __restrict__ best_bits,
+                                                   int* __restrict__ flag) {
+  const bool recon_bad = rstatus != nullptr && *rstatus != 0;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const double J = bits[b] + term.of(b, lam[b]);
+    const bool better = !recon_bad && qstatus[b] == 0 && J < best_J[b];   // NaN: not better
+    flag[b] = better ? 1 : 0;
+    if (better) {
+      best_J[b] = J;
+      best_iter[b] = iter;
+      best_bits[b] = bits[b];
+      term.record(b);
+    }
+  }
+}
+
 __global__ void refine_decide_kernel(const double* __restrict__ bits, const long* __restrict__ sse,
                                      const double* __restrict__ lam,
                                      const int* __restrict__ qstatus,
@@ -102,18 +151,18 @@ __global__ void refine_decide_kernel(const double* __restrict__ bits, const long
                                      double* __restrict__ best_J, int* __restrict__ best_iter,
                                      double* __restrict__ best_bits, long* __restrict__ best_sse,
                                      int* __restrict__ flag) {
-  const bool recon_bad = rstatus != nullptr && *rstatus != 0;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    const double J = bits[b] + ((lam[b] / 3.0) * (double)sse[b]) / 65025.0;
-    const bool better = !recon_bad && qstatus[b] == 0 && J < best_J[b];   // NaN: not better
-    flag[b] = better ? 1 : 0;
-    if (better) {
-      best_J[b] = J;
-      best_iter[b] = iter;
-      best_bits[b] = bits[b];
-      best_sse[b] = sse[b];
-    }
-  }
+  refine_decide_body(bits, SseTerm{sse, best_sse}, lam, qstatus, rstatus, B, iter, best_J,
+                     best_iter, best_bits, flag);
+}
+
+__global__ void refine_decide_msssim_kernel(
+    const double* __restrict__ bits, const float* __restrict__ ms, const double* __restrict__ lam,
+    const double* __restrict__ area, const int* __restrict__ qstatus,
+    const int* __restrict__ rstatus, int B, int iter, double* __restrict__ best_J,
+    int* __restrict__ best_iter, double* __restrict__ best_bits, float* __restrict__ best_ms,
+    int* __restrict__ flag) {
+  refine_decide_body(bits, MsssimTerm{ms, area, best_ms}, lam, qstatus, rstatus, B, iter, best_J,
+                     best_iter, best_bits, flag);
 }
 
 // grid (blocks per image, B)
@@ -126,6 +175,14 @@ __global__ void __launch_bounds__(kThreads) refine_copy_kernel(const float* __re
   for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < per_image;
        i += (long)gridDim.x * kThreads)
     best[base + i] = y_hat[base + i];
+}
+
+int copy_kept(const char* what, const float* y_hat, int B, int64_t per_image, const int32_t* flag,
+              float* best, hipStream_t st) {
+  const long blocks = ((long)per_image + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(refine_copy_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks), (unsigned)B),
+                     dim3(kThreads), 0, st, y_hat, (long)per_image, (const int*)flag, best);
+  return check_launch(what);
 }
 
 }  // namespace
@@ -206,10 +263,28 @@ int iclr17_refine_keep(const double* bits, const int64_t* sse, const double* lam
                      (int*)best_iter, best_bits, (long*)best_sse, (int*)flag);
   int rc = check_launch("refine_keep (decide)");
   if (rc) return rc;
-  const long blocks = ((long)per_image + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(refine_copy_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks), (unsigned)B),
-                     dim3(kThreads), 0, st, y_hat, (long)per_image, (const int*)flag, best);
-  return check_launch("refine_keep");
+  return copy_kept("refine_keep", y_hat, B, per_image, flag, best, st);
+}
+
+int iclr17_refine_keep_msssim(const double* bits, const float* ms, const double* lam,
+                              const double* area, const int32_t* qstatus,
+                              const int32_t* recon_status, const float* y_hat, int B,
+                              int64_t per_image, int iter, double* best_J, int32_t* best_iter,
+                              double* best_bits, float* best_ms, float* best, int32_t* flag,
+                              void* stream) {
+  ICLR17_REQUIRE(bits && ms && lam && area && qstatus && y_hat && best_J && best_iter &&
+                     best_bits && best_ms && best && flag,
+                 ICLR17_EINVAL, "refine_keep_msssim: null pointer");
+  ICLR17_REQUIRE(B > 0 && B <= 65535 && per_image > 0 && iter >= 0, ICLR17_EINVAL,
+                 "refine_keep_msssim: bad shape B=%d per_image=%lld iter=%d", B,
+                 (long long)per_image, iter);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(refine_decide_msssim_kernel, dim3(1), dim3(256), 0, st, bits, ms, lam, area,
+                     (const int*)qstatus, (const int*)recon_status, B, iter, best_J,
+                     (int*)best_iter, best_bits, best_ms, (int*)flag);
+  int rc = check_launch("refine_keep_msssim (decide)");
+  if (rc) return rc;
+  return copy_kept("refine_keep_msssim", y_hat, B, per_image, flag, best, st);
 }
 
 }  // extern "C"

@@ -1790,6 +1790,37 @@ def refine_keep(bits: Tensor, sse: Tensor, lam: Tensor, qstatus: Tensor,
          _p(best_sse), _p(best), _p(flag), _stream(y_hat))
 
 
+def refine_keep_msssim(bits: Tensor, ms: Tensor, lam: Tensor, area: Tensor, qstatus: Tensor,
+                       recon_status: Optional[Tensor], y_hat: Tensor, it: int, best_J: Tensor,
+                       best_iter: Tensor, best_bits: Tensor, best_ms: Tensor, best: Tensor,
+                       flag: Tensor) -> None:
+    """``refine_keep`` for the MS-SSIM objective, the same decision: J_b = bits_b +
+    (λ_b·area_b)·(1 − ms_b) in float64 (``ms`` fp32 [B], ``image_msssim_fwd_saved``'s values;
+    ``area`` float64 [B], H_b·W_b); ``best_ms`` (fp32 [B]) takes the iterate's MS-SSIM where
+    ``refine_keep`` records the SSE. ``recon_status``: ``image_msssim_fwd_saved``'s."""
+    _check(y_hat, "latent")
+    B = y_hat.shape[0]
+    dev = y_hat.device
+    want = ((bits, torch.float64), (ms, torch.float32), (lam, torch.float64),
+            (area, torch.float64), (qstatus, torch.int32), (best_J, torch.float64),
+            (best_iter, torch.int32), (best_bits, torch.float64), (best_ms, torch.float32),
+            (flag, torch.int32))
+    for q, dt in want:
+        if q.dtype != dt or q.numel() != B or q.device != dev or not q.is_contiguous():
+            raise Iclr17Error(f"iclr17: refine_keep_msssim: a per-image argument is not {dt} [{B}] "
+                              "on the latent's device")
+    if (best.shape != y_hat.shape or best.dtype != torch.float32 or best.device != dev
+            or not best.is_contiguous() or not y_hat.is_contiguous()):
+        raise Iclr17Error("iclr17: refine_keep_msssim: best must be a contiguous fp32 tensor of the "
+                          "latent's shape")
+    if recon_status is not None and (recon_status.dtype != torch.int32 or recon_status.device != dev):
+        raise Iclr17Error("iclr17: refine_keep_msssim: recon_status must be an int32 tensor on the "
+                          "device")
+    call("iclr17_refine_keep_msssim", _p(bits), _p(ms), _p(lam), _p(area), _p(qstatus),
+         _p(recon_status), _p(y_hat), B, y_hat.numel() // B, int(it), _p(best_J), _p(best_iter),
+         _p(best_bits), _p(best_ms), _p(best), _p(flag), _stream(y_hat))
+
+
 # ---------------------------------------------------------------- image files (§1 f5)
 def _image_desc(what: str, nbytes: int, offsets, shapes, canvas) -> Tensor:
     """The int64 [B][4] descriptors {byte offset, H, W, 0} of uint8 HWC images packed in a buffer
@@ -1987,6 +2018,76 @@ def image_msssim(recon: Tensor, offsets, shapes, ref: Tensor):
             raise Iclr17Error(H3_RANGE_MESSAGE)
         raise Iclr17Error("iclr17: image_msssim: non-finite reconstruction")
     return host[:4 * B].view(torch.float32)
+
+
+def image_msssim_grad_workspace(B: int, Hc: int, Wc: int, device) -> Tensor:
+    """The workspace (uint8) that ``image_msssim_fwd_saved`` fills and ``image_msssim_bwd`` reads,
+    for B images on a canvas Hc×Wc: made once, before a loop."""
+    nbytes = query("iclr17_image_msssim_grad_workspace_size", int(B), int(Hc), int(Wc))
+    if nbytes == 0:
+        raise Iclr17Error(f"iclr17: image_msssim: the canvas {Hc}x{Wc} is too small for 5 levels of "
+                          "an 11-tap window")
+    return torch.empty(nbytes, device=device, dtype=torch.uint8)
+
+
+def _image_msssim_grad_args(what: str, recon: Tensor, ref: Tensor, desc: Tensor, ws: Tensor):
+    _check(recon, "reconstruction", 4)
+    B, C, Hc, Wc = recon.shape
+    if C != 3:
+        raise Iclr17Error(f"iclr17: {what} takes a [B,3,Hc,Wc] reconstruction (got {C} channels)")
+    _check_u8(ref, "reference bytes")
+    ref = _check_u8_gpu(ref, "reference bytes")
+    if (tuple(desc.shape) != (B, 4) or desc.dtype != torch.int64 or desc.device != recon.device
+            or not desc.is_contiguous()):
+        raise Iclr17Error(f"iclr17: {what}: checked descriptors int64 [{B}, 4] on the device (got "
+                          f"{desc.dtype} {tuple(desc.shape)})")
+    if (ws.dtype != torch.uint8 or ws.device != recon.device or not ws.is_contiguous()
+            or not recon.is_contiguous()):
+        raise Iclr17Error(f"iclr17: {what}: a contiguous reconstruction and the workspace of "
+                          "image_msssim_grad_workspace on its device")
+    return B, Hc, Wc, ref
+
+
+def image_msssim_fwd_saved(recon: Tensor, ref: Tensor, desc: Tensor, ws: Tensor, out=None):
+    """``image_msssim_device``'s values and status, bit for bit, → (values fp32 [B], status int32
+    [1]), both on the device, and in ``ws`` (``image_msssim_grad_workspace``) what
+    ``image_msssim_bwd`` reads. ``desc``: the checked descriptors on the device, of images that
+    passed ``check_msssim_shapes`` (the caller's duty, as ``refine_grad_recon``'s). ``out``: an
+    earlier call's pair to write into. Nothing is read back."""
+    B, Hc, Wc, ref = _image_msssim_grad_args("image_msssim_fwd_saved", recon, ref, desc, ws)
+    if out is None:
+        out = (torch.empty(B, device=recon.device, dtype=torch.float32),
+               torch.empty(1, device=recon.device, dtype=torch.int32))
+    values, status = out
+    if (values.dtype != torch.float32 or values.numel() != B or status.dtype != torch.int32
+            or status.numel() != 1 or values.device != recon.device or status.device != recon.device):
+        raise Iclr17Error(f"iclr17: image_msssim_fwd_saved: out is (fp32 [{B}], int32 [1]) on the "
+                          "device")
+    call("iclr17_image_msssim_u8_fwd_saved", _p(recon), _p(desc), B, Hc, Wc, _p(ref), _p(ws),
+         ws.numel(), _p(values), _p(status), _stream(recon))
+    return values, status
+
+
+def image_msssim_bwd(recon: Tensor, ref: Tensor, desc: Tensor, ws: Tensor, g: Tensor,
+                     out: Optional[Tensor] = None) -> Tensor:
+    """The gradient of ``image_msssim_fwd_saved``'s values on ``recon`` (unchanged since, as ``ws``):
+    g fp32 [B] = ∂loss/∂MS-SSIM_b → d_recon fp32 [B,3,Hc,Wc], inside image b's own H_b×W_b
+    g_b·∂MS-SSIM_b/∂X straight through the 8-bit rounding, 0 where recon lies outside [0, 1] and a
+    descent step would push it further out, and exact +0.0 on the canvas padding. ``out``: a
+    tensor of recon's shape to write into."""
+    B, Hc, Wc, ref = _image_msssim_grad_args("image_msssim_bwd", recon, ref, desc, ws)
+    _check(g, "ms_ssim gradient", 1)
+    if g.numel() != B or g.dtype != torch.float32:
+        raise Iclr17Error(f"iclr17: image_msssim_bwd: g is fp32 [{B}]")
+    if out is None:
+        out = torch.empty_like(recon)
+    if out.shape != recon.shape or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != recon.device:
+        raise Iclr17Error("iclr17: image_msssim_bwd: out must be a contiguous fp32 tensor of the "
+                          "reconstruction's shape")
+    call("iclr17_image_msssim_u8_bwd", _p(recon), _p(desc), B, Hc, Wc, _p(ref), _p(ws), ws.numel(),
+         _p(g.contiguous()), _p(out), _stream(recon))
+    return out
 
 
 # ------------------------------------------------------------------------------ modules

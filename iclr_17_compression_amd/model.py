@@ -599,7 +599,13 @@ class ImageCompressor(nn.Module):
         (none given: index 8) and ``tile``; the blobs are ordinary I17Q / I17T ones and any decoder
         reads them. With a budget, a quality target, ``rdo`` or ``step_offsets`` and in the bf16
         mode it raises. ``stats`` receives "refine_kept", "objective", "objective_plain" and
-        "refine_iters" per image."""
+        "refine_iters" per image.
+
+        ``refine_lambda=codec.msssim_lambda(λ)`` (a scalar or one per image; not mixed with plain
+        values) makes the distortion MS-SSIM: J = bits + λ·H·W·(1 − MS-SSIM8),
+        λ in the units of train.py's λ·(1 − MS-SSIM) + bpp. Both sides of every image must then be
+        at least 161, and ``stats`` also receives "refine_distortion" ("ms-ssim"), "ms_ssim" and
+        "ms_ssim_plain", the judged values."""
         from . import codec
         return codec.compress_images(self, images, max_batch, streams_per_image, K, step=step,
                                      max_bytes=max_bytes, bpp=bpp, stats=stats,
@@ -622,7 +628,7 @@ class ImageCompressor(nn.Module):
         host synchronisation inside (codec.refine_loop); then the best iterate and the plain
         ŷ = rint(y/Δ) are judged through the eval chain, and the best is returned only where its
         J = bits + (λ/3)·SSE8/255² is strictly lower. ``stats`` as in ``compress_images``. Not in the
-        bf16 mode."""
+        bf16 mode. With codec.msssim_lambda values the distortion is MS-SSIM, as there."""
         from . import codec
         B = y.shape[0]
         idx = self._step_indices(steps, B)

@@ -485,6 +485,16 @@ int iclr17_refine_keep(const double* bits, const int64_t* sse, const double* lam
                        int B, int64_t per_image, int iter, double* best_J, int32_t* best_iter,
                        double* best_bits, int64_t* best_sse, float* best, int32_t* flag,
                        void* stream);
+/* iclr17_refine_keep for the MS-SSIM objective, the same decision body:
+ * J_b = bits[b] + (lam[b]·area[b])·(1 − (double)ms[b]) in float64, with ms the fp32 [B] values of
+ * iclr17_image_msssim_u8_fwd_saved, area float64 [B] = H_b·W_b and *recon_status that entry's
+ * status; best_ms[b] (fp32) = ms[b] where iclr17_refine_keep records the SSE. */
+int iclr17_refine_keep_msssim(const double* bits, const float* ms, const double* lam,
+                              const double* area, const int32_t* qstatus,
+                              const int32_t* recon_status, const float* y_hat, int B,
+                              int64_t per_image, int iter, double* best_J, int32_t* best_iter,
+                              double* best_bits, float* best_ms, float* best, int32_t* flag,
+                              void* stream);
 
 /* testKodak's MS-SSIM (train.py:178 → models/ms_ssim_torch.py:123-196): per-image
  * ms_ssim(x, y, data_range) of NCHW [B,3,H,W] fp32 images, 11-tap σ=1.5 window, 5 levels (each
@@ -588,6 +598,28 @@ size_t iclr17_image_msssim_workspace_size(int B, int Hc, int Wc);
 int iclr17_image_msssim_u8(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
                            const uint8_t* ref, void* workspace, size_t workspace_bytes, float* out,
                            int32_t* status, void* stream);
+/* The gradient of iclr17_image_msssim_u8 on recon (the distortion term of latent refinement for
+ * MS-SSIM). recon, desc, ref and the size rule as above.
+ * fwd_saved: out and status bit for bit iclr17_image_msssim_u8's (the same tiles, the same
+ * partials in the same order), and in the workspace what the backward reads: the pyramid, the
+ * per-level means and the per-pixel derivative maps (no dY maps), an image's at its own size in
+ * slots of the canvas's level size. The workspace lives from the forward to the backward, recon
+ * unchanged; iclr17_image_msssim_grad_workspace_size(B, Hc, Wc) bytes (0: the canvas is too small).
+ * bwd: g fp32 [B] (the upstream gradient per image) → d_recon fp32 [B][3][Hc][Wc]. Inside image
+ * b's own H_b×W_b, with d = g[b]·∂MS-SSIM_b/∂X taken straight through the 8-bit rounding (X is
+ * recomputed from recon, Y read from ref a byte at a time: no level-0 plane exists in memory) and
+ * v the recon value: 0 where (v < 0 and d > 0) or (v > 1 and d < 0) (a descent step would push a
+ * clamped value further out), else d — bit for bit iclr17_ms_ssim_bwd's dx for that image's two
+ * planes as a batch of one, gated. The canvas padding receives +0.0 whatever recon holds there.
+ * Nothing is scattered and no sum uses atomics: bitwise reproducible, an image's gradient
+ * independent of its batch. */
+size_t iclr17_image_msssim_grad_workspace_size(int B, int Hc, int Wc);
+int iclr17_image_msssim_u8_fwd_saved(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
+                                     const uint8_t* ref, void* workspace, size_t workspace_bytes,
+                                     float* out, int32_t* status, void* stream);
+int iclr17_image_msssim_u8_bwd(const float* recon, const int64_t* desc, int B, int Hc, int Wc,
+                               const uint8_t* ref, void* workspace, size_t workspace_bytes,
+                               const float* g, float* d_recon, void* stream);
 
 /* train.py:106-112: element-wise gradient clamp to ±grad_clip (≤ 0: none; written back to the
  * gradient) fused with one torch.optim.Adam step (no weight decay, no amsgrad) over n_tensors

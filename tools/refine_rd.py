@@ -11,8 +11,14 @@ First a small sweep chooses the learning rate (``refine_lr``, in units of Δ): i
 first six images, the candidate with the lowest mean objective relative to the plain one. The
 table is then made with that value, and it is what codec.DEFAULT_REFINE_LR records.
 
+``--distortion ms-ssim`` refines for bits + λ·H·W·(1 − MS-SSIM) with λ = L/Δ². The
+sweep then chooses L and the learning rate together, on the same six images at index 8 with K = 20:
+the pair whose refined point lies highest above those images' own plain curve in MS-SSIM at equal
+bpp (objectives under different λ do not compare). The table is made as above.
+
     python tools/refine_rd.py [--out profiles/refine_rd.txt] [--first 4] [--last 16]
                               [--iters 0,5,20,100] [--lr R]
+                              [--distortion ms-ssim [--lam L] [--lam-sweep 4,16,64,256]]
 """
 import argparse
 import json
@@ -34,10 +40,15 @@ ap.add_argument("--last", type=int, default=16)
 ap.add_argument("--iters", default="0,5,20,100")
 ap.add_argument("--lr", type=float, default=None, help="skip the sweep and use this value")
 ap.add_argument("--sweep", default="0.001,0.003,0.01,0.03,0.1")
+ap.add_argument("--distortion", choices=codec.REFINE_DISTORTIONS, default="mse",
+                help="ms-ssim: the objective of DESIGN.md §0o, λ = L/Δ² with L from --lam-sweep")
+ap.add_argument("--lam", type=float, default=None, help="ms-ssim: skip the sweep and use this L")
+ap.add_argument("--lam-sweep", default="4,16,64,256")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 ITERS = [int(v) for v in args.iters.split(",")]
 LAMBDA = 650.25
+MSSSIM = args.distortion == "ms-ssim"
 PORTRAIT = (3, 8, 9, 16, 17, 18)
 out = open(args.out, "w") if args.out else None
 
@@ -51,6 +62,8 @@ def emit(row):
 
 
 def lam_of(s):
+    if MSSSIM:   # 1 − MS-SSIM of the quantiser's error scales with Δ² as the squared error does
+        return codec.msssim_lambda(LAMBDA / codec.step_size(s) ** 2)
     return LAMBDA / codec.step_size(s) ** 2
 
 
@@ -61,11 +74,40 @@ net = net.to(dev).eval()
 imgs = [np.ascontiguousarray(synth.smooth_image_u8(100 + i, *((768, 512) if i in PORTRAIT
                                                              else (512, 768))).transpose(1, 2, 0))
         for i in range(24)]
-emit({"weights": "g9_weights_n192.npz", "images": "kodak-synth 24", "lambda": "650.25 / step^2",
-      "iters": ITERS})
+emit({"weights": "g9_weights_n192.npz", "images": "kodak-synth 24", "distortion": args.distortion,
+      "lambda": "L / step^2 (L: the sweep below)" if MSSSIM else "650.25 / step^2", "iters": ITERS})
 
 lr = args.lr
-if lr is None:
+if MSSSIM:
+    # λ and the learning rate together: index 8, K = 20, the first six images; the pair whose
+    # refined point lies highest above those six images' own plain curve in MS-SSIM at equal bpp
+    # (objectives under different λ do not compare)
+    near = [net.evaluate_images(imgs[:6], want_msssim=True, step=s) for s in range(5, 12)]
+    px = [float(np.mean([r["bpp"] for r in rows])) for rows in near][::-1]
+    pm = [float(np.mean([r["ms_ssim"] for r in rows])) for rows in near][::-1]
+    lams = [args.lam] if args.lam is not None else [float(v) for v in args.lam_sweep.split(",")]
+    lrs = [lr] if lr is not None else [float(v) for v in args.sweep.split(",")]
+    best = None
+    for L in lams:
+        for cand in lrs:
+            rows = net.evaluate_images(imgs[:6], want_msssim=True, step=8, refine=20,
+                                       refine_lambda=codec.msssim_lambda(L), refine_lr=cand)
+            bpp = float(np.mean([r["bpp"] for r in rows]))
+            ms = float(np.mean([r["ms_ssim"] for r in rows]))
+            gain = ms - float(np.interp(bpp, px, pm))
+            emit({"lambda_sweep": L, "lr_sweep": cand, "index": 8, "iters": 20, "images": 6,
+                  "kept": sum(r["refine_kept"] > 0 for r in rows), "bpp": round(bpp, 5),
+                  "ms_ssim": round(ms, 6), "ms_ssim_minus_plain_curve": round(gain, 6),
+                  "psnr_u8": round(float(np.mean([r["psnr_u8"] for r in rows])), 4),
+                  "mean_objective_over_plain": round(float(np.mean(
+                      [r["objective"] / r["objective_plain"] for r in rows])), 6)})
+            if px[0] <= bpp <= px[-1] and (best is None or gain > best[0]):
+                best = (gain, L, cand)
+    if best is None:
+        sys.exit("no candidate landed inside the plain curve of indices 5..11")
+    LAMBDA, lr = best[1], best[2]
+    emit({"lambda_at_index_8": LAMBDA})
+elif lr is None:
     best = None
     for cand in (float(v) for v in args.sweep.split(",")):
         rows = net.evaluate_images(imgs[:6], step=8, refine=20, refine_lambda=lam_of(8),
@@ -124,6 +166,9 @@ if 0 in curves:
                   "the indices inside the plain curve's range", "points": len(wins),
                   "above": sum(v > 0 for v in wins), "mean_db": round(float(np.mean(wins)), 4),
                   "min_db": round(min(wins), 4), "max_db": round(max(wins), 4),
-                  "mean_ms_ssim_diff": round(float(np.mean(wins_ms)), 6)})
+                  "mean_ms_ssim_diff": round(float(np.mean(wins_ms)), 6),
+                  **({"ms_ssim_above": sum(v > 0 for v in wins_ms),
+                      "min_ms_ssim_diff": round(min(wins_ms), 6),
+                      "max_ms_ssim_diff": round(max(wins_ms), 6)} if MSSSIM else {})})
 if out:
     out.close()

@@ -7,9 +7,12 @@ Per iteration: the training forward of the synthesis; its data gradient alone
 (autograd.synthesis_backward); the fused latent kernel (kernels.refine_step) against the sequence
 of existing kernels it replaces (step_noise_rate_bwd for the rate derivative, adam_step,
 quantise_steps, and step_noise_rate with zero noise as the per-image rate pass); the two small
-kernels. Then ``compress_images(step=8, refine=K)`` for K = 0, 5, 20, wall clock.
+kernels; for the MS-SSIM objective kernels.image_msssim_fwd_saved and
+kernels.image_msssim_bwd against the Uniform pair on ready fp32 planes of the same size and against
+the squared-error pair image_sse_device + refine_grad_recon. Then
+``compress_images(step=8, refine=K)`` for K = 0, 5, 20 and both objectives, wall clock.
 
-    python tools/refine_time.py [--rounds 15] [--precision h3] [--out profiles/refine_ab.txt]
+    python tools/refine_time.py [--rounds 15] [--precision h3] [--out profiles/refine_msssim_ab.txt]
 """
 import argparse
 import ctypes
@@ -120,7 +123,27 @@ with torch.no_grad(), kernels.precision_scope(mode):
         bJ.fill_(float("inf"))
         kernels.refine_keep(bits, sse, lam, status, None, qh, 1, bJ, bi, bb, bs, best, flag)
 
+    # the MS-SSIM objective: the canvas pair against the Uniform pair on ready
+    # fp32 planes of the same size (what ragged extents and the 8-bit conversion cost) and against
+    # the SSE pair image_sse_device + refine_grad_recon (what an iteration gains in cost)
+    ms_ws = kernels.image_msssim_grad_workspace(B, 256, 256, dev)
+    ms_out = (torch.empty(B, device=dev), torch.empty(1, device=dev, dtype=torch.int32))
+    ms_g = torch.full((B,), -8.0 * 256 * 256, device=dev)
+    recon = recon.contiguous()
+    ms_d = torch.empty_like(recon)
+    X = (torch.round(recon.clamp(0, 1) * 255) / 255).contiguous()
+    Y = x.contiguous()
+    uni_ws = [None]
+
+    def uniform_fwd():
+        _, uni_ws[0] = kernels.ms_ssim_fwd_saved(X, Y, want_dy=False)
+
     arms = {
+        "image_msssim_fwd_saved": lambda: kernels.image_msssim_fwd_saved(recon, packed, desc, ms_ws, ms_out),
+        "image_msssim_bwd": lambda: kernels.image_msssim_bwd(recon, packed, desc, ms_ws, ms_g, ms_d),
+        "ms_ssim_fwd_saved (ready fp32 planes, no dY)": uniform_fwd,
+        "ms_ssim_bwd (ready fp32 planes, dx only)": lambda: kernels.ms_ssim_bwd(
+            X, Y, uni_ws[0], ms_g, saved_dy=False, want_dy=False),
         "train_synthesis (forward)": lambda: m.train_synthesis(dec, y_deq, None, None),
         "synthesis_latent_grad": lambda: autograd.synthesis_latent_grad(dec, saved, g_recon, mode=m.name),
         "synthesis_backward (full)": lambda: autograd.synthesis_backward(dec, saved, g_recon, mode=m.name),
@@ -148,17 +171,26 @@ with torch.no_grad(), kernels.precision_scope(mode):
           round(med["synthesis_backward (full)"] - med["synthesis_latent_grad"], 4),
           "fused_over_unfused": round(med["refine_step (fused)"]
                                       / med["unfused: rate_bwd + adam + quantise + rate"], 4)})
+    emit({"msssim_pair_ms": round(med["image_msssim_fwd_saved"] + med["image_msssim_bwd"], 4),
+          "uniform_pair_on_ready_planes_ms":
+          round(med["ms_ssim_fwd_saved (ready fp32 planes, no dY)"]
+                + med["ms_ssim_bwd (ready fp32 planes, dx only)"], 4),
+          "sse_pair_ms": round(med["image_sse_device"] + med["refine_grad_recon"], 4)})
 
-    for K in (0, 5, 20):
-        net.compress_images(imgs, step=8, refine=K, refine_lambda=LAM)
-        ts = []
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            net.compress_images(imgs, step=8, refine=K, refine_lambda=LAM)
-            torch.cuda.synchronize()
-            ts.append(1e3 * (time.perf_counter() - t0))
-        emit({"compress_images": f"step=8, refine={K}", "wall_ms": [round(v, 2) for v in sorted(ts)]})
+    for what, lam_of in (("mse", LAM), ("ms-ssim", codec.msssim_lambda(8.0))):
+        for K in (0, 5, 20):
+            if K == 0 and what != "mse":
+                continue
+            net.compress_images(imgs, step=8, refine=K, refine_lambda=lam_of)
+            ts = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                net.compress_images(imgs, step=8, refine=K, refine_lambda=lam_of)
+                torch.cuda.synchronize()
+                ts.append(1e3 * (time.perf_counter() - t0))
+            emit({"compress_images": f"step=8, refine={K}, {what}",
+                  "wall_ms": [round(v, 2) for v in sorted(ts)]})
 
 if args.out:
     with open(args.out, "w") as f:
