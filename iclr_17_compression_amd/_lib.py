@@ -133,6 +133,9 @@ SIGNATURES = {
     "iclr17_refine_keep": (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _I, _P, _P, _P, _P, _P, _P, _P]),
     "iclr17_refine_keep_msssim": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, _I, _P, _P, _P, _P, _P,
                                        _P, _P]),
+    "iclr17_recon_offsets": (_I, [_P, _I, _I, _P, _I, _I, _F, _P, _P]),
+    "iclr17_dequantise_recon": (_I, [_P, _I, _I, _I, _I, _F, _P, _I, _P, _P]),
+    "iclr17_dequantise_recon_map": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
     "iclr17_ms_ssim_workspace_size": (_SZ, [_I, _I, _I]),
     "iclr17_ms_ssim": (_I, [_P, _P, _I, _I, _I, _F, _P, _SZ, _P, _P]),
     "iclr17_ssim_workspace_size": (_SZ, [_I, _I, _I]),

@@ -803,6 +803,35 @@ def _per_image(name: str, value, n: int, check) -> List[float]:
     return [check(v.item() if isinstance(v, np.generic) else v) for v in per]
 
 
+# ------------------------------------------------------------------------------ reconstruction
+# Where the decoder places a level inside its bin: None / "centre" at Δ·ŷ, as ever;
+# "centroid" at the bin's mean under the rate model; "zero" the same for the zero bin alone.
+RECON_MODES = (None, "centre", "centroid", "zero")
+
+_RECON_NOT_BUILT = {
+    "psnr": "a quality target that knows the decoder's reconstruction points",
+    "msssim": "a quality target that knows the decoder's reconstruction points",
+    "refine": "refinement towards the decoder's reconstruction points",
+}
+RECON_WITH = {k: f"iclr17: codec: recon with {k}: {v} is not built (the search and the objective "
+                 "assume bin centres)" for k, v in _RECON_NOT_BUILT.items()}
+
+
+def recon_value(recon, strength=1.0) -> Optional[Tuple[str, float]]:
+    """``recon`` / ``recon_strength`` checked on the host: ``recon`` one of None, "centre",
+    "centroid", "zero"; ``strength`` a real number, not a bool, finite, in [0, 1]. → None for the
+    bin centre (None, "centre"), else (mode, strength)."""
+    if not (recon is None or isinstance(recon, str)) or recon not in RECON_MODES:
+        raise Iclr17Error(f"iclr17: codec: recon must be one of {RECON_MODES} (got {recon!r})")
+    if isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating)):
+        raise Iclr17Error(f"iclr17: codec: recon_strength must be a real number (got {strength!r})")
+    a = float(strength)
+    if not (math.isfinite(a) and 0.0 <= a <= 1.0):
+        raise Iclr17Error(f"iclr17: codec: recon_strength must be finite and in [0, 1] "
+                          f"(got {strength!r})")
+    return None if recon in (None, "centre") else (recon, a)
+
+
 # ------------------------------------------------------------------------------ refinement
 # refine_lr=None: the learning rate in units of Δ per Adam step that tools/refine_rd.py's sweep
 # chose (profiles/refine_rd.txt, DESIGN.md §0n)
@@ -1368,9 +1397,12 @@ def compress_images(net, images, max_batch: int = 64,
     return blobs
 
 
-def decode_groups(net, blobs, max_batch: int, refs=None):
+def decode_groups(net, blobs, max_batch: int, refs=None, recon=None, recon_strength=1.0):
     """``decompress_images``; with ``refs`` (the original uint8 images, one per blob) also each
-    image's Σ (decoded − original)² → ([uint8 HWC arrays], [int] | None)."""
+    image's Σ (decoded − original)² → ([uint8 HWC arrays], [int] | None). ``recon`` /
+    ``recon_strength``: ``recon_value``'s, for every blob of the call."""
+    recon_value(recon, recon_strength)   # before any device use
+    how_recon = {} if recon is None else {"recon": recon, "recon_strength": recon_strength}
     device = next(net.parameters()).device
     fp, N = fingerprint(net), net.out_channel_N
     parsed = [parse_blob(b, N, fp) for b in blobs]
@@ -1399,7 +1431,7 @@ def decode_groups(net, blobs, max_batch: int, refs=None):
         if isinstance(s0, TileInfo):
             how = {"step": s0.step, "tile": s0.tile}
         dec = net.decompress([blobs[i][starts[i]:] for i in idx], (Hc // 16, Wc // 16),
-                             streams_per_image=h0.P, K=h0.K, device=device, **how)
+                             streams_per_image=h0.P, K=h0.K, device=device, **how, **how_recon)
         shapes = [(heads[i].H, heads[i].W) for i in idx]
         ref = None
         if refs is not None:
@@ -1418,19 +1450,22 @@ def decode_groups(net, blobs, max_batch: int, refs=None):
     return out, sses
 
 
-def decode_region(net, blob, box, stats: Optional[dict] = None) -> np.ndarray:
+def decode_region(net, blob, box, stats: Optional[dict] = None, recon=None,
+                  recon_strength=1.0) -> np.ndarray:
     """``ImageCompressor.decompress_region``: the pixels ``box`` of one blob → uint8 [y1 − y0,
     x1 − x0, 3]. A tiled blob: the streams of ``region_window``'s tile rectangle are decoded into
     a compact latent (kernels.rans_decode_tiled), dequantised with the blob's step and synthesised
     as an image of its own; ``image_egress`` runs on the crop (from the 16-pixel grid line above
     and left of it: the egress takes canvases of multiples of 16). Any other blob is decoded
-    whole and cropped."""
+    whole and cropped. ``recon`` / ``recon_strength`` as ``decode_groups`` takes them: the compact
+    latent is dequantised with the step's offsets (kernels.dequantise_recon)."""
     from . import chain
+    rc = recon_value(recon, recon_strength)   # before any device use
     device = next(net.parameters()).device
     head, info = parse_blob(blob, net.out_channel_N, fingerprint(net))
     x0, y0, x1, y1 = _checked_box(head.H, head.W, box)
     if not isinstance(info, TileInfo):
-        full = decode_groups(net, [blob], 1)[0][0]
+        full = decode_groups(net, [blob], 1, recon=recon, recon_strength=recon_strength)[0][0]
         if stats is not None:
             stats["streams_decoded"] = stats["streams_total"] = head.P
         return np.ascontiguousarray(full[y0:y1, x0:x1])
@@ -1453,7 +1488,11 @@ def decode_region(net, blob, box, stats: Optional[dict] = None) -> np.ndarray:
                                       Hc // 16, Wc // 16, N, t, K, P, rect=win.tiles)
     if stats is not None:
         stats["streams_decoded"], stats["streams_total"] = len(picked), int(flat.size)
-    y_deq = kernels.dequantise_step(y_hat, step_size(info.step))
+    if rc is None:
+        y_deq = kernels.dequantise_step(y_hat, step_size(info.step))
+    else:
+        y_deq = kernels.dequantise_recon(y_hat, step_size(info.step),
+                                         net.bitEstimator.recon_offsets(K, info.step, *rc), K)
     m = chain.MODES[kernels.precision()]
     clipped, _, _ = m.synthesis(net.Decoder, y_deq, m.latent_operand(y_deq), None, False, False,
                                 None, False)
@@ -1470,8 +1509,16 @@ def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
                     step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
                     block: int = DEFAULT_BLOCK, rdo=None, rdo_weights=None,
                     tile: Optional[int] = None, psnr=None,
-                    estimate: bool = DEFAULT_ESTIMATE, msssim=None, refine=None,
-                    refine_lambda=None, refine_lr=None) -> List[dict]:
+                    estimate: bool = DEFAULT_ESTIMATE, recon=None, recon_strength=1.0,
+                    msssim=None, refine=None, refine_lambda=None, refine_lr=None) -> List[dict]:
+    # recon / recon_strength stand before the pinned tail (msssim, refine, refine_lambda,
+    # refine_lr: DESIGN.md §0o); everything from step= on is meant to be passed by name
+    rc = recon_value(recon, recon_strength)
+    if rc is not None:   # the search and the objective assume bin centres
+        for name, given in (("psnr", psnr is not None), ("msssim", msssim is not None),
+                            ("refine", bool(refine_value(refine)))):
+            if given:
+                raise Iclr17Error(RECON_WITH[name])
     imgs = [as_u8_hwc(im) for im in images]
     stats: dict = {}
     blobs = compress_images(net, imgs, max_batch=max_batch, step=step, max_bytes=max_bytes, bpp=bpp,
@@ -1479,7 +1526,8 @@ def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
                             tile=tile, psnr=psnr, estimate=estimate, msssim=msssim, stats=stats,
                             refine=refine, refine_lambda=refine_lambda, refine_lr=refine_lr)
     want_msssim = want_msssim or msssim is not None
-    recons, sses = decode_groups(net, blobs, max_batch, refs=imgs)
+    recons, sses = decode_groups(net, blobs, max_batch, refs=imgs, recon=recon,
+                                 recon_strength=recon_strength)
     device = next(net.parameters()).device
     res = []
     for im, blob, rec, sse in zip(imgs, blobs, recons, sses):
@@ -1502,6 +1550,8 @@ def evaluate_images(net, images, want_msssim: bool = False, max_batch: int = 64,
         for name in ("refine_kept", "objective", "objective_plain", "refine_iters"):
             if name in stats:
                 r[name] = stats[name][len(res)]
+        if recon is not None:   # "recon" is the decoded image: the mode goes by its own name
+            r["recon_mode"], r["recon_strength"] = recon, float(recon_strength)
         if "refine_distortion" in stats:   # an MS-SSIM refinement: the judged values (with
             for name in ("refine_distortion", "ms_ssim", "ms_ssim_plain"):   # want_msssim the decode's
                 r.setdefault(name, stats[name][len(res)])                    # own: the same bits)
@@ -1592,6 +1642,7 @@ def build_parser() -> argparse.ArgumentParser:
     dec.add_argument("--region", default=None, metavar="X0,Y0,X1,Y1",
                      help="decode this pixel box alone (half-open); of a tiled stream only the "
                           "tiles it needs are decoded")
+    _recon_arguments(dec)
     ev = sub.add_parser("eval", parents=[common], help="IMG...: one JSON line per image and a mean")
     ev.add_argument("images", nargs="+")
     ev.add_argument("--ms-ssim", action="store_true")
@@ -1604,7 +1655,17 @@ def build_parser() -> argparse.ArgumentParser:
     ev.add_argument("--msssim", type=float, default=None, metavar="T",
                     help="MS-SSIM target per image (not with --steps, --rdo or --psnr)")
     _refine_arguments(ev, "--steps or none")
+    _recon_arguments(ev)
     return ap
+
+
+def _recon_arguments(parser) -> None:
+    parser.add_argument("--recon", choices=[m for m in RECON_MODES if m], default=None, metavar="M",
+                        help="where the decoder places a level in its bin: centre (the default), "
+                             "centroid (the bin's mean under the rate model) or zero (the mean "
+                             "for the zero bin alone); costs no bits, any stream decodes with it")
+    parser.add_argument("--recon-strength", type=float, default=1.0, metavar="A",
+                        help="0 <= A <= 1: the share of the way from the centre to the mean")
 
 
 def _refine_arguments(parser, goes_with: str) -> None:
@@ -1653,6 +1714,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                          rdo=args.rdo, psnr=args.psnr, msssim=args.msssim,
                          step_offsets=[None] if getattr(args, "roi", None) else None,
                          **_refine_of(args))
+    if args.cmd != "encode":   # the same, for the reconstruction point
+        how_recon = ({} if args.recon is None and args.recon_strength == 1.0 else
+                     {"recon": args.recon, "recon_strength": args.recon_strength})
+        if recon_value(args.recon, args.recon_strength) is not None:
+            for name in ("psnr", "msssim", "refine"):
+                if getattr(args, name, None):
+                    raise Iclr17Error(RECON_WITH[name])
     net = _model(args)
     with kernels.precision_scope(args.precision or kernels.precision()):
         if args.cmd == "encode":
@@ -1671,9 +1739,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             with open(args.input, "rb") as f:
                 blob = f.read()
             if args.region is None:
-                image = net.decompress_images([blob])[0]
+                image = net.decompress_images([blob], **how_recon)[0]
             else:
-                image = net.decompress_region(blob, _region(args.region))
+                image = net.decompress_region(blob, _region(args.region), **how_recon)
             Image.fromarray(image).save(args.output, format="PNG")
         else:
             imgs = [_load_image(p) for p in args.images]
@@ -1681,8 +1749,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             for step in steps:
                 rows = net.evaluate_images(imgs, want_msssim=args.ms_ssim, step=step,
                                            rdo=args.rdo, psnr=args.psnr, msssim=args.msssim,
-                                           **_refine_of(args))
+                                           **_refine_of(args), **how_recon)
                 tag = {} if step is None else {"step": step}
+                if args.recon is not None:
+                    tag["recon"] = args.recon
+                    tag["recon_strength"] = args.recon_strength
                 if args.psnr is not None:
                     tag["psnr"] = args.psnr
                 if args.msssim is not None:

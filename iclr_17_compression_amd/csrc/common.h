@@ -147,6 +147,22 @@ __device__ __forceinline__ float bitparm_cdf(float v, const float* __restrict__ 
   return 1.0f / (1.0f + expf(-t));        // torch.sigmoid
 }
 
+// The same function in float64 on the fp32 pack, for what only the decoder derives from the model
+// (recon.hip): nothing here has to match the fp32 rate path, it has to be accurate.
+__device__ __forceinline__ double bitparm_cdf64(double v, const float* __restrict__ rp, int C,
+                                                int c) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double sp = (double)rp[(3 * k + 0) * C + c];
+    const double bb = (double)rp[(3 * k + 1) * C + c];
+    const double ta = (double)rp[(3 * k + 2) * C + c];
+    const double t = v * sp + bb;
+    v = t + tanh(t) * ta;
+  }
+  const double t = v * (double)rp[9 * C + c] + (double)rp[10 * C + c];
+  return 1.0 / (1.0 + exp(-t));
+}
+
 // model.py:71-73 per element: clamp(-log(F(z+.5) - F(z-.5) + 1e-10) / ln 2, 0, 50)
 __device__ __forceinline__ float element_bits(float z, const float* __restrict__ rp, int C, int c) {
   const float hi = bitparm_cdf(z + 0.5f, rp, C, c);

@@ -1541,6 +1541,83 @@ def rans_decode_map(words: Tensor, offsets: Tensor, cum: Tensor, slots, block: i
 
 
 # ------------------------------------------------------------ tiled streams (csrc/rans.hip, §0k)
+# ---------------------------------------------------- centroid reconstruction (csrc/recon.hip)
+RECON_MODES = {"centroid": 0, "zero": 1}   # ICLR17_RECON_CENTROID / ICLR17_RECON_ZERO
+
+
+def _levels(K, what: str) -> int:
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= 1024:
+        raise Iclr17Error(f"iclr17: {what}: K must be an integer in 1..1024 (got {K!r})")
+    return int(K)
+
+
+def recon_offsets(rate_packed: Tensor, N: int, K: int, steps: Sequence[float], mode: str,
+                  strength: float = 1.0) -> Tensor:
+    """The reconstruction offsets of 1..32 steps → fp32 [S, N, 2K + 1]: entry [s, c, v + K] is
+    ``strength`` times the mean of level v's bin under channel c's rate model at step steps[s],
+    minus v, in level units (clamped to ±½; 0 where the bin's probability is below 2⁻²⁴).
+    ``mode``: "centroid" (every level) or "zero" (the zero bin only, the rest 0). ``rate_packed``
+    is the UNscaled pack. Float64 on the device, deterministic."""
+    _rate_pack(rate_packed, N, "recon_offsets")
+    K = _levels(K, "recon_offsets")
+    if mode not in RECON_MODES:
+        raise Iclr17Error(f"iclr17: recon_offsets: mode must be one of {tuple(RECON_MODES)} "
+                          f"(got {mode!r})")
+    if (isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating))
+            or not 0.0 <= float(strength) <= 1.0):
+        raise Iclr17Error(f"iclr17: recon_offsets: strength must be a real number in [0, 1] "
+                          f"(got {strength!r})")
+    arr, S = _steps_arg(steps, "recon_offsets")
+    off = torch.empty(S, N, 2 * K + 1, device=rate_packed.device, dtype=torch.float32)
+    call("iclr17_recon_offsets", _p(rate_packed.contiguous()), N, K, arr, S, RECON_MODES[mode],
+         ctypes.c_float(float(strength)), _p(off), _stream(rate_packed))
+    return off
+
+
+def _recon_table(off: Tensor, shape, what: str) -> Tensor:
+    if (not isinstance(off, torch.Tensor) or off.device.type != "cuda" or off.dtype != torch.float32
+            or tuple(off.shape) != tuple(shape)):
+        raise Iclr17Error(f"iclr17: {what}: the offsets must be an fp32 GPU tensor "
+                          f"{list(shape)}")
+    return off.contiguous()
+
+
+def dequantise_recon(y_hat: Tensor, step: float, off: Tensor, K: int = ENTROPY_K) -> Tensor:
+    """step·(ŷ + off[c, ŷ + K]) for |ŷ| ≤ K and step·ŷ beyond (escapes, non-finite values): ŷ fp32
+    NHWC [B,h,w,N], ``off`` fp32 [N, 2K + 1] (one set of ``recon_offsets``). One fp32 add, then
+    ``dequantise_step``'s product: a zero table gives its output."""
+    _check(y_hat, "latent", 4)
+    B, h, w, N = y_hat.shape
+    K = _levels(K, "dequantise_recon")
+    off = _recon_table(off, (N, 2 * K + 1), "dequantise_recon")
+    d = _step_value(step, "dequantise_recon")
+    y_hat = y_hat.contiguous()
+    out = torch.empty_like(y_hat)
+    call("iclr17_dequantise_recon", _p(y_hat), B, h, w, N, ctypes.c_float(d), _p(off), K, _p(out),
+         _stream(y_hat))
+    return out
+
+
+def dequantise_recon_map(y_hat: Tensor, slots, block: int, steps: Sequence[float], off: Tensor,
+                         K: int = ENTROPY_K) -> Tensor:
+    """``dequantise_recon`` with a step and a table per block: ``slots`` [B, mh, mw] with values
+    < S, ``steps`` the S step sizes and ``off`` fp32 [S, N, 2K + 1] their ``recon_offsets``; a
+    block of slot t is reconstructed with steps[t] and off[t]. A zero table gives
+    ``dequantise_step_map``'s output."""
+    _check(y_hat, "latent", 4)
+    B, h, w, N = y_hat.shape
+    K = _levels(K, "dequantise_recon_map")
+    arr, S = _steps_arg(steps, "dequantise_recon_map")
+    off = _recon_table(off, (S, N, 2 * K + 1), "dequantise_recon_map")
+    sl = _map_on(y_hat.device, slots, "dequantise_recon_map", "slots", B, h, w, block, 0, S - 1,
+                 np.uint8)
+    y_hat = y_hat.contiguous()
+    out = torch.empty_like(y_hat)
+    call("iclr17_dequantise_recon_map", _p(y_hat), B, h, w, N, _p(sl), MAP_BLOCKS.index(block), arr,
+         _p(off), S, K, _p(out), _stream(y_hat))
+    return out
+
+
 TILES = (8, 16, 32, 64)        # tile edges t of the tiled coder, in latent positions
 TILE_WAVES = (1, 2, 4, 8, 16)  # waves per workgroup of the tiled kernels (one stream each)
 

@@ -464,20 +464,28 @@ class ImageCompressor(nn.Module):
     def decompress(self, strings, shape, streams_per_image: int = kernels.STREAMS_PER_IMAGE,
                    K: int = kernels.ENTROPY_K, device=None, step: Optional[int] = None,
                    step_map=None, block: int = 4,
-                   tile: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                   tile: Optional[int] = None, recon=None,
+                   recon_strength=1.0) -> Dict[str, torch.Tensor]:
         """Inverse of ``compress``: byte strings → {"y_hat": NCHW latents, "x_hat": the clipped
         reconstruction} (bit-identical latents; the synthesis as in ``forward``). With ``step``
         the inverse of ``compress_latents`` at that ladder step: the step's tables decode ŷ, and
         the synthesis runs on Δ·ŷ as a general (non-integer) latent. With ``step_map`` /
         ``block`` the inverse of ``compress_latents(step_map=…)``; with ``tile`` the inverse of
-        ``compress`` / ``compress_latents`` with that tile edge."""
+        ``compress`` / ``compress_latents`` with that tile edge.
+
+        ``recon`` / ``recon_strength`` (codec.recon_value): "centroid" places every
+        level at ``recon_strength`` of the way from its bin's centre to the bin's mean under the
+        rate model, "zero" the zero bin alone; the synthesis then runs on Δ·(ŷ + offset)
+        (kernels.dequantise_recon / dequantise_recon_map; a plain stream counts as ladder index
+        8). None and "centre" are the call without them: no other kernel, the same bytes."""
+        from . import codec
+        rc = codec.recon_value(recon, recon_strength)   # before any device use
         if step is not None and step_map is not None:
             raise kernels.Iclr17Error("iclr17: decompress: step and step_map given together")
         P, N = streams_per_image, self.out_channel_N
         h, w = shape
         if tile is not None:
             if step_map is not None:
-                from . import codec
                 raise kernels.Iclr17Error(codec.TILE_WITH_MAP)
             th, tw = kernels.tile_grid(h, w, tile)
             P = th * tw * streams_per_image   # streams per image
@@ -509,16 +517,26 @@ class ImageCompressor(nn.Module):
             y_hat = kernels.rans_decode_map(words, offsets, tables, slots, block, B, h, w, N, K, P)
         m = chain.MODES[kernels.precision()]
         if step_map is not None:
-            from . import codec
-            y_deq = kernels.dequantise_step_map(y_hat, step_map, block,
-                                                [codec.step_size(s) for s in range(codec.STEPS)])
+            if rc is None:
+                y_deq = kernels.dequantise_step_map(y_hat, step_map, block,
+                                                    [codec.step_size(s) for s in range(codec.STEPS)])
+            else:   # _map_tables' slots: the indices the map uses, ascending
+                used = [int(e) for e in np.unique(np.asarray(step_map))]
+                y_deq = kernels.dequantise_recon_map(
+                    y_hat, slots, block, [codec.step_size(s) for s in used],
+                    self.bitEstimator.stacked_recon_offsets(K, used, *rc), K)
+            clipped, _, _ = m.synthesis(self.Decoder, y_deq, m.latent_operand(y_deq), None, False,
+                                        False, None, False)
+        elif rc is not None:
+            e = codec.UNIT_STEP if step is None else step
+            y_deq = kernels.dequantise_recon(y_hat, codec.step_size(e),
+                                             self.bitEstimator.recon_offsets(K, e, *rc), K)
             clipped, _, _ = m.synthesis(self.Decoder, y_deq, m.latent_operand(y_deq), None, False,
                                         False, None, False)
         elif step is None:
             clipped, _, _ = m.synthesis(self.Decoder, y_hat, m.latent_operand(y_hat), None, False,
                                         True, None, False)
         else:
-            from . import codec
             y_deq = kernels.dequantise_step(y_hat, codec.step_size(step))
             clipped, _, _ = m.synthesis(self.Decoder, y_deq, m.latent_operand(y_deq), None, False,
                                         False, None, False)
@@ -637,7 +655,7 @@ class ImageCompressor(nn.Module):
                                     refine_lr, stats)
 
     @torch.no_grad()
-    def decompress_images(self, blobs, max_batch: int = 64):
+    def decompress_images(self, blobs, max_batch: int = 64, recon=None, recon_strength=1.0):
         """Inverse of ``compress_images``: blobs → uint8 HWC numpy arrays of the true sizes, in
         input order (``decompress`` per canvas batch, then kernels.image_egress: round-half-even of
         the clipped reconstruction·255, cropped). Plain (I17C), stepped (I17Q), mapped (I17M) and
@@ -645,27 +663,34 @@ class ImageCompressor(nn.Module):
         ones: of one block edge; tiled ones: of one tile edge). Raises Iclr17Error on a foreign or truncated blob, a corrupt step map,
         another N or other weights (the header's fingerprint). Within one precision mode
         the bytes are reproducible and independent of the batch; between modes a pixel may differ
-        by one 8-bit step."""
+        by one 8-bit step. ``recon`` / ``recon_strength`` as ``decompress`` takes them, for every
+        blob of the call whatever its kind."""
         from . import codec
-        return codec.decode_groups(self, list(blobs), max_batch)[0]
+        return codec.decode_groups(self, list(blobs), max_batch, recon=recon,
+                                   recon_strength=recon_strength)[0]
 
     @torch.no_grad()
-    def decompress_region(self, blob, box, stats: Optional[dict] = None):
+    def decompress_region(self, blob, box, stats: Optional[dict] = None, recon=None,
+                          recon_strength=1.0):
         """The pixels ``box`` = (x0, y0, x1, y1) (half-open, inside the image) of one blob → uint8
         [y1 − y0, x1 − x0, 3], byte for byte ``decompress_images([blob])[0][y0:y1, x0:x1]``. Of a
         tiled (I17T) blob only the streams of the tiles that cover the latent positions the box
         depends on (codec.region_window) are decoded, and the synthesis runs on that rectangle of
         the latent as an image of its own; any other blob is decoded whole. ``stats`` (a dict)
-        receives "streams_decoded" and "streams_total"."""
+        receives "streams_decoded" and "streams_total". ``recon`` / ``recon_strength`` as
+        ``decompress_images`` takes them; the equality above holds with the same two arguments on
+        both sides."""
         from . import codec
-        return codec.decode_region(self, blob, box, stats)
+        return codec.decode_region(self, blob, box, stats, recon=recon,
+                                   recon_strength=recon_strength)
 
     @torch.no_grad()
     def evaluate_images(self, images, want_msssim: bool = False, max_batch: int = 64,
                         step: Optional[int] = None, max_bytes=None, bpp=None, step_offsets=None,
                         block: int = 4, rdo=None, rdo_weights=None, tile: Optional[int] = None,
-                        psnr=None, estimate: Optional[bool] = None, msssim=None, refine=None,
-                        refine_lambda=None, refine_lr=None):
+                        psnr=None, estimate: Optional[bool] = None, recon=None,
+                        recon_strength=1.0, msssim=None, refine=None, refine_lambda=None,
+                        refine_lr=None):
         """The real codec path per image, compress_images then decompress_images, measured on
         the 8-bit decoded image as codecs are reported: a dict per image with ``bytes``, ``bpp`` =
         8·len(blob)/(H·W) (header included, true pixel count), ``sse_u8`` (int), ``psnr_u8`` =
@@ -679,8 +704,11 @@ class ImageCompressor(nn.Module):
         row's ``step`` is the index found; so is ``msssim``, whose rows also carry ``ms_ssim`` and
         ``ms_ssim_db`` as ``want_msssim`` gives them. ``refine`` / ``refine_lambda`` /
         ``refine_lr`` as in ``compress_images``: the rows then also carry ``refine_kept``,
-        ``objective``, ``objective_plain`` and ``refine_iters``. Precision as
-        ``decompress_images``."""
+        ``objective``, ``objective_plain`` and ``refine_iters``. ``recon`` /
+        ``recon_strength`` as ``decompress_images`` takes them (the encode is untouched): the rows
+        then also carry ``recon_mode`` and ``recon_strength`` (``recon`` is the decoded image);
+        with ``psnr``, ``msssim`` or ``refine`` a codec.RECON_WITH "is not built" error. Precision
+        as ``decompress_images``."""
         from . import codec
         return codec.evaluate_images(self, images, want_msssim, max_batch, step=step,
                                      max_bytes=max_bytes, bpp=bpp, step_offsets=step_offsets,
@@ -688,7 +716,8 @@ class ImageCompressor(nn.Module):
                                      psnr=psnr,
                                      estimate=codec.DEFAULT_ESTIMATE if estimate is None else estimate,
                                      msssim=msssim, refine=refine, refine_lambda=refine_lambda,
-                                     refine_lr=refine_lr)
+                                     refine_lr=refine_lr, recon=recon,
+                                     recon_strength=recon_strength)
 
     @torch.no_grad()
     def evaluate(self, x: torch.Tensor, want_y: bool = False,

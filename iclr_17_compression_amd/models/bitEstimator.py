@@ -97,6 +97,33 @@ class BitEstimator(nn.Module):
             kept = self._pack.get(f"cdf{K}_map", ps, build, force=True)
         return kept[1]
 
+    def recon_offsets(self, K: int, step: int, mode: str, strength: float = 1.0):
+        """The reconstruction offsets of ladder step ``step`` (kernels.recon_offsets: fp32
+        [C, 2K + 1], ``mode`` "centroid" or "zero"), cached like ``entropy_tables``."""
+        from ..codec import step_size
+        ps = self.params_in_order()
+        return self._pack.get(
+            f"recon{K}_s{step}_{mode}_{float(strength)!r}", ps,
+            lambda: kernels.recon_offsets(self.packed(), self.channel, K, [step_size(step)], mode,
+                                          strength)[0])
+
+    def stacked_recon_offsets(self, K: int, steps, mode: str, strength: float = 1.0):
+        """``recon_offsets`` of the ladder steps ``steps`` (ascending, distinct) as fp32
+        [S, C, 2K + 1], from one launch, for the mapped dequantiser. The last stack is kept, as
+        ``stacked_tables`` keeps its."""
+        from ..codec import step_size
+        ps = self.params_in_order()
+        want = (tuple(int(s) for s in steps), mode, float(strength))
+
+        def build():
+            return want, kernels.recon_offsets(self.packed(), self.channel, K,
+                                               [step_size(s) for s in want[0]], mode, strength)
+
+        kept = self._pack.get(f"recon{K}_map", ps, build)
+        if kept[0] != want:
+            kept = self._pack.get(f"recon{K}_map", ps, build, force=True)
+        return kept[1]
+
     def forward(self, x):
         # bitEstimator.py:38-42
         from ..autograd import BitEstimatorFn, needs_grad

@@ -496,6 +496,35 @@ int iclr17_refine_keep_msssim(const double* bits, const float* ms, const double*
                               double* best_bits, float* best_ms, float* best, int32_t* flag,
                               void* stream);
 
+/* ------------------------------------------------------- centroid reconstruction (csrc/recon.hip)
+ * A decoder-side choice of the reconstruction point; no stream changes. With F_c
+ * the rate model's CDF of channel c (float64 on the fp32 pack) and Δ a step, level v's bin has
+ * a = F_c(Δ(v − ½)), b = F_c(Δ(v + ½)), p = b − a and the mean v + (½(a + b) − I)/p in level units,
+ * I = ∫_{−½}^{½} F_c(Δ(v + u)) du by composite Simpson (512 sub-intervals, summed k = 0..512). */
+#define ICLR17_RECON_CENTROID 0   /* every level |v| ≤ K */
+#define ICLR17_RECON_ZERO 1       /* the zero bin only */
+/* off[s][c][v + K] (fp32 [S][N][2K + 1]) = strength · clamp((½(a + b) − I)/p, −½, ½) at step
+ * steps[s] where p ≥ 2⁻²⁴, else 0; with ICLR17_RECON_ZERO every entry but v = 0 is 0. rate_packed
+ * is the UNscaled pack; steps is a host array of S ≤ 32 steps, copied at the call; K in 1..1024;
+ * 0 ≤ strength ≤ 1. Evaluated in float64, one thread per entry (ICLR17_RECON_ZERO: per step and
+ * channel, on a table zeroed by a memset on the stream): deterministic. */
+int iclr17_recon_offsets(const float* rate_packed, int N, int K, const float* steps, int S,
+                         int mode, float strength, float* off, void* stream);
+/* y_deq = step ⊗ (y_hat ⊕ off[c][y_hat + K]) for |y_hat| ≤ K and step ⊗ y_hat otherwise (escapes,
+ * infinities, NaN): one fp32 add, then iclr17_dequantise_step's product, so a zero table gives
+ * its output. y_hat, y_deq: fp32 NHWC [B][h][w][N]; off: fp32 [N][2K + 1], staged in LDS where it
+ * fits 64 KiB, else read from global memory. Nothing is read past the table, whatever y_hat
+ * holds. */
+int iclr17_dequantise_recon(const float* y_hat, int B, int h, int w, int N, float step,
+                            const float* off, int K, float* y_deq, void* stream);
+/* The same with a step and a table per block: Δ = steps[t] and off[t][c] with t = slots[b][block]
+ * (device u8 [B][mh][mw] as iclr17_rans_decode_map's, each < S; a larger one reads set S − 1);
+ * steps: a host array of S ≤ 32 steps, copied at the call; off: fp32 [S][N][2K + 1], read from
+ * global memory. A zero table gives iclr17_dequantise_step_map's output. */
+int iclr17_dequantise_recon_map(const float* y_hat, int B, int h, int w, int N,
+                                const uint8_t* slots, int log2_g, const float* steps,
+                                const float* off, int S, int K, float* y_deq, void* stream);
+
 /* testKodak's MS-SSIM (train.py:178 → models/ms_ssim_torch.py:123-196): per-image
  * ms_ssim(x, y, data_range) of NCHW [B,3,H,W] fp32 images, 11-tap σ=1.5 window, 5 levels (each
  * level must be ≥ 11×11: H, W ≥ 161 or so), the reference's level weights and final product.
